@@ -13,6 +13,11 @@ medians/LR/range -> interpolate; plane module: vertical derivative + histogram -
 per GPU, D=128, inputs resident in HBM.  Frames shard by id across ranks (weak scaling); the only
 exchange is the all-gather of per-frame 256-bin histograms for the plane-parameter schedule.
 Prints ONE JSON line on rank 0.
+
+A plain run does only what the headline needs: set-up (engine, inputs, placement search), warm-up, ONE timed block of exactly
+--steps steps, the outputs of the last timed step when --dump-outputs DIR is given, the line.  --full adds everything else the
+line has carried: the median of --repeats blocks, the untuned and the event-free blocks, the copy rate, the 8UC3 and the
+PCIe-inclusive legs, the CPU baseline and the check of the timed outputs against the oracle ("verified").
 """
 import argparse
 import json
@@ -25,6 +30,40 @@ sys.path.insert(0, os.path.join(ROOT, "cart-slam_amd"))
 
 _REAL_STDOUT = 1   # file descriptor the JSON line is written to (main() moves descriptor 1 out of librccl's way)
 HBM_PEAK_GBS = 8000.0  # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8 TB/s (6.3 TB/s achievable)
+
+
+DUMP_BYTES = 64_000_000   # --dump-outputs writes at most this much
+DUMP_SEED = 1242375
+
+
+def dump_outputs(out, path):
+    """--dump-outputs: the arrays StereoPipeline.process_batch hands its caller (`out`, this rank's last timed step) as
+    path/<name>.npy -- float32 for the 8- and 16-bit outputs, float64 for the 32-bit ones (both exact).  Rows of the component
+    table past a frame's n_components are undefined (include/cart_engine.h) and are written as 0.  Smallest first, an array is
+    written whole while it fits an equal share of what is left of DUMP_BYTES; a larger one is written flattened, as the elements at
+    the sorted indices numpy.random.default_rng(DUMP_SEED).choice(size, n, replace=False) -- the same for every run and build."""
+    import numpy as np
+    import torch
+    arrays = {}
+    for k, v in out.items():
+        if not torch.is_tensor(v):
+            continue   # "done": the event after which the outputs are complete
+        a = v.cpu().numpy()
+        if k == "components":
+            nc = np.minimum(out["n_components"].cpu().numpy(), a.shape[1])
+            a = np.where((np.arange(a.shape[1])[None, :] < nc[:, None])[..., None], a, 0)
+        arrays[k] = a.astype(np.float32 if a.dtype.itemsize <= 2 else np.float64)
+    os.makedirs(path, exist_ok=True)
+    left = DUMP_BYTES
+    names = sorted(arrays, key=lambda k: arrays[k].nbytes)
+    for i, k in enumerate(names):
+        a = arrays[k]
+        n = (left // (len(names) - i) - 256) // a.itemsize   # 256: room for the .npy header
+        if a.size > n:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(DUMP_SEED).choice(a.size, n, replace=False))]
+        f = os.path.join(path, k + ".npy")
+        np.save(f, a)
+        left -= os.path.getsize(f)
 
 
 def alg_bytes_per_pair(w, h, D, P):
@@ -170,7 +209,11 @@ def main():
                     "the search ends at the first fast set, or after six tries on a box that has none: include/cart_engine.h, cart_engine_tune_placement)")
     ap.add_argument("--no-overlap", action="store_true", help="run the plane stages on the main stream (no two-stream pipelining of consecutive batches)")
     ap.add_argument("--overlap", action="store_true", help="force the two-stream pipelining (the default)")
-    ap.add_argument("--repeats", type=int, default=5, help="the timed block of --steps steps is run this many times; `value` is the median block, `spread` the fastest / slowest")
+    ap.add_argument("--full", action="store_true", help="also run what the headline does not need (module docstring): the informational blocks and legs, "
+                    "the CPU baseline and the check of the timed outputs against the oracle")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the outputs of the last timed step as DIR/<name>.npy (dump_outputs: at most 64 MB)")
+    ap.add_argument("--repeats", type=int, default=None, help="the timed block of --steps steps is run this many times (default 1, with --full 5); "
+                    "`value` is the median block, `spread` the fastest / slowest")
     ap.add_argument("--collective-timeout", type=float, default=120.0, help="seconds after which a torch.distributed call gives up (a dead peer then ends the job non-zero instead of hanging it)")
     ap.add_argument("--sequence", action="store_true", help="also time the batched-sequence mode (BASELINE configs[4]): frames start on rank 0, "
                     "are scattered frame k -> rank k mod N, outputs are gathered back on rank 0; informational, never `value`")
@@ -183,6 +226,8 @@ def main():
     ap.add_argument("--chunk", type=int, default=0, help="frames per launch sequence inside a batch (0 = engine default)")
     ap.add_argument("--plan", default="auto", choices=["auto", "slabs", "fused_up"], help="force a launch plan of the SGM core (all bit-identical)")
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
     if "RANK" not in os.environ and args.gpus > 1:
         sys.exit(launch_ranks(args))
 
@@ -263,17 +308,19 @@ def run(args, world, rank, dev_index):
             dist.barrier()
 
     # What a caller gets WITHOUT the placement search (every product path defaults to one try: modules.cpp, FrameSharder): one block of --steps
-    # steps on the placement the engine was created with, after its own pre-warm; informational (`placement_tuning.value_untuned`), never `value`.
+    # steps on the placement the engine was created with, after its own pre-warm; informational (`placement_tuning.value_untuned`, --full), never `value`.
     placement = None
     if args.placement_tries > 1:
         for _ in range(32 + args.warmup):   # the same pre-warm + warm-up the timed blocks get
             pipe.process_batch(left, right, inputs_ready=resident)
         barrier(); torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(args.steps):
-            pipe.process_batch(left, right, inputs_ready=resident)
-        torch.cuda.synchronize(); barrier()
-        untuned = world * B * args.steps / (time.perf_counter() - t0)   # this rank's clock: informational
+        untuned = None
+        if args.full:
+            t0 = time.perf_counter()
+            for _ in range(args.steps):
+                pipe.process_batch(left, right, inputs_ready=resident)
+            torch.cuda.synchronize(); barrier()
+            untuned = world * B * args.steps / (time.perf_counter() - t0)   # this rank's clock: informational
         # Untimed set-up, like the allocation itself: the engine times its two slab-bound launches on up to --placement-tries physical
         # placements of the slab workspace and keeps the fastest (include/cart_engine.h, cart_engine_tune_placement; profiles/r03_alloc.txt)
         # a dedicated bench process may hold whatever leaves 4 GiB free while it searches; ranks that share a card (rehearsals) keep to two units
@@ -287,7 +334,8 @@ def run(args, world, rank, dev_index):
                              "the slowest seen (a set with a launch in its slow mode was met and avoided); mixed = the sets differ by 1.5-5.5 %, the fastest is "
                              "kept; uniform = six sets within 1.5 % of each other (all fast or all slow: stages_ms_per_launch tells which -- the aggregation "
                              "launch of the headline configuration takes ~1.45 ms in its fast mode, ~1.55 in its slow one, the WTA 1.16-1.19 / 1.22-1.27)"}
-        placement["value_untuned"] = round(untuned, 2)
+        if untuned is not None:
+            placement["value_untuned"] = round(untuned, 2)
 
     # Untimed pre-warm, before the W warm-up steps the contract asks for: first touch of the workspaces (15 GB of slabs), code
     # object loads, allocator pools and the clock ramp of a GPU that has just been handed over idle.
@@ -320,6 +368,8 @@ def run(args, world, rank, dev_index):
     elapsed = sorted(blocks)[len(blocks) // 2]
     stages, ncalls = eng.collect_timing()
     eng.set_timing(False)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(last, args.dump_outputs)
     # what the LAST timed step produced for the first and the last frame of this rank's batch (checked against the oracle
     # below, outside every timed region)
     check_frames = sorted({0, B - 1})
@@ -327,18 +377,20 @@ def run(args, world, rank, dev_index):
                "params": [int(v) for v in last["params"][k].cpu().numpy()]} for k in check_frames} if rank == 0 else {}
     # Informational, never `value`: the same block of --steps steps once more WITHOUT the engine's stage events (six hipEventRecord per step on
     # the launch stream, ~0.02 ms per step: profiles/r04_overlap.txt) -- what the step does uninstrumented.  Same bracket, max over ranks.
-    barrier(); torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        pipe.process_batch(left, right, inputs_ready=resident)
-    torch.cuda.synchronize(); barrier()
-    dt_plain = time.perf_counter() - t0
-    if world > 1:
-        t = torch.tensor([dt_plain], dtype=torch.float64, device="cuda" if args.backend == "nccl" else "cpu")
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        dt_plain = float(t.item())
+    dt_plain = None
+    if args.full:
+        barrier(); torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            pipe.process_batch(left, right, inputs_ready=resident)
+        torch.cuda.synchronize(); barrier()
+        dt_plain = time.perf_counter() - t0
+        if world > 1:
+            t = torch.tensor([dt_plain], dtype=torch.float64, device="cuda" if args.backend == "nccl" else "cpu")
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            dt_plain = float(t.item())
     copy_gbps = None
-    if rank == 0:
+    if rank == 0 and args.full:
         # achievable-copy ceiling of THIS box ("quote both fractions"): device-to-device copy of 2 GiB,
         # bytes read + bytes written per second
         try:
@@ -379,7 +431,7 @@ def run(args, world, rank, dev_index):
     # B_alg).  The frames are the gray frames replicated into three channels: (1868 + 9617 + 4899) g + 8192 >> 14 == g, so the
     # disparities must equal the gray run's bit for bit, which is checked.
     bgr = None
-    if world == 1 and not args.no_bgr:   # one rank only: a step of the sharded pipeline is a collective
+    if args.full and world == 1 and not args.no_bgr:   # one rank only: a step of the sharded pipeline is a collective
         l3 = left.unsqueeze(-1).expand(-1, -1, -1, 3).contiguous()
         r3 = right.unsqueeze(-1).expand(-1, -1, -1, 3).contiguous()
         torch.cuda.synchronize()
@@ -396,7 +448,7 @@ def run(args, world, rank, dev_index):
                "disparity_equals_gray_run": bool(torch.equal(o3["disparity"], last["disparity"]))}
         del l3, r3, o3
     pcie = None
-    if world == 1 and not args.no_pcie:
+    if args.full and world == 1 and not args.no_pcie:
         # Informational (never `value`): the same step when the caller hands over HOST buffers -- H2D of the 16 pairs
         # from pinned memory, the hot path, D2H of disparity + planes into pinned memory, copies on their own stream.
         hl, hr = left.cpu().pin_memory(), right.cpu().pin_memory()
@@ -581,7 +633,8 @@ def run(args, world, rank, dev_index):
                                    "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(wta_bytes / (wta_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
                                    "traffic": measured_traffic("wta"), "traffic_source": "profiles/traffic.json" if measured_traffic("wta") else None,
                                    "alg_bytes_per_launch": wta_bytes, "launch_ms": round(wta_ms, 4)}
-        out["value_without_stage_events"] = round(world * B * args.steps / dt_plain, 2)   # informational: one untimed-by-events block after the timed ones
+        if dt_plain:
+            out["value_without_stage_events"] = round(world * B * args.steps / dt_plain, 2)   # informational: one untimed-by-events block after the timed ones
         if pcie:
             out["pcie_inclusive"] = pcie
             out["value_pcie_inclusive"] = pcie["pairs_per_s"]   # the same step with the pair uploaded and disparity + planes downloaded
@@ -595,7 +648,7 @@ def run(args, world, rank, dev_index):
         if placement:
             out["placement_tuning"] = placement
         verified = None
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             # the CPU leg: the oracle timed on the host cores (N = 1 only); the same child also hands back the oracle's outputs of
             # the first and the last frame of rank 0's batch, against which the LAST TIMED STEP's outputs are compared (outside
             # every timed region; with more than one rank the child only verifies)
@@ -617,7 +670,7 @@ def run(args, world, rank, dev_index):
                 verified = not bad
                 out["verification"] = {"frames": check_frames, "of": "the last timed step", "against": "oracle (cpu_baseline child): disparity bit-exact, "
                                        "plane labels bit-exact under the parameters the run used", "mismatches": bad}
-        out["verified"] = verified   # None: not checked (--no-cpu-baseline)
+        out["verified"] = verified   # None: not checked (a run without --full, or --no-cpu-baseline)
         sys.stdout.flush()
         os.write(_REAL_STDOUT, (json.dumps(out) + "\n").encode())
         if verified is False:

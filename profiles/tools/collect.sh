@@ -2,7 +2,7 @@
 # usage (GPU box): collect.sh <tag> <bench args...>: bench line (with CPU baseline / PCIe legs when FULL=1), rocprofv3 kernel stats of the
 # same command, SQ / FETCH_SIZE / WRITE_SIZE passes; everything lands in gpurun_out/<tag>/ for copying into profiles/
 export TMPDIR=/tmp; R=$GRAFT_REPO_ROOT; T=$1; shift; OUT=$R/gpurun_out/$T; mkdir -p $OUT
-EXTRA="--no-cpu-baseline --no-pcie"; [ "$FULL" = 1 ] && EXTRA="--latency"
+EXTRA="--no-cpu-baseline --no-pcie"; [ "$FULL" = 1 ] && EXTRA="--full --latency"
 cd $R && timeout -k 10 400 python3 bench.py $EXTRA "$@" > $OUT/bench.json 2> $OUT/bench.err || { tail -5 $OUT/bench.err; exit 1; }
 python3 -c 'import json,sys; d=json.loads(open(sys.argv[1]).read()); print(sys.argv[2], d["value"], d["ms_per_step"], d["stages_ms_per_launch"], d["roofline"]["frac"], d.get("value_pcie_inclusive"))' $OUT/bench.json $T
 cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o s -- python3 $R/bench.py --no-cpu-baseline --no-pcie --no-bgr "$@" > $OUT/bench_under_rocprof.json 2> $OUT/stats.log

@@ -2,7 +2,7 @@
 # GPU box, round 5, first call: baseline bench line of this box, the format of rocprofv3's JSON counter records (per-instance values?), and the
 # DRAM-destined read counters of the 1080p aggregation launch.
 export TMPDIR=/tmp; R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r05_first; mkdir -p $O; cd $R
-timeout -k 10 400 python3 bench.py > $O/bench_default.json 2> $O/bench_default.err; echo "bench default rc=$?" | tee -a $O/progress.txt
+timeout -k 10 400 python3 bench.py --full > $O/bench_default.json 2> $O/bench_default.err; echo "bench default rc=$?" | tee -a $O/progress.txt
 cd /tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --pmc TCC_EA0_WRREQ_STALL TCC_EA0_WRREQ --kernel-include-regex "aggregate_kernel" --output-format json csv -d $O/pmc_json -o j -- python3 $R/bench.py --steps 2 --warmup 1 --repeats 1 --no-cpu-baseline --no-pcie --no-bgr --no-overlap --placement-tries 8 > $O/pmc_json.log 2>&1; echo "pmc json rc=$?" | tee -a $O/progress.txt
 ls -la $O/pmc_json/* | tee -a $O/progress.txt

@@ -22,7 +22,7 @@ def one_json_line(stdout):
 
 
 def test_single_gpu_line_is_verified_and_complete():
-    pr = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + SMALL, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=540)
+    pr = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full"] + SMALL, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=540)
     assert pr.returncode == 0, pr.stderr.decode(errors="replace")[-3000:]
     d = one_json_line(pr.stdout)
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data",
@@ -50,13 +50,42 @@ def test_single_gpu_line_is_verified_and_complete():
     assert pt["value_untuned"] > 0 and pt["seconds"] < 12
 
 
+def test_plain_run_times_its_steps_and_dumps_the_same_outputs(tmp_path):
+    """Without --full: one timed block of exactly --steps steps and none of the --full legs; --dump-outputs writes what the last timed
+    step handed its caller, the same in two fresh processes, and its disparity is the oracle's."""
+    import numpy as np
+    import oracle_lib as O
+    from cartslam import synth
+    dumps = []
+    for i in range(2):
+        out = tmp_path / str(i)
+        pr = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--batch", "4", "--width", "320", "--height", "96",
+                             "--disparities", "64", "--dump-outputs", str(out)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
+        assert pr.returncode == 0, pr.stderr.decode(errors="replace")[-3000:]
+        d = one_json_line(pr.stdout)
+        assert d["steps"] == 3 and d["repeats"] == 1 and d["value"] > 0 and d["unit"] == "stereo-pairs/sec" and d["dtype"] == "u8"
+        assert abs(d["value"] - 4 * 3 / (d["ms_per_step"] * 3e-3)) / d["value"] < 1e-3
+        for k in ("cpu_baseline", "verification", "bgr_input", "pcie_inclusive", "value_without_stage_events"):
+            assert k not in d, k
+        assert d["verified"] is None and "value_untuned" not in d["placement_tuning"] and d["roofline"]["copy_rate_GBps"] is None
+        dumps.append({f.name: np.load(f) for f in out.iterdir()})
+    assert set(dumps[0]) == {n + ".npy" for n in ("disparity", "planes", "params", "ids", "components", "n_components")}
+    for name, a in dumps[0].items():
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, dumps[1][name]), name
+    disp = dumps[0]["disparity.npy"]
+    assert disp.shape == (4, 96, 320)
+    for k in (0, 3):
+        l, r, _ = synth.make_pair(320, 96, 64, 4, frame=k)
+        assert (disp[k] == O.disparity_module(l, r, 64, 8, 4, radius=2, iterations=1)).all(), f"frame {k}"
+
+
 def test_two_ranks_through_the_drivers_launch_form():
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))
         port = s.getsockname()[1]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port),
-           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--allow-shared-gpu", "--sequence"] + SMALL
+           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--allow-shared-gpu", "--sequence", "--full"] + SMALL
     pr = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=540)
     assert pr.returncode == 0, pr.stderr.decode(errors="replace")[-3000:]
     d = one_json_line(pr.stdout)
@@ -77,7 +106,7 @@ def test_four_ranks_and_a_64_frame_sequence():
         port = s.getsockname()[1]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "4", "--master-addr", "127.0.0.1", "--master-port", str(port),
-           os.path.join(ROOT, "bench.py"), "--gpus", "4", "--backend", "gloo", "--allow-shared-gpu", "--sequence",
+           os.path.join(ROOT, "bench.py"), "--gpus", "4", "--backend", "gloo", "--allow-shared-gpu", "--sequence", "--full",
            "--steps", "3", "--warmup", "1", "--repeats", "3", "--batch", "16", "--width", "256", "--height", "96", "--disparities", "64", "--no-pcie"]
     pr = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=540)
     assert pr.returncode == 0, pr.stderr.decode(errors="replace")[-3000:]
