@@ -5,4 +5,4 @@ live here; all arithmetic is in the HIP library (cart-slam_amd/csrc).  Nothing h
 """
 from . import _lib, synth  # noqa: F401
 from ._lib import EngineParams, PlaneParams, SuperpixelParams  # noqa: F401
-from .engine import INVALID, DevicePlaneSchedule, Engine, EngineError, Superpixels, find_peaks, find_plane_params  # noqa: F401
+from .engine import INVALID, DevicePlaneSchedule, Engine, EngineError, PlaneFit, Superpixels, find_peaks, find_plane_params, plane_cluster  # noqa: F401

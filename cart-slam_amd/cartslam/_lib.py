@@ -43,6 +43,11 @@ class PlacementReport(C.Structure):
                 ("seconds", C.c_float), ("units", C.c_int), ("candidates", C.c_int), ("mode", C.c_int), ("stop_reason", C.c_int)]
 
 
+PRED_PLANEFIT, PRED_PLANECLUSTER = 0, 1        # CART_PLANE_PREDICATE_*
+PLANEFIT_MAX_PLANES = 100                      # CART_PLANEFIT_MAX_PLANES
+PLANEFIT_THRESHOLD = 0.01                      # CART_PLANEFIT_THRESHOLD
+
+
 PLACE_MODES = {0: "unknown", 1: "fast", 2: "mixed", 3: "uniform"}                                       # CART_PLACE_MODE_*
 PLACE_STOPS = {0: "nothing to do", 1: "fast set found", 2: "uniform", 3: "tries", 4: "time", 5: "memory"}   # CART_PLACE_STOP_*
 
@@ -93,6 +98,14 @@ PROTOTYPES = {
     "cart_superpixels_max_label": (_i, [_vp]),
     "cart_superpixel_plane_classify": (_i, [_vp, _vp, _sz, _vp, _sz, _i, C.POINTER(PlaneParams), _i, C.POINTER(_vp), C.POINTER(_sz),
                                            C.POINTER(_vp), C.POINTER(_sz), _vp, _sz, _vp, _sz, _vp]),
+    "cart_planefit_create": (_i, [_vp, _i, C.POINTER(_vp)]),
+    "cart_planefit_destroy": (None, [_vp]),
+    "cart_planefit_label_planes": (_i, [_vp, _vp, _sz, _i, _vp, _sz, _i, C.c_double, C.c_uint64, C.c_uint64, _vp, _vp, _vp, _vp]),
+    "cart_planefit_points": (_i, [_vp, _vp, _sz, _vp, _vp]),
+    "cart_planefit_adjacency": (_i, [_vp, _vp, _sz, _i, _vp, _vp, _sz, _vp]),
+    "cart_planefit_fit": (_i, [_vp, _vp, _sz, C.c_uint64, C.c_uint64, _vp, _vp, _vp, C.POINTER(_i), _vp]),
+    "cart_planefit_status": (_i, [_vp, C.POINTER(_i)]),
+    "cart_plane_cluster": (_i, [_vp, _i, _vp, _vp, _vp, _vp, C.POINTER(_i)]),
     "cart_optical_flow": (_i, [_vp, _vp, _sz, _vp, _sz, _i, _i, _i, _vp, _sz, _vp]),
     "cart_resize_linear": (_i, [_i, _vp, _sz, _i, _i, _i, _vp, _sz, _i, _i, _vp]),
     "cart_copy_narrow": (_i, [_vp, _vp, _vp, _sz, _i, _vp]),

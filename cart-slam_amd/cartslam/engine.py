@@ -510,6 +510,122 @@ class Superpixels:
             pass
 
 
+class PlaneFit:
+    """Superpixel plane fitting (cart_planefit_* in the C ABI): per-label RANSAC planes, point lists,
+    8-neighbour adjacency and the planefit assignment loop on the device.  Labels are uint16 carried as int16 tensors,
+    xyz is float32 [h, w, 3] (the "depth" image)."""
+
+    def __init__(self, engine, max_label_capacity=16383):
+        self._eng = engine
+        self._lib = engine._lib
+        self._h = C.c_void_p()
+        self.max_label = None
+        rc = self._lib.cart_planefit_create(engine._h, int(max_label_capacity), C.byref(self._h))
+        if rc != 0:
+            raise EngineError("cart_planefit_create: " + self._lib.cart_last_error(engine._h).decode())
+
+    def _check(self, rc, what):
+        if rc != 0:
+            raise EngineError(f"{what}: " + self._lib.cart_last_error(self._eng._h).decode())
+
+    def _labels(self, labels):
+        if labels.element_size() != 2 or tuple(labels.shape) != (self._eng.height, self._eng.width):
+            raise EngineError("labels must be a 16-bit [h, w] tensor of the engine's size")
+        _, p, s, _ = _geom(labels, 1)
+        return p, s
+
+    def label_planes(self, labels, xyz, max_label, predicate=_lib.PRED_PLANEFIT, thr=_lib.PLANEFIT_THRESHOLD, seed=0, frame_id=0):
+        """S17 for labels 0..max_label -> (planes f64 [L+1, 4], npoints i32 [L+1], counts i32 [L+1, 2] (all, invalid))."""
+        import torch
+        lp, ls = self._labels(labels)
+        if xyz.dtype != torch.float32 or tuple(xyz.shape) != (self._eng.height, self._eng.width, 3):
+            raise EngineError("xyz must be float32 [h, w, 3]")
+        _, xp, xs, _ = _geom(xyz, 2)
+        L1 = int(max_label) + 1
+        dev = labels.device
+        planes = torch.empty((L1, 4), dtype=torch.float64, device=dev)
+        npts = torch.empty(L1, dtype=torch.int32, device=dev)
+        counts = torch.empty((L1, 2), dtype=torch.int32, device=dev)
+        self._check(self._lib.cart_planefit_label_planes(self._h, lp, ls, int(max_label), xp, xs, int(predicate), float(thr), int(seed), int(frame_id),
+                                                         C.c_void_p(planes.data_ptr()), C.c_void_p(npts.data_ptr()), C.c_void_p(counts.data_ptr()),
+                                                         _stream_ptr()), "cart_planefit_label_planes")
+        self.max_label = int(max_label)
+        return planes, npts, counts
+
+    def points(self, capacity=None):
+        """Point lists of the last label_planes call -> (points f32 [n, 4], offsets i32 [L+2])."""
+        import torch
+        cap = int(capacity) if capacity is not None else self._eng.width * self._eng.height
+        pts = torch.empty((cap, 4), dtype=torch.float32, device="cuda")
+        off = torch.empty(self.max_label + 2, dtype=torch.int32, device="cuda")
+        self._check(self._lib.cart_planefit_points(self._h, C.c_void_p(pts.data_ptr()), cap, C.c_void_p(off.data_ptr()), _stream_ptr()),
+                    "cart_planefit_points")
+        return pts[:int(off[-1].item())], off
+
+    def adjacency(self, labels, max_label):
+        """8-neighbour label sets -> (offsets i32 [L+2], neighbours i32 [offsets[-1]])."""
+        import torch
+        lp, ls = self._labels(labels)
+        L1 = int(max_label) + 1
+        cap = max(1, min(8 * self._eng.width * self._eng.height, L1 * (L1 - 1)))
+        off = torch.empty(L1 + 1, dtype=torch.int32, device=labels.device)
+        nb = torch.empty(cap, dtype=torch.int32, device=labels.device)
+        self._check(self._lib.cart_planefit_adjacency(self._h, lp, ls, int(max_label), C.c_void_p(off.data_ptr()), C.c_void_p(nb.data_ptr()), cap,
+                                                      _stream_ptr()), "cart_planefit_adjacency")
+        return off, nb[:int(off[-1].item())]
+
+    def fit(self, labels, seed=0, frame_id=0):
+        """S19 after label_planes(predicate=PRED_PLANEFIT) -> (planes f64 [k, 4], assignments u64 as int64 [L+1], launches)."""
+        import torch
+        lp, ls = self._labels(labels)
+        planes = torch.zeros((_lib.PLANEFIT_MAX_PLANES, 4), dtype=torch.float64, device=labels.device)
+        assign = torch.empty(self.max_label + 1, dtype=torch.int64, device=labels.device)
+        n = torch.empty(1, dtype=torch.int32, device=labels.device)
+        launches = C.c_int(0)
+        self._check(self._lib.cart_planefit_fit(self._h, lp, ls, int(seed), int(frame_id), C.c_void_p(planes.data_ptr()), C.c_void_p(assign.data_ptr()),
+                                                C.c_void_p(n.data_ptr()), C.byref(launches), _stream_ptr()), "cart_planefit_fit")
+        k = int(n.item())
+        if k < 0:
+            raise EngineError("cart_planefit_fit: the label image holds a label above max_label")
+        return planes[:k], assign, launches.value
+
+    def status(self):
+        """-> True if a label image since the last label_planes / adjacency call held a label above max_label (synchronises)."""
+        bad = C.c_int(0)
+        self._check(self._lib.cart_planefit_status(self._h, C.byref(bad)), "cart_planefit_status")
+        return bool(bad.value)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.cart_planefit_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def plane_cluster(planes, offsets, neighbours):
+    """S18 on the host (cart_plane_cluster): planes f64 [L+1, 4], adjacency CSR -> (planes [k, 4], assignments uint64 [L+1])."""
+    lib = _lib.load()
+    planes = np.ascontiguousarray(planes, dtype=np.float64)
+    off = np.ascontiguousarray(offsets, dtype=np.int32)
+    nb = np.ascontiguousarray(neighbours, dtype=np.int32)
+    if nb.size == 0:
+        nb = np.zeros(1, np.int32)
+    L1 = planes.shape[0]
+    out = np.zeros((L1, 4), np.float64)
+    assign = np.zeros(L1, np.uint64)
+    n = C.c_int(0)
+    rc = lib.cart_plane_cluster(planes.ctypes.data_as(C.c_void_p), L1 - 1, off.ctypes.data_as(C.c_void_p), nb.ctypes.data_as(C.c_void_p),
+                                out.ctypes.data_as(C.c_void_p), assign.ctypes.data_as(C.c_void_p), C.byref(n))
+    if rc != 0:
+        raise EngineError("cart_plane_cluster: " + lib.cart_last_error(None).decode())
+    return out[:n.value], assign
+
+
 def resize_linear(img, dst_width, dst_height):
     """cv::cuda::resize(..., INTER_LINEAR) of the KITTI source (cart_resize_linear): uint8 CUDA [h,w] or [h,w,3] -> [dh,dw(,3)]."""
     import torch

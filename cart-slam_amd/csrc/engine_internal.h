@@ -186,6 +186,33 @@ struct SpClassifyArgs {
 };
 void launch_sp_classify(const SpClassifyArgs &a, hipStream_t s);
 
+// ---- superpixel plane fitting (planefit_kernels.hip) ----
+constexpr int kPfMaxLocal = 64;     // grid slots of selectRandomSuperpixels(4, 3): at most 8 x 8 for any image the engine accepts
+constexpr int kPfMaxPlanes = 100;   // planefit.cu:400 (iterations)
+struct PfFitState { int assigned, done, iter, nplanes, nlocal, pending, err, pad; };
+struct PfFitArgs {
+    const uint16_t *labels; size_t lstep;
+    int w, h, L1;
+    uint64_t seed, frame;
+    const int32_t *cnt, *npts, *start, *err;
+    const float4 *pts;
+    const double *planes17;   // [L1][4]
+    PfFitState *state;
+    double *local;            // [kPfMaxLocal][4]
+    uint64_t *accept;         // [L1]
+    double *planes_out;       // [kPfMaxPlanes][4]
+    uint64_t *assign;         // [L1]
+    int32_t *nplanes_out;
+};
+int pf_tiles(int w, int h);   // 1024-pixel raster tiles of the point sort
+void launch_pf_points(const uint16_t *labels, size_t lstep, const float *xyz, size_t xstep, int w, int h, int L1, int pred,
+                      int32_t *cursor, int ntiles, int32_t *cnt, int32_t *npts, int32_t *start, float4 *pts, int32_t *err, hipStream_t s);
+void launch_pf_ransac(const float4 *pts, const int32_t *start, const int32_t *npts, int L1, double thr, uint64_t seed, uint64_t frame,
+                      double *planes, hipStream_t s);
+void launch_pf_adjacency(const uint16_t *labels, size_t lstep, int w, int h, int L1, uint32_t *bits, int32_t *cnt, int32_t *off,
+                         int32_t *neigh, size_t capacity, int32_t *err, hipStream_t s);
+int launch_pf_fit(const PfFitArgs &a, hipStream_t s);   // returns the number of launches it queued
+
 // ---- optical flow (flow_kernels.hip) ----
 void launch_block_flow(const uint32_t *cen_cur, const uint32_t *cen_prev, const Geometry &g, int radius, int block, int16_t *flow,
                        size_t flow_step, hipStream_t s);

@@ -13,6 +13,7 @@
 #include "cartslam_amd/json.hpp"
 #include "cartslam_amd/modules/depth.hpp"
 #include "cartslam_amd/modules/disparity.hpp"
+#include "cartslam_amd/modules/planefit.hpp"
 #include "cartslam_amd/modules/planeseg.hpp"
 #include "cartslam_amd/modules/superpixels.hpp"
 
@@ -107,6 +108,10 @@ void applyModuleConfig(const Value &modulesConfig, std::shared_ptr<System> syste
             system->addModule<OpticalFlowFileModule>();
         } else if (moduleType == "optflow") {  // cartconfig.cpp:183-185; search_radius / block_radius are extensions
             system->addModule<ImageOpticalFlowModule>(dataSource->getImageSize(), get(moduleConfig, "search_radius", 8), get(moduleConfig, "block_radius", 2));
+        } else if (moduleType == "planefit") {  // extension key "seed" (default 0): the reference seeds from std::random_device
+            system->addModule<SuperPixelPlaneFitModule>((uint64_t)get(moduleConfig, "seed", 0));
+        } else if (moduleType == "planecluster") {
+            system->addModule<SuperPixelPlaneClusterModule>((uint64_t)get(moduleConfig, "seed", 0));
         } else if (endsWith(moduleType, "_visualization")) {
             std::cerr << "[cartconfig] skipping GUI module type " << moduleType << " (out of scope)\n";
         } else {

@@ -12,10 +12,12 @@
 #include <future>
 #include <fstream>
 #include <iostream>
+#include <vector>
 
 #include "cartslam_amd/cartconfig.hpp"
 #include "cartslam_amd/modules/depth.hpp"
 #include "cartslam_amd/timing.hpp"
+#include "cartslam_amd/modules/planefit.hpp"
 #include "cartslam_amd/modules/planeseg.hpp"
 
 int main(int argc, char **argv) {
@@ -66,6 +68,19 @@ int main(int argc, char **argv) {
                     std::ofstream o(dump + "/" + std::to_string(id) + "_" + CARTSLAM_KEY_SUPERPIXELS_MAX_LABEL + ".bin", std::ios::binary);
                     o.write(reinterpret_cast<const char *>(&mx), sizeof(mx));
                 }
+                if (run->hasData(CARTSLAM_KEY_PLANES_EQ)) {   // planes f64 [N][4], assignments u64 [max_label + 1]
+                    auto pf = run->getData<cart::plane_fit_data_t>(CARTSLAM_KEY_PLANES_EQ);
+                    std::ofstream p(dump + "/" + std::to_string(id) + "_" + CARTSLAM_KEY_PLANES_EQ + "_planes.bin", std::ios::binary);
+                    if (!pf->planes.empty()) p.write(reinterpret_cast<const char *>(pf->planes.data()), (std::streamsize)(pf->planes.size() * sizeof(cart::Vec4d)));
+                    std::vector<uint64_t> as(pf->planeAssignments.begin(), pf->planeAssignments.end());
+                    std::ofstream a(dump + "/" + std::to_string(id) + "_" + CARTSLAM_KEY_PLANES_EQ + "_assignments.bin", std::ios::binary);
+                    a.write(reinterpret_cast<const char *>(as.data()), (std::streamsize)(as.size() * sizeof(uint64_t)));
+                }
+                if (run->hasData(CARTSLAM_KEY_PLANES_EQ_LABEL_PLANES)) {   // f64 [max_label + 1][4]
+                    auto lp = run->getData<std::vector<cart::Vec4d>>(CARTSLAM_KEY_PLANES_EQ_LABEL_PLANES);
+                    std::ofstream p(dump + "/" + std::to_string(id) + "_" + CARTSLAM_KEY_PLANES_EQ_LABEL_PLANES + ".bin", std::ios::binary);
+                    p.write(reinterpret_cast<const char *>(lp->data()), (std::streamsize)(lp->size() * sizeof(cart::Vec4d)));
+                }
                 for (const char *k : keys) {
                     if (!run->hasData(k)) continue;
                     auto img = run->getData<cart::image_t>(k);
@@ -84,6 +99,7 @@ int main(int argc, char **argv) {
         std::cout << "frames " << frames << " failed " << failed;
         for (const auto &m : system->getModules())
             if (auto d = std::dynamic_pointer_cast<cart::ImageDisparityModule>(m)) std::cout << " frames_per_launch " << d->meanFramesPerLaunch();
+            else if (auto c = std::dynamic_pointer_cast<cart::SuperPixelPlaneClusterModule>(m)) std::cout << " merge_ms " << c->meanMergeMs();
         std::cout << "\n";
         return failed ? 2 : 0;
     } catch (const std::exception &e) {

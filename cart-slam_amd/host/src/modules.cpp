@@ -14,6 +14,7 @@
 #include "cartslam_amd/coalescer.hpp"
 #include "cartslam_amd/modules/depth.hpp"
 #include "cartslam_amd/modules/disparity.hpp"
+#include "cartslam_amd/modules/planefit.hpp"
 #include "cartslam_amd/modules/planeseg.hpp"
 #include "cartslam_amd/modules/superpixels.hpp"
 
@@ -650,5 +651,195 @@ void HistogramPeakPlaneParameterProvider::updatePlaneParameters(System &, System
     verticalRange = std::make_pair(p.vertical_min, p.vertical_max);
     horizontalCenter = p.horizontal_center;
     verticalCenter = p.vertical_center;
+}
+
+// ---------------------------------------------------------------- superpixel plane fit / cluster (planefit.cu:182-445, planecluster.cpp:19-177)
+// The engine and the cart_planefit workspaces are made for the first frame's image size and kept: a free slot is leased
+// per frame, so frames of one run may overlap.  Every slot owns its device output buffer and a pinned host buffer for the
+// download; both only grow, and a slot's buffers are touched by one frame at a time (no allocation or free inside a frame).
+class PlaneFitPool {
+   public:
+    struct Slot {
+        cart_planefit *pf = nullptr;
+        void *dev = nullptr, *host = nullptr;
+        size_t devBytes = 0, hostBytes = 0;
+        void reserve(size_t dBytes, size_t hBytes) {
+            if (dBytes > devBytes) {
+                if (dev) hipCheck(hipFree(dev), "hipFree");
+                dev = nullptr; devBytes = 0;
+                hipCheck(hipMalloc(&dev, dBytes), "hipMalloc");
+                devBytes = dBytes;
+            }
+            if (hBytes > hostBytes) {
+                if (host) hipCheck(hipHostFree(host), "hipHostFree");
+                host = nullptr; hostBytes = 0;
+                hipCheck(hipHostMalloc(&host, hBytes, hipHostMallocDefault), "hipHostMalloc");
+                hostBytes = hBytes;
+            }
+        }
+    };
+    struct Lease {
+        PlaneFitPool &pool;
+        Slot *slot;
+        ~Lease() { std::lock_guard<std::mutex> lk(pool.mu); pool.idle.push_back(slot); }
+    };
+    ~PlaneFitPool() {
+        for (auto &s : all) {
+            cart_planefit_destroy(s->pf);
+            if (s->dev) (void)hipFree(s->dev);
+            if (s->host) (void)hipHostFree(s->host);
+        }
+    }
+    std::shared_ptr<EngineHandle> engineFor(const image_t &labels) {
+        std::lock_guard<std::mutex> lk(mu);
+        if (!engine) {
+            Size res; res.width = labels.cols; res.height = labels.rows;
+            engine = std::make_shared<EngineHandle>(res, paramsFor(res, 0, 0, -1, 0, 0, 10, 120, 12));
+        }
+        return engine;
+    }
+    Slot *acquire(const image_t &labels) {
+        auto eng = engineFor(labels);
+        std::lock_guard<std::mutex> lk(mu);
+        if (!idle.empty()) { Slot *s = idle.back(); idle.pop_back(); return s; }
+        auto s = std::make_unique<Slot>();
+        if (cart_planefit_create(eng->get(), 16383, &s->pf) != 0) eng->fail("cart_planefit_create");
+        all.push_back(std::move(s));
+        return all.back().get();
+    }
+
+   private:
+    std::mutex mu;
+    std::shared_ptr<EngineHandle> engine;
+    std::vector<std::unique_ptr<Slot>> all;
+    std::vector<Slot *> idle;
+};
+
+namespace {
+struct PlaneInputs {
+    std::shared_ptr<image_t> labels, depth;
+    contour::label_t maxLabel;
+};
+PlaneInputs planeInputs(SystemRunData &data) {
+    PlaneInputs in{data.getData<image_t>(CARTSLAM_KEY_SUPERPIXELS), data.getData<image_t>(CARTSLAM_KEY_DEPTH),
+                   *data.getData<contour::label_t>(CARTSLAM_KEY_SUPERPIXELS_MAX_LABEL)};
+    if (in.labels->type() != CV_16UC1) throw std::runtime_error("Superpixels must be of type CV_16UC1");
+    if (in.depth->type() != CV_32FC3 || in.depth->rows != in.labels->rows || in.depth->cols != in.labels->cols)
+        throw std::runtime_error("Depth must be CV_32FC3 of the superpixel image's size");
+    return in;
+}
+}  // namespace
+
+SuperPixelPlaneFitModule::SuperPixelPlaneFitModule(uint64_t seed) : SyncWrapperSystemModule("PlaneFit"), seed(seed), pool(std::make_shared<PlaneFitPool>()) {
+    this->requiresData.push_back(module_dependency_t(CARTSLAM_KEY_DEPTH));   // planefit.cu:182-187
+    this->requiresData.push_back(module_dependency_t(CARTSLAM_KEY_SUPERPIXELS));
+    this->requiresData.push_back(module_dependency_t(CARTSLAM_KEY_SUPERPIXELS_MAX_LABEL));
+    this->requiresData.push_back(module_dependency_t(CARTSLAM_KEY_DISPARITY_DERIVATIVE));
+    this->providesData.push_back(CARTSLAM_KEY_PLANES_EQ);
+    this->providesData.push_back(CARTSLAM_KEY_PLANES_EQ_LABEL_PLANES);
+}
+SuperPixelPlaneFitModule::~SuperPixelPlaneFitModule() = default;
+
+namespace {
+std::vector<Vec4d> toPlanes(const double *p, size_t n) {
+    std::vector<Vec4d> out(n);
+    for (size_t k = 0; k < n; ++k) out[k] = Vec4d{p[k * 4], p[k * 4 + 1], p[k * 4 + 2], p[k * 4 + 3]};
+    return out;
+}
+}  // namespace
+
+system_data_t SuperPixelPlaneFitModule::runInternal(System &, SystemRunData &data) {
+    const PlaneInputs in = planeInputs(data);
+    auto eng = pool->engineFor(*in.labels);
+    PlaneFitPool::Lease lease{*pool, pool->acquire(*in.labels)};
+    PlaneFitPool::Slot &sl = *lease.slot;
+    const size_t L1 = (size_t)in.maxLabel + 1;
+    // output layout (device and host alike): label planes [L1][4] f64 | planes [100][4] f64 | assignments [L1] u64 | n_planes
+    const size_t bytes = L1 * 32 + CART_PLANEFIT_MAX_PLANES * 32 + L1 * 8 + 8;
+    sl.reserve(bytes, bytes);
+    double *labelPlanesDev = static_cast<double *>(sl.dev);
+    double *planesDev = labelPlanesDev + L1 * 4;
+    uint64_t *assignDev = reinterpret_cast<uint64_t *>(planesDev + CART_PLANEFIT_MAX_PLANES * 4);
+    int32_t *nDev = reinterpret_cast<int32_t *>(assignDev + L1);
+    ScopedStream stream;
+    if (cart_planefit_label_planes(sl.pf, in.labels->ptr<uint16_t>(), in.labels->step, (int)in.maxLabel, in.depth->ptr<float>(), in.depth->step,
+                                   CART_PLANE_PREDICATE_PLANEFIT, CART_PLANEFIT_THRESHOLD, seed, data.id, labelPlanesDev, nullptr, nullptr, stream.s) != 0)
+        eng->fail("cart_planefit_label_planes");
+    if (cart_planefit_fit(sl.pf, in.labels->ptr<uint16_t>(), in.labels->step, seed, data.id, planesDev, assignDev, nDev, nullptr, stream.s) != 0)
+        eng->fail("cart_planefit_fit");
+    hipCheck(hipMemcpyAsync(sl.host, sl.dev, bytes, hipMemcpyDeviceToHost, stream.s), "hipMemcpyAsync of the planefit outputs");
+    stream.wait();   // the frame's only blocking synchronisation
+    const uint8_t *h = static_cast<const uint8_t *>(sl.host);
+    const int32_t n = *reinterpret_cast<const int32_t *>(h + L1 * 32 + CART_PLANEFIT_MAX_PLANES * 32 + L1 * 8);
+    if (n < 0) throw std::runtime_error("superpixel label above superpixels_max_label");
+    plane_fit_data_t out;
+    out.planes = toPlanes(reinterpret_cast<const double *>(h + L1 * 32), (size_t)n);
+    const uint64_t *as = reinterpret_cast<const uint64_t *>(h + L1 * 32 + CART_PLANEFIT_MAX_PLANES * 32);
+    out.planeAssignments.assign(as, as + L1);
+    return MODULE_RETURN_ALL(std::make_pair(std::string(CARTSLAM_KEY_PLANES_EQ), std::shared_ptr<void>(std::make_shared<plane_fit_data_t>(std::move(out)))),
+                             std::make_pair(std::string(CARTSLAM_KEY_PLANES_EQ_LABEL_PLANES),
+                                            std::shared_ptr<void>(std::make_shared<std::vector<Vec4d>>(toPlanes(reinterpret_cast<const double *>(h), L1)))));
+}
+
+SuperPixelPlaneClusterModule::SuperPixelPlaneClusterModule(uint64_t seed) : SyncWrapperSystemModule("PlaneCluster"), seed(seed), pool(std::make_shared<PlaneFitPool>()) {
+    this->requiresData.push_back(module_dependency_t(CARTSLAM_KEY_DEPTH));   // planecluster.hpp:15-17
+    this->requiresData.push_back(module_dependency_t(CARTSLAM_KEY_SUPERPIXELS));
+    this->requiresData.push_back(module_dependency_t(CARTSLAM_KEY_SUPERPIXELS_MAX_LABEL));
+    this->providesData.push_back(CARTSLAM_KEY_PLANES_EQ);
+    this->providesData.push_back(CARTSLAM_KEY_PLANES_EQ_LABEL_PLANES);
+}
+SuperPixelPlaneClusterModule::~SuperPixelPlaneClusterModule() = default;
+
+system_data_t SuperPixelPlaneClusterModule::runInternal(System &, SystemRunData &data) {
+    const PlaneInputs in = planeInputs(data);
+    auto eng = pool->engineFor(*in.labels);
+    PlaneFitPool::Lease lease{*pool, pool->acquire(*in.labels)};
+    PlaneFitPool::Slot &sl = *lease.slot;
+    const size_t L1 = (size_t)in.maxLabel + 1;
+    const size_t cap = std::max<size_t>(1, std::min<size_t>(8 * (size_t)in.labels->rows * in.labels->cols, L1 * (L1 - 1)));
+    // layout: label planes [L1][4] f64 | offsets [L1 + 1] | neighbours [cap]; the host copy takes the head, then the neighbours
+    const size_t head = L1 * 32 + (L1 + 1) * 4;
+    sl.reserve(head + cap * 4, head + cap * 4);
+    double *planesDev = static_cast<double *>(sl.dev);
+    int32_t *offDev = reinterpret_cast<int32_t *>(planesDev + L1 * 4);
+    int32_t *nbDev = offDev + L1 + 1;
+    ScopedStream stream;
+    if (cart_planefit_label_planes(sl.pf, in.labels->ptr<uint16_t>(), in.labels->step, (int)in.maxLabel, in.depth->ptr<float>(), in.depth->step,
+                                   CART_PLANE_PREDICATE_PLANECLUSTER, CART_PLANEFIT_THRESHOLD, seed, data.id, planesDev, nullptr, nullptr, stream.s) != 0)
+        eng->fail("cart_planefit_label_planes");
+    if (cart_planefit_adjacency(sl.pf, in.labels->ptr<uint16_t>(), in.labels->step, (int)in.maxLabel, offDev, nbDev, cap, stream.s) != 0)
+        eng->fail("cart_planefit_adjacency");
+    hipCheck(hipMemcpyAsync(sl.host, sl.dev, head, hipMemcpyDeviceToHost, stream.s), "hipMemcpyAsync of the plane tables");
+    stream.wait();
+    uint8_t *h = static_cast<uint8_t *>(sl.host);
+    const int32_t *off = reinterpret_cast<const int32_t *>(h + L1 * 32);
+    if (off[0] != 0 || off[L1] < 0 || (size_t)off[L1] > cap) throw std::runtime_error("adjacency table out of range");
+    int32_t *nb = reinterpret_cast<int32_t *>(h + head);
+    if (off[L1] > 0) {
+        hipCheck(hipMemcpyAsync(nb, nbDev, (size_t)off[L1] * 4, hipMemcpyDeviceToHost, stream.s), "hipMemcpyAsync of the adjacency");
+        stream.wait();
+    }
+    int bad = 0;
+    if (cart_planefit_status(sl.pf, &bad) != 0) eng->fail("cart_planefit_status");
+    if (bad) throw std::runtime_error("superpixel label above superpixels_max_label");
+    std::vector<double> planesOut(L1 * 4);
+    std::vector<uint64_t> assign(L1);
+    int n = 0;
+    const auto t0 = std::chrono::steady_clock::now();
+    if (cart_plane_cluster(reinterpret_cast<const double *>(h), (int)L1 - 1, off, nb, planesOut.data(), assign.data(), &n) != 0)
+        eng->fail("cart_plane_cluster");
+    mergeNs.fetch_add((long long)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count());
+    mergeCalls.fetch_add(1);
+    plane_fit_data_t out;
+    out.planes = toPlanes(planesOut.data(), (size_t)n);
+    out.planeAssignments.assign(assign.begin(), assign.end());
+    return MODULE_RETURN_ALL(std::make_pair(std::string(CARTSLAM_KEY_PLANES_EQ), std::shared_ptr<void>(std::make_shared<plane_fit_data_t>(std::move(out)))),
+                             std::make_pair(std::string(CARTSLAM_KEY_PLANES_EQ_LABEL_PLANES),
+                                            std::shared_ptr<void>(std::make_shared<std::vector<Vec4d>>(toPlanes(reinterpret_cast<const double *>(h), L1)))));
+}
+
+double SuperPixelPlaneClusterModule::meanMergeMs() const {
+    const long n = mergeCalls.load();
+    return n ? 1e-6 * (double)mergeNs.load() / (double)n : 0.0;
 }
 }  // namespace cart

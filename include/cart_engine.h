@@ -337,6 +337,61 @@ int cart_superpixel_plane_classify(cart_engine *engine, const int16_t *deriv2, s
                                    uint8_t *planes_unsmoothed, size_t planes_unsmoothed_step,
                                    uint8_t *planes, size_t planes_step, void *stream);
 
+/* ---- superpixel plane fitting: planefit / planecluster ----------------------------------------------
+ * replaces: the host work of SuperPixelPlaneFitModule (src/modules/planefit.cu:223-445) and SuperPixelPlaneClusterModule
+ * (src/modules/planecluster.cpp:19-177), and segmentPlane / getPlaneFromPoints (src/utils/plane.cpp:56-180).  The reference
+ * downloads labels + depth every frame and runs a std::random_device-seeded RANSAC per superpixel under OpenMP; its output
+ * cannot be reproduced, so the stages follow a deterministic spec:
+ *   S17 per-label RANSAC plane: the label's points in raster order whose xyz passes `predicate`, widened to double; fewer
+ *       than 16 points -> plane (0,0,0,0).  Hypothesis h (0..99) draws 4 distinct indices from the counter-based stream
+ *       stream(1, frame_id, label, h) (splitmix64; uniform index = (hi32(draw) * n) >> 32), fits them with sequential sums,
+ *       and scores count = #(|((a*x + b*y) + c*z) + d| < thr) and qerr = sum of floor(dist^2 / thr^2 * 2^24); the best
+ *       maximises (count, -qerr, -h) over count >= 1.  Refit on its inliers with 64-lane strided sums + butterfly.  fp64.
+ *   S18 planecluster merge (host, cart_plane_cluster): the reference's region growing with one thread, groups >= 32.
+ *   S19 planefit loop (device): grid samples from stream(2, frame_id, iteration, slot), up to 100 iterations, inliers at
+ *       0.02, acceptance > half the label's pixels, winner needs >= 16 labels; the count starts at the VALID regions
+ *       (planefit.cu:390-396, kept literally: with >= 90 % valid regions the loop does not run). */
+enum { CART_PLANE_PREDICATE_PLANEFIT = 0,       /* isfinite(z) && z <= 40 && z > 0      (planefit.cu:20)     */
+       CART_PLANE_PREDICATE_PLANECLUSTER = 1 }; /* !(z <= 0 || z > 40), NaN z kept      (planecluster.cpp:35) */
+#define CART_PLANEFIT_MAX_PLANES 100            /* planefit.cu:400 */
+#define CART_PLANEFIT_THRESHOLD 0.01            /* segmentPlane default distance threshold (plane.hpp:7-12) */
+
+typedef struct cart_planefit cart_planefit;
+/* Workspaces for labels 0..max_label_capacity (<= 16383, cart_superpixels' limit) at the engine's image size. */
+int cart_planefit_create(cart_engine *engine, int max_label_capacity, cart_planefit **out);
+void cart_planefit_destroy(cart_planefit *pf);
+/* S17 for every label 0..max_label (replaces planefit.cu:366-384 + plane.cpp:102-180, planecluster.cpp:31-67).  labels =
+ * CV_16UC1, xyz = CV_32FC3 "depth" (device, steps in bytes).  Keeps the per-label statistics, point lists and planes in the
+ * object for cart_planefit_fit / cart_planefit_points.  Optional device outputs (NULL = not written): planes [max_label+1][4]
+ * f64, npoints [max_label+1] (points passing the predicate), counts [max_label+1][2] (all pixels, pixels failing the
+ * predicate; planefit.cu:39-77).  Labels > max_label are not counted and are reported by cart_planefit_status. */
+int cart_planefit_label_planes(cart_planefit *pf, const uint16_t *labels, size_t labels_step, int max_label, const float *xyz,
+                               size_t xyz_step, int predicate, double thr, uint64_t seed, uint64_t frame_id, double *planes,
+                               int32_t *npoints, int32_t *counts, void *stream);
+/* Test / diagnostic access: the point lists of the last label_planes call.  points = device [capacity][4] f32 (x, y, z, 0),
+ * label-major, raster order inside a label; offsets = device [max_label+2].  Fails if capacity < the number of points
+ * (synchronises `stream` to read it). */
+int cart_planefit_points(cart_planefit *pf, float *points, size_t capacity, int32_t *offsets, void *stream);
+/* 8-neighbour label sets (planecluster.cpp:72-96) in CSR form: offsets = device [max_label+2], neighbours = device int32,
+ * ascending inside a label.  capacity must be >= min(8 * width * height, (max_label+1) * max_label), which bounds every
+ * label image: no set is ever truncated. */
+int cart_planefit_adjacency(cart_planefit *pf, const uint16_t *labels, size_t labels_step, int max_label, int32_t *offsets,
+                            int32_t *neighbours, size_t capacity, void *stream);
+/* S19 on the device (replaces planefit.cu:386-445 incl. attemptAssignment and selectRandomSuperpixels): uses the last
+ * label_planes call, which must have used CART_PLANE_PREDICATE_PLANEFIT.  Device outputs: planes [100][4] f64 (the first
+ * *n_planes rows are set), assignments [max_label+1] u64 (1 + plane index, 0 = none), n_planes (int32; -1 when the label
+ * image held a label > max_label).  *launches (host, may be NULL) = kernel launches queued.  No host synchronisation. */
+int cart_planefit_fit(cart_planefit *pf, const uint16_t *labels, size_t labels_step, uint64_t seed, uint64_t frame_id,
+                      double *planes, uint64_t *assignments, int32_t *n_planes, int *launches, void *stream);
+/* Synchronises the object's last stream; *bad_labels = 1 if a label image given since the last label_planes / adjacency
+ * call held a label above its max_label (those pixels were left out). */
+int cart_planefit_status(cart_planefit *pf, int *bad_labels);
+/* S18 on the HOST (replaces planecluster.cpp:44-177): planes = [max_label+1][4] S17 planes (CART_PLANE_PREDICATE_PLANECLUSTER),
+ * offsets / neighbours = the adjacency CSR (host copies).  Outputs: planes_out [max_label+1][4] (the first *n_planes rows),
+ * assignments [max_label+1] (1 + plane index, 0 = none).  glibc atan2 / sin / cos, no FMA contraction. */
+int cart_plane_cluster(const double *planes, int max_label, const int32_t *offsets, const int32_t *neighbours, double *planes_out,
+                       uint64_t *assignments, int *n_planes);
+
 /* Stand-in for ImageOpticalFlowModule's device work (src/modules/optflow.cpp:96-140: cvtColor x2 +
  * cv::cuda::NvidiaOpticalFlow_2_0::calc(current, previous), NVIDIA fixed-function hardware): dense census block
  * matching (oracle S15).  cur / prev = the reference images of frame id and id-1 (1-channel gray or 3-channel BGR),
