@@ -48,6 +48,14 @@ PLANEFIT_MAX_PLANES = 100                      # CART_PLANEFIT_MAX_PLANES
 PLANEFIT_THRESHOLD = 0.01                      # CART_PLANEFIT_THRESHOLD
 
 
+ORB_DEFAULT_FEATURES, ORB_MAX_FEATURES, ORB_LEVELS, ORB_DESCRIPTOR_BYTES = 5000, 65536, 8, 32   # CART_ORB_*
+
+
+class Keypoint(C.Structure):
+    # mirrors cart_keypoint (include/cart_engine.h): cv::KeyPoint's layout
+    _fields_ = [(n, C.c_float) for n in ("x", "y", "size", "angle", "response")] + [("octave", C.c_int32), ("class_id", C.c_int32)]
+
+
 PLACE_MODES = {0: "unknown", 1: "fast", 2: "mixed", 3: "uniform"}                                       # CART_PLACE_MODE_*
 PLACE_STOPS = {0: "nothing to do", 1: "fast set found", 2: "uniform", 3: "tries", 4: "time", 5: "memory"}   # CART_PLACE_STOP_*
 
@@ -106,6 +114,11 @@ PROTOTYPES = {
     "cart_planefit_fit": (_i, [_vp, _vp, _sz, C.c_uint64, C.c_uint64, _vp, _vp, _vp, C.POINTER(_i), _vp]),
     "cart_planefit_status": (_i, [_vp, C.POINTER(_i)]),
     "cart_plane_cluster": (_i, [_vp, _i, _vp, _vp, _vp, _vp, C.POINTER(_i)]),
+    "cart_orb_create": (_i, [_vp, _i, _i, _i, C.POINTER(_vp)]),
+    "cart_orb_destroy": (None, [_vp]),
+    "cart_orb_levels": (_i, [_i, _i, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
+    "cart_orb_detect": (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_sz), _i, _i, _i, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_sz), _vp, _vp]),
+    "cart_orb_debug_level": (_i, [_vp, _i, _i, _vp, _sz, C.POINTER(C.c_int32), _vp]),
     "cart_optical_flow": (_i, [_vp, _vp, _sz, _vp, _sz, _i, _i, _i, _vp, _sz, _vp]),
     "cart_resize_linear": (_i, [_i, _vp, _sz, _i, _i, _i, _vp, _sz, _i, _i, _vp]),
     "cart_copy_narrow": (_i, [_vp, _vp, _vp, _sz, _i, _vp]),

@@ -607,6 +607,105 @@ class PlaneFit:
             pass
 
 
+KEYPOINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"), ("response", "<f4"), ("octave", "<i4"),
+                           ("class_id", "<i4")])   # cart_keypoint = cv::KeyPoint's layout
+
+
+def orb_levels(width, height, nfeatures=_lib.ORB_DEFAULT_FEATURES):
+    """S20 level layout (cart_orb_levels, host only) -> (built levels, [(w_l, h_l, n_l)] for all 8 levels)."""
+    lib = _lib.load()
+    arr = [(C.c_int * _lib.ORB_LEVELS)() for _ in range(3)]
+    n = lib.cart_orb_levels(int(width), int(height), int(nfeatures), *arr)
+    if n < 0:
+        raise EngineError("cart_orb_levels: " + lib.cart_last_error(None).decode())
+    return n, [(arr[0][l], arr[1][l], arr[2][l]) for l in range(_lib.ORB_LEVELS)]
+
+
+class OrbFeatures:
+    """ORB keypoints + steered-BRIEF descriptors (cart_orb_* in the C ABI): the work of the reference's
+    ImageFeatureDetectorModule (cv::cuda::ORB::create(5000)->detectAndComputeAsync + convert) for images up to
+    max_width x max_height."""
+
+    def __init__(self, engine, max_width, max_height, nfeatures=_lib.ORB_DEFAULT_FEATURES):
+        self._eng = engine
+        self._lib = engine._lib
+        self._h = C.c_void_p()
+        self.nfeatures = int(nfeatures)
+        self._size = None
+        rc = self._lib.cart_orb_create(engine._h, int(max_width), int(max_height), self.nfeatures, C.byref(self._h))
+        if rc != 0:
+            raise EngineError("cart_orb_create: " + self._lib.cart_last_error(engine._h).decode())
+
+    def _check(self, rc, what):
+        if rc != 0:
+            raise EngineError(f"{what}: " + self._lib.cart_last_error(self._eng._h).decode())
+
+    def levels(self, width=None, height=None):
+        """-> (built levels, [(w_l, h_l, n_l)] x 8) for this object's nfeatures; default size = the last detect call's."""
+        w, h = (width, height) if width is not None else self._size
+        return orb_levels(w, h, self.nfeatures)
+
+    def detect(self, left, right=None, raw=False):
+        """uint8 device images, gray [h, w] or BGR [h, w, 3] (row-pitched views allowed; both of one shape) ->
+        one (keypoints, descriptors) per image: keypoints = numpy structured KEYPOINT_DTYPE [n] (host, like the reference's
+        orb->convert), descriptors = uint8 device tensor [n, 32].  raw=True gives the keypoints as the device float32
+        [n, 7] view of the records instead (octave / class_id as float bits)."""
+        import torch
+        imgs = [left] if right is None else [left, right]
+        if any(t.dtype != torch.uint8 or not t.is_cuda for t in imgs):
+            raise EngineError("images must be uint8 CUDA tensors")
+        if any(t.dim() != imgs[0].dim() or tuple(t.shape) != tuple(imgs[0].shape) for t in imgs) or imgs[0].dim() not in (2, 3):
+            raise EngineError("images must share one shape, [h, w] or [h, w, 3]")
+        ch = 1 if imgs[0].dim() == 2 else imgs[0].shape[2]
+        if ch not in (1, 3):
+            raise EngineError("images must be [h, w] or [h, w, 3]")
+        h, w = imgs[0].shape[:2]
+        geo = [_geom(t, 1 if ch == 1 else 2) for t in imgs]
+        n = len(imgs)
+        dev = imgs[0].device
+        kp = torch.empty((n, self.nfeatures, 7), dtype=torch.float32, device=dev)
+        de = torch.empty((n, self.nfeatures, 32), dtype=torch.uint8, device=dev)
+        counts = torch.zeros(n, dtype=torch.int32, device=dev)
+        ptrs = (C.c_void_p * n)(*[g[1].value for g in geo])
+        steps = (C.c_size_t * n)(*[g[2] for g in geo])
+        kps = (C.c_void_p * n)(*[kp[i].data_ptr() for i in range(n)])
+        des = (C.c_void_p * n)(*[de[i].data_ptr() for i in range(n)])
+        self._check(self._lib.cart_orb_detect(self._h, n, ptrs, steps, int(ch), int(w), int(h), kps, des, None,
+                                              C.c_void_p(counts.data_ptr()), _stream_ptr()), "cart_orb_detect")
+        self._size = (int(w), int(h))
+        cnt = counts.cpu().tolist()
+        out = []
+        for i in range(n):
+            k = kp[i, :cnt[i]]
+            if not raw:
+                k = k.cpu().numpy().view(KEYPOINT_DTYPE).reshape(-1)
+            out.append((k, de[i, :cnt[i]]))
+        return out
+
+    def debug_level(self, image, level):
+        """Level `level` of image `image` (0 = left) of the last detect call -> (uint8 device tensor [h_l, w_l], number of
+        NMS survivors of that level before selection)."""
+        import torch
+        _, lv = self.levels()
+        w, h, _ = lv[level]
+        dst = torch.empty((h, w), dtype=torch.uint8, device="cuda")
+        n = C.c_int32(0)
+        self._check(self._lib.cart_orb_debug_level(self._h, int(image), int(level), C.c_void_p(dst.data_ptr()), w, C.byref(n), _stream_ptr()),
+                    "cart_orb_debug_level")
+        return dst, n.value
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.cart_orb_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def plane_cluster(planes, offsets, neighbours):
     """S18 on the host (cart_plane_cluster): planes f64 [L+1, 4], adjacency CSR -> (planes [k, 4], assignments uint64 [L+1])."""
     lib = _lib.load()

@@ -218,6 +218,35 @@ void launch_block_flow(const uint32_t *cen_cur, const uint32_t *cen_prev, const 
                        size_t flow_step, hipStream_t s);
 
 void launch_resize_linear(const uint8_t *src, size_t sstep, int sw, int sh, int channels, uint8_t *dst, size_t dstep, int dw, int dh, hipStream_t s);
+// ---- ORB features (orb_kernels.hip) ----
+constexpr int kOrbLevels = 8;
+constexpr int kOrbEdge = 31;          // edge threshold = patch size
+constexpr int kOrbTileW = 64, kOrbTileH = 16;
+struct OrbCand { long long R; int y, x; };   // one NMS survivor of a level (16 B)
+struct OrbLevel {
+    int w, h;            // level size of this call
+    int tiles_x, tile0;  // detect tiles of this level: [tile0, tile0 + tiles_x * tiles_y)
+    int quota;           // n_l
+    int cap;             // capacity of the level's candidate list
+    size_t pyr_off;      // level image offset inside one image's pyramid (tight rows of w bytes)
+    size_t cand_off;     // first record of the level inside one image's candidate lists
+    float fx, fy;        // S16 ratios from the level above (level >= 1)
+    float scale;         // (float)s_l
+};
+struct OrbPlan {
+    int n_images, n_levels, total_tiles, nfeatures;
+    size_t pyr_stride, cand_stride;   // per image
+    OrbLevel lev[kOrbLevels];
+};
+struct OrbOut {
+    const uint8_t *src[2]; size_t src_step[2]; int channels;
+    cart_keypoint *kp[2]; uint8_t *desc[2]; size_t desc_step[2];
+    int32_t *counts;
+};
+void launch_orb_pyramid_level(const OrbPlan &p, int level, const OrbOut &o, uint8_t *pyr, hipStream_t s);
+void launch_orb_detect(const OrbPlan &p, const uint8_t *pyr, OrbCand *cand, int32_t *cand_cnt, hipStream_t s);
+void launch_orb_select(const OrbPlan &p, const OrbCand *cand, const int32_t *cand_cnt, OrbCand *sel, int4 *kpi, int32_t *counts, hipStream_t s);
+void launch_orb_describe(const OrbPlan &p, const uint8_t *pyr, const int4 *kpi, const char4 *pattern, const OrbOut &o, hipStream_t s);
 void launch_narrow_copy(const void *src, void *dst, size_t bytes, int blocks, hipStream_t s);
 int kernel_count();
 

@@ -16,6 +16,7 @@
 
 #include "cartslam_amd/cartconfig.hpp"
 #include "cartslam_amd/modules/depth.hpp"
+#include "cartslam_amd/modules/features.hpp"
 #include "cartslam_amd/timing.hpp"
 #include "cartslam_amd/modules/planefit.hpp"
 #include "cartslam_amd/modules/planeseg.hpp"
@@ -75,6 +76,19 @@ int main(int argc, char **argv) {
                     std::vector<uint64_t> as(pf->planeAssignments.begin(), pf->planeAssignments.end());
                     std::ofstream a(dump + "/" + std::to_string(id) + "_" + CARTSLAM_KEY_PLANES_EQ + "_assignments.bin", std::ios::binary);
                     a.write(reinterpret_cast<const char *>(as.data()), (std::streamsize)(as.size() * sizeof(uint64_t)));
+                }
+                if (run->hasData(CARTSLAM_KEY_FEATURES)) {   // keypoints: 28-byte cv::KeyPoint records; descriptors: n x 32 bytes
+                    auto f = run->getData<std::pair<cart::ImageFeatures, cart::ImageFeatures>>(CARTSLAM_KEY_FEATURES);
+                    const std::pair<const char *, const cart::ImageFeatures *> sides[] = {{"left", &f->first}, {"right", &f->second}};
+                    for (const auto &side : sides) {
+                        const std::string base = dump + "/" + std::to_string(id) + "_" + CARTSLAM_KEY_FEATURES + "_" + side.first;
+                        std::ofstream k(base + "_keypoints.bin", std::ios::binary);
+                        k.write(reinterpret_cast<const char *>(side.second->keypoints.data()), (std::streamsize)(side.second->keypoints.size() * sizeof(cart::KeyPoint)));
+                        std::vector<uint8_t> d((size_t)side.second->descriptors.rows * CART_ORB_DESCRIPTOR_BYTES);
+                        if (!d.empty()) side.second->descriptors.download(d.data(), CART_ORB_DESCRIPTOR_BYTES);
+                        std::ofstream o(base + "_descriptors.bin", std::ios::binary);
+                        o.write(reinterpret_cast<const char *>(d.data()), (std::streamsize)d.size());
+                    }
                 }
                 if (run->hasData(CARTSLAM_KEY_PLANES_EQ_LABEL_PLANES)) {   // f64 [max_label + 1][4]
                     auto lp = run->getData<std::vector<cart::Vec4d>>(CARTSLAM_KEY_PLANES_EQ_LABEL_PLANES);

@@ -14,6 +14,7 @@
 #include "cartslam_amd/coalescer.hpp"
 #include "cartslam_amd/modules/depth.hpp"
 #include "cartslam_amd/modules/disparity.hpp"
+#include "cartslam_amd/modules/features.hpp"
 #include "cartslam_amd/modules/planefit.hpp"
 #include "cartslam_amd/modules/planeseg.hpp"
 #include "cartslam_amd/modules/superpixels.hpp"
@@ -841,5 +842,102 @@ system_data_t SuperPixelPlaneClusterModule::runInternal(System &, SystemRunData 
 double SuperPixelPlaneClusterModule::meanMergeMs() const {
     const long n = mergeCalls.load();
     return n ? 1e-6 * (double)mergeNs.load() / (double)n : 0.0;
+}
+// ---------------------------------------------------------------- ORB features (features.cpp:10-66)
+// The engine and the cart_orb workspaces are made for the first frame's image size and kept; a free slot is leased per
+// frame.  Every slot owns its device keypoint / count buffer and the pinned host buffer of the download (no allocation or
+// free inside a frame; the descriptors are the frame's own output images, like every other module's outputs).
+class OrbPool {
+   public:
+    struct Slot {
+        cart_orb *orb = nullptr;
+        void *dev = nullptr, *host = nullptr;   // counts [2] int32 + 8 B padding | keypoints [2][nfeatures]
+    };
+    struct Lease {
+        OrbPool &pool;
+        Slot *slot;
+        ~Lease() { std::lock_guard<std::mutex> lk(pool.mu); pool.idle.push_back(slot); }
+    };
+    explicit OrbPool(int nfeatures) : nfeatures(nfeatures) {}
+    ~OrbPool() {
+        for (auto &s : all) {
+            cart_orb_destroy(s->orb);
+            if (s->dev) (void)hipFree(s->dev);
+            if (s->host) (void)hipHostFree(s->host);
+        }
+    }
+    size_t bytes() const { return 16 + 2 * (size_t)nfeatures * sizeof(KeyPoint); }
+    std::shared_ptr<EngineHandle> engineFor(const image_t &image) {
+        std::lock_guard<std::mutex> lk(mu);
+        if (!engine) {
+            res.width = image.cols; res.height = image.rows;
+            engine = std::make_shared<EngineHandle>(res, paramsFor(res, 0, 0, -1, 0, 0, 10, 120, 12));
+        }
+        return engine;
+    }
+    Slot *acquire(const image_t &image) {
+        auto eng = engineFor(image);
+        std::lock_guard<std::mutex> lk(mu);
+        if (!idle.empty()) { Slot *s = idle.back(); idle.pop_back(); return s; }
+        auto s = std::make_unique<Slot>();
+        if (cart_orb_create(eng->get(), res.width, res.height, nfeatures, &s->orb) != 0) eng->fail("cart_orb_create");
+        hipCheck(hipMalloc(&s->dev, bytes()), "hipMalloc");
+        hipCheck(hipHostMalloc(&s->host, bytes(), hipHostMallocDefault), "hipHostMalloc");
+        all.push_back(std::move(s));
+        return all.back().get();
+    }
+    const int nfeatures;
+
+   private:
+    std::mutex mu;
+    Size res;
+    std::shared_ptr<EngineHandle> engine;
+    std::vector<std::unique_ptr<Slot>> all;
+    std::vector<Slot *> idle;
+};
+
+std::pair<ImageFeatures, ImageFeatures> detectOrbFeatures(OrbPool &pool, const image_t &left, const image_t &right) {
+    const int channels = left.type() == CV_8UC3 ? 3 : 1;
+    if ((left.type() != CV_8UC3 && left.type() != CV_8UC1) || right.type() != left.type() || right.cols != left.cols || right.rows != left.rows)
+        throw std::runtime_error("ImageFeatureDetectorModule requires two CV_8UC1 or CV_8UC3 images of one size");
+    auto eng = pool.engineFor(left);
+    OrbPool::Lease lease{pool, pool.acquire(left)};
+    OrbPool::Slot &sl = *lease.slot;
+    const int n = pool.nfeatures;
+    image_t desc[2] = {image_t(n, CART_ORB_DESCRIPTOR_BYTES, CV_8UC1), image_t(n, CART_ORB_DESCRIPTOR_BYTES, CV_8UC1)};
+    int32_t *countsDev = static_cast<int32_t *>(sl.dev);
+    KeyPoint *kpDev = reinterpret_cast<KeyPoint *>(static_cast<uint8_t *>(sl.dev) + 16);
+    const uint8_t *images[2] = {left.ptr<uint8_t>(), right.ptr<uint8_t>()};
+    const size_t steps[2] = {left.step, right.step}, descSteps[2] = {desc[0].step, desc[1].step};
+    cart_keypoint *kps[2] = {kpDev, kpDev + n};
+    uint8_t *descs[2] = {desc[0].ptr<uint8_t>(), desc[1].ptr<uint8_t>()};
+    ScopedStream stream;
+    if (cart_orb_detect(sl.orb, 2, images, steps, channels, left.cols, left.rows, kps, descs, descSteps, countsDev, stream.s) != 0)
+        eng->fail("cart_orb_detect");
+    hipCheck(hipMemcpyAsync(sl.host, sl.dev, pool.bytes(), hipMemcpyDeviceToHost, stream.s), "hipMemcpyAsync of the keypoints");
+    stream.wait();   // the frame's only blocking synchronisation (the reference's orb->convert)
+    const int32_t *counts = static_cast<const int32_t *>(sl.host);
+    const KeyPoint *kpHost = reinterpret_cast<const KeyPoint *>(static_cast<const uint8_t *>(sl.host) + 16);
+    std::vector<ImageFeatures> out;
+    for (int i = 0; i < 2; ++i) {
+        if (counts[i] < 0 || counts[i] > n) throw std::runtime_error("cart_orb_detect: keypoint count out of range");
+        desc[i].rows = counts[i];   // the first counts[i] rows are the descriptors
+        out.emplace_back(std::vector<KeyPoint>(kpHost + (size_t)i * n, kpHost + (size_t)i * n + counts[i]), desc[i]);
+    }
+    return std::make_pair(out[0], out[1]);
+}
+
+ImageFeatureDetectorModule::ImageFeatureDetectorModule(int nfeatures) : SyncWrapperSystemModule("ImageFeatureDetector") {
+    if (nfeatures < 1 || nfeatures > CART_ORB_MAX_FEATURES) throw std::invalid_argument("nfeatures must be in [1, 65536]");
+    pool = std::make_shared<OrbPool>(nfeatures);
+    this->providesData.push_back(CARTSLAM_KEY_FEATURES);
+}
+ImageFeatureDetectorModule::~ImageFeatureDetectorModule() = default;
+
+system_data_t ImageFeatureDetectorModule::runInternal(System &, SystemRunData &data) {
+    if (data.dataElement->type != DataElementType::STEREO) throw std::runtime_error("ImageFeatureDetectorModule requires StereoDataElement");
+    auto stereo = std::static_pointer_cast<StereoDataElement>(data.dataElement);   // ImageFeatureDetectorVisitor::visitStereo
+    auto result = std::make_shared<std::pair<ImageFeatures, ImageFeatures>>(detectOrbFeatures(*pool, stereo->left, stereo->right));
+    return MODULE_RETURN(CARTSLAM_KEY_FEATURES, result);
 }
 }  // namespace cart

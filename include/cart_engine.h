@@ -392,6 +392,49 @@ int cart_planefit_status(cart_planefit *pf, int *bad_labels);
 int cart_plane_cluster(const double *planes, int max_label, const int32_t *offsets, const int32_t *neighbours, double *planes_out,
                        uint64_t *assignments, int *n_planes);
 
+/* ---- ORB keypoints and descriptors: ImageFeatureDetectorModule -------------------------------------------
+ * replaces: detectOrbFeatures (src/modules/features.cpp:48-66) = cv::cuda::ORB::create(CARTSLAM_OPTION_KEYPOINTS = 5000)
+ * ->detectAndComputeAsync(image, noArray(), keypoints, descriptors) + orb->convert(keypoints, host vector).  cv::cuda::ORB
+ * is not deterministic (atomic FAST append, unstable sort, fastAtan2), so the stage follows a deterministic spec with
+ * cv::cuda::ORB's structure and defaults (scale 1.2, 8 levels, edge 31, patch 31, FAST 20, Harris, WTA_K 2, no blur):
+ *   S20 pyramid level 0 = the image (S1 gray for 3 channels), level l = S16 of level l-1 to rint(w / 1.2^l) x rint(h / 1.2^l),
+ *       built while both sides are >= 63; per-level quotas n_l of nfeatures (cv::cuda::ORB's, last level clipped at 0);
+ *       FAST-9 score >= 20 on [31, w-31) x [31, h-31), strict 3x3 NMS, Harris R = 25 (ab - c^2) - (a+b)^2 (int64, 7x7);
+ *       per level the first n_l under (R desc, y asc, x asc); intensity-centroid moments over the half-size-15 patch,
+ *       quantised to 30 bins of 12 degrees by integer cross products; 256 steered point pairs drawn from the S17 stream.
+ *       Descriptors are NOT interchangeable with OpenCV's (different pattern); angles are multiples of 12 degrees. */
+#define CART_ORB_DEFAULT_FEATURES 5000   /* CARTSLAM_OPTION_KEYPOINTS, include/modules/features.hpp:11 */
+#define CART_ORB_MAX_FEATURES 65536
+#define CART_ORB_LEVELS 8
+#define CART_ORB_DESCRIPTOR_BYTES 32
+
+/* cv::KeyPoint's layout (28 B): pt.x, pt.y, size, angle, response, octave, class_id */
+typedef struct cart_keypoint {
+    float x, y, size, angle, response;
+    int32_t octave, class_id;
+} cart_keypoint;
+
+typedef struct cart_orb cart_orb;
+/* Workspaces (pyramids, candidate lists, counters, the steered pattern) for two images up to max_width x max_height and
+ * nfeatures in [1, 65536]; nothing is allocated per call.  Works on an engine of any disparity setting (0 / 0 included). */
+int cart_orb_create(cart_engine *engine, int max_width, int max_height, int nfeatures, cart_orb **out);
+void cart_orb_destroy(cart_orb *orb);
+/* Host only, no GPU (features.cpp's orb object's level layout): level sizes and quotas of all 8 levels into the arrays
+ * (each CART_ORB_LEVELS long, any may be NULL).  Returns the number of levels built (0..8), or -1 on bad arguments. */
+int cart_orb_levels(int width, int height, int nfeatures, int *level_w, int *level_h, int *level_n);
+/* detectAndComputeAsync + convert for 1 or 2 images (the left and right image of a frame go through one launch sequence,
+ * features.cpp:21-22).  images[i] = device u8, channels 1 (gray) or 3 (BGR), width x height <= the create size, rows
+ * steps[i] bytes apart.  Device outputs per image: keypoints[i] = cart_keypoint [nfeatures] (4-byte aligned),
+ * descriptors[i] = [nfeatures] rows of 32 bytes, descriptor_steps[i] bytes apart (NULL = 32), counts[i] = keypoints
+ * written (int32, device).  Keypoints are ordered by level, then (response desc, y asc, x asc).  No host synchronisation. */
+int cart_orb_detect(cart_orb *orb, int n_images, const uint8_t *const *images, const size_t *steps, int channels, int width,
+                    int height, cart_keypoint *const *keypoints, uint8_t *const *descriptors, const size_t *descriptor_steps,
+                    int32_t *counts, void *stream);
+/* Test / diagnostic access to the last detect call: level `level` of image `image` (device dst, level_w x level_h u8,
+ * dst_step bytes; NULL = not copied) and the number of NMS survivors of that level before selection (host int32, NULL =
+ * not read; synchronises `stream`).  Fails for a level that call did not build. */
+int cart_orb_debug_level(cart_orb *orb, int image, int level, uint8_t *dst, size_t dst_step, int32_t *n_candidates, void *stream);
+
 /* Stand-in for ImageOpticalFlowModule's device work (src/modules/optflow.cpp:96-140: cvtColor x2 +
  * cv::cuda::NvidiaOpticalFlow_2_0::calc(current, previous), NVIDIA fixed-function hardware): dense census block
  * matching (oracle S15).  cur / prev = the reference images of frame id and id-1 (1-channel gray or 3-channel BGR),
