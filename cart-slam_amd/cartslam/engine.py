@@ -403,43 +403,24 @@ class Engine:
         return {names[i].decode(): float(ms[i]) for i in range(n)}, calls.value
 
 
-class DevicePlaneSchedule:
-    """Device-side replay of the reference's plane-parameter bookkeeping (cart_plane_schedule_* in the C ABI)."""
+class _DeviceObject:
+    """A C-ABI object made on an engine: cart_<_name>_create(engine, ..., &out) and cart_<_name>_destroy.  A failing call
+    raises EngineError with the library's last error."""
+    _name = None
 
-    def __init__(self, engine, provider="histogram_peak", static_params=None, update_interval=30, reset_interval=10):
-        if provider not in ("histogram_peak", "static"):
-            raise ValueError("Unknown parameter provider type.")  # cartconfig.cpp:77
+    def __init__(self, engine, *args):
         self._eng = engine
         self._lib = engine._lib
-        init = PlaneParams(*(static_params or (0,) * 6))
         self._h = C.c_void_p()
-        rc = self._lib.cart_plane_schedule_create(engine._h, 1 if provider == "histogram_peak" else 0, C.byref(init), update_interval,
-                                                  reset_interval, C.byref(self._h))
-        if rc != 0:
-            raise EngineError("cart_plane_schedule_create: " + self._lib.cart_last_error(engine._h).decode())
+        self._check(getattr(self._lib, f"cart_{self._name}_create")(engine._h, *args, C.byref(self._h)), f"cart_{self._name}_create")
 
-    def advance(self, first_id, hists):
-        """hists: int32 CUDA [n,256] in frame-id order -> int32 CUDA [n,6] parameters per frame."""
-        import torch
-        if hists.dtype != torch.int32 or not hists.is_contiguous() or hists.dim() != 2 or hists.shape[1] != 256:
-            raise EngineError("hists must be a contiguous int32 [n,256] CUDA tensor")
-        out = torch.empty((hists.shape[0], 6), dtype=torch.int32, device=hists.device)
-        rc = self._lib.cart_plane_schedule_advance(self._h, first_id, hists.shape[0], C.c_void_p(hists.data_ptr()),
-                                                   C.c_void_p(out.data_ptr()), _stream_ptr())
+    def _check(self, rc, what):
         if rc != 0:
-            raise EngineError("cart_plane_schedule_advance: " + self._lib.cart_last_error(self._eng._h).decode())
-        return out
-
-    def read(self):
-        p = PlaneParams()
-        cum = (C.c_int32 * 256)()
-        if self._lib.cart_plane_schedule_read(self._h, C.byref(p), cum) != 0:
-            raise EngineError("cart_plane_schedule_read: " + self._lib.cart_last_error(self._eng._h).decode())
-        return p, np.array(cum, dtype=np.int32)
+            raise EngineError(f"{what}: " + self._lib.cart_last_error(self._eng._h).decode())
 
     def close(self):
         if getattr(self, "_h", None):
-            self._lib.cart_plane_schedule_destroy(self._h)
+            getattr(self._lib, f"cart_{self._name}_destroy")(self._h)
             self._h = None
 
     def __del__(self):
@@ -449,25 +430,44 @@ class DevicePlaneSchedule:
             pass
 
 
-class Superpixels:
+class DevicePlaneSchedule(_DeviceObject):
+    """Device-side replay of the reference's plane-parameter bookkeeping (cart_plane_schedule_* in the C ABI)."""
+    _name = "plane_schedule"
+
+    def __init__(self, engine, provider="histogram_peak", static_params=None, update_interval=30, reset_interval=10):
+        if provider not in ("histogram_peak", "static"):
+            raise ValueError("Unknown parameter provider type.")  # cartconfig.cpp:77
+        init = PlaneParams(*(static_params or (0,) * 6))
+        super().__init__(engine, 1 if provider == "histogram_peak" else 0, C.byref(init), update_interval, reset_interval)
+
+    def advance(self, first_id, hists):
+        """hists: int32 CUDA [n,256] in frame-id order -> int32 CUDA [n,6] parameters per frame."""
+        import torch
+        if hists.dtype != torch.int32 or not hists.is_contiguous() or hists.dim() != 2 or hists.shape[1] != 256:
+            raise EngineError("hists must be a contiguous int32 [n,256] CUDA tensor")
+        out = torch.empty((hists.shape[0], 6), dtype=torch.int32, device=hists.device)
+        self._check(self._lib.cart_plane_schedule_advance(self._h, first_id, hists.shape[0], C.c_void_p(hists.data_ptr()),
+                                                          C.c_void_p(out.data_ptr()), _stream_ptr()), "cart_plane_schedule_advance")
+        return out
+
+    def read(self):
+        p = PlaneParams()
+        cum = (C.c_int32 * 256)()
+        self._check(self._lib.cart_plane_schedule_read(self._h, C.byref(p), cum), "cart_plane_schedule_read")
+        return p, np.array(cum, dtype=np.int32)
+
+
+class Superpixels(_DeviceObject):
     """The reference's ContourRelaxation object (persistent label image + relax), cart_superpixels_* in the C ABI.
     Label images are uint16; torch tensors carry them as int16 (same bits)."""
+    _name = "superpixels"
 
     def __init__(self, engine, block_size=12, direct_clique_cost=0.5, diagonal_clique_cost=None, compactness_weight=0.1,
                  progressive_compactness_cost=0.0, image_weight=1.5, disparity_weight=1.0, block_h=None):
-        self._eng = engine
-        self._lib = engine._lib
         p = SuperpixelParams(direct_clique_cost, direct_clique_cost / np.sqrt(2.0) if diagonal_clique_cost is None else diagonal_clique_cost,
                              compactness_weight, progressive_compactness_cost, image_weight, disparity_weight)
         self.params = p
-        self._h = C.c_void_p()
-        rc = self._lib.cart_superpixels_create(engine._h, C.byref(p), int(block_size), int(block_h or block_size), C.byref(self._h))
-        if rc != 0:
-            raise EngineError("cart_superpixels_create: " + self._lib.cart_last_error(engine._h).decode())
-
-    def _check(self, rc, what):
-        if rc != 0:
-            raise EngineError(f"{what}: " + self._lib.cart_last_error(self._eng._h).decode())
+        super().__init__(engine, C.byref(p), int(block_size), int(block_h or block_size))
 
     @property
     def max_label(self):
@@ -498,35 +498,16 @@ class Superpixels:
                     "cart_superpixels_relax")
         return out
 
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.cart_superpixels_destroy(self._h)
-            self._h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class PlaneFit:
+class PlaneFit(_DeviceObject):
     """Superpixel plane fitting (cart_planefit_* in the C ABI): per-label RANSAC planes, point lists,
     8-neighbour adjacency and the planefit assignment loop on the device.  Labels are uint16 carried as int16 tensors,
     xyz is float32 [h, w, 3] (the "depth" image)."""
+    _name = "planefit"
 
     def __init__(self, engine, max_label_capacity=16383):
-        self._eng = engine
-        self._lib = engine._lib
-        self._h = C.c_void_p()
         self.max_label = None
-        rc = self._lib.cart_planefit_create(engine._h, int(max_label_capacity), C.byref(self._h))
-        if rc != 0:
-            raise EngineError("cart_planefit_create: " + self._lib.cart_last_error(engine._h).decode())
-
-    def _check(self, rc, what):
-        if rc != 0:
-            raise EngineError(f"{what}: " + self._lib.cart_last_error(self._eng._h).decode())
+        super().__init__(engine, int(max_label_capacity))
 
     def _labels(self, labels):
         if labels.element_size() != 2 or tuple(labels.shape) != (self._eng.height, self._eng.width):
@@ -595,17 +576,6 @@ class PlaneFit:
         self._check(self._lib.cart_planefit_status(self._h, C.byref(bad)), "cart_planefit_status")
         return bool(bad.value)
 
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.cart_planefit_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 KEYPOINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"), ("response", "<f4"), ("octave", "<i4"),
                            ("class_id", "<i4")])   # cart_keypoint = cv::KeyPoint's layout
@@ -621,24 +591,16 @@ def orb_levels(width, height, nfeatures=_lib.ORB_DEFAULT_FEATURES):
     return n, [(arr[0][l], arr[1][l], arr[2][l]) for l in range(_lib.ORB_LEVELS)]
 
 
-class OrbFeatures:
+class OrbFeatures(_DeviceObject):
     """ORB keypoints + steered-BRIEF descriptors (cart_orb_* in the C ABI): the work of the reference's
     ImageFeatureDetectorModule (cv::cuda::ORB::create(5000)->detectAndComputeAsync + convert) for images up to
     max_width x max_height."""
+    _name = "orb"
 
     def __init__(self, engine, max_width, max_height, nfeatures=_lib.ORB_DEFAULT_FEATURES):
-        self._eng = engine
-        self._lib = engine._lib
-        self._h = C.c_void_p()
         self.nfeatures = int(nfeatures)
         self._size = None
-        rc = self._lib.cart_orb_create(engine._h, int(max_width), int(max_height), self.nfeatures, C.byref(self._h))
-        if rc != 0:
-            raise EngineError("cart_orb_create: " + self._lib.cart_last_error(engine._h).decode())
-
-    def _check(self, rc, what):
-        if rc != 0:
-            raise EngineError(f"{what}: " + self._lib.cart_last_error(self._eng._h).decode())
+        super().__init__(engine, int(max_width), int(max_height), self.nfeatures)
 
     def levels(self, width=None, height=None):
         """-> (built levels, [(w_l, h_l, n_l)] x 8) for this object's nfeatures; default size = the last detect call's."""
@@ -693,17 +655,6 @@ class OrbFeatures:
         self._check(self._lib.cart_orb_debug_level(self._h, int(image), int(level), C.c_void_p(dst.data_ptr()), w, C.byref(n), _stream_ptr()),
                     "cart_orb_debug_level")
         return dst, n.value
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.cart_orb_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def plane_cluster(planes, offsets, neighbours):

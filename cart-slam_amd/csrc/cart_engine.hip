@@ -311,6 +311,70 @@ SlabTable slab_table(const SlabPool &sp, int s0, int n, const std::vector<uint8_
     return t;
 }
 
+// The lifecycle of the stateful device objects (cart_superpixels, cart_planefit, cart_orb).  An object keeps the device and
+// geometry of the engine it was made on, not the engine, so that it may be destroyed after its engine.  Calls on one object are
+// serialised by `mu` (superpixels.cu:97-99); a call that arrives on another stream than the previous one first waits for
+// `done`, which every call records on its stream (ObjectCall).
+struct DeviceObject {
+    int device_id;
+    Geometry g;
+    std::mutex mu;
+    hipEvent_t done = nullptr;
+    hipStream_t last_stream = nullptr;
+    bool used = false;
+    std::vector<void *> bufs;   // every device allocation, freed by destroy_object
+
+    explicit DeviceObject(const cart_engine *e) : device_id(e->params.device_id), g(e->g) {}
+    // hipMalloc recorded in bufs; a zero-byte request gets a small real buffer (hipMalloc would hand back no pointer)
+    template <typename T>
+    int alloc(T **p, size_t bytes) {
+        HIP_TRY(hipMalloc(reinterpret_cast<void **>(p), bytes ? bytes : 256));
+        bufs.push_back(*p);
+        return 0;
+    }
+    int create_event() {
+        HIP_TRY(hipEventCreateWithFlags(&done, hipEventDisableTiming));
+        return 0;
+    }
+};
+
+// One entry point's hold on an object: begin() makes the object's device current, takes its lock and orders the call after
+// the previous one if that came on another stream; once begin() has succeeded, every way out of the call, early error
+// returns included, records `done` on the call's stream.
+class ObjectCall {
+   public:
+    ObjectCall(DeviceObject &o, hipStream_t stream) : o(o), stream(stream) {}
+    int begin() {
+        HIP_TRY(hipSetDevice(o.device_id));
+        lk = std::unique_lock<std::mutex>(o.mu);
+        if (o.used && o.last_stream != stream) HIP_TRY(hipStreamWaitEvent(stream, o.done, 0));
+        entered = true;
+        return 0;
+    }
+    ~ObjectCall() {
+        if (!entered) return;
+        (void)hipEventRecord(o.done, stream);
+        o.last_stream = stream;
+        o.used = true;
+    }
+
+   private:
+    DeviceObject &o;
+    hipStream_t stream;
+    std::unique_lock<std::mutex> lk;   // released after the record above
+    bool entered = false;
+};
+
+template <typename T>
+void destroy_object(T *o) {
+    if (!o) return;
+    (void)hipSetDevice(o->device_id);   // the caller's current device may be another one
+    (void)hipDeviceSynchronize();
+    for (void *b : o->bufs) (void)hipFree(b);
+    if (o->done) (void)hipEventDestroy(o->done);
+    delete o;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1164,8 +1228,8 @@ int cart_reproject_depth(cart_engine *e, int n_frames, const int16_t *disp, size
 }
 
 // ---- superpixels (replaces ContourRelaxation + SuperPixelModule's device work; oracle S13/S14) ----
-struct cart_superpixels {
-    cart_engine *engine = nullptr;
+struct cart_superpixels : DeviceObject {
+    using DeviceObject::DeviceObject;
     cart_superpixel_params params;
     int block_w = 0, block_h = 0;
     int max_label_id = 0;        // number of initial blocks (labels are < max_label_id)
@@ -1175,29 +1239,7 @@ struct cart_superpixels {
     long long *stats = nullptr;  // [kSpStatRows][ld] statistics followed by [kSpStatRows][ld] of per-sweep delta (capacity 2 x kSpStatRows x kSpMaxLabels)
     double *costs = nullptr;
     int *max_seen = nullptr;
-    std::mutex mu;               // serialises calls (superpixels.cu:97-99)
-    hipEvent_t done = nullptr;   // orders successive calls that arrive on different streams
-    hipStream_t last_stream = nullptr;
-    bool used = false;
-    unsigned long long released_seq = 0;  // order of the last release (guarded by mu)
 };
-
-namespace {
-int sp_enter(cart_superpixels *sp, hipStream_t stream) {
-    if (sp->used && sp->last_stream != stream) HIP_TRY(hipStreamWaitEvent(stream, sp->done, 0));
-    return 0;
-}
-void sp_leave(cart_superpixels *sp, hipStream_t stream) {
-    (void)hipEventRecord(sp->done, stream);
-    sp->last_stream = stream;
-    sp->used = true;
-}
-// records the completion event on every way out of a call, early error returns included
-struct SpScope {
-    cart_superpixels *sp; hipStream_t stream;
-    ~SpScope() { sp_leave(sp, stream); }
-};
-}  // namespace
 
 void cart_superpixel_default_params(cart_superpixel_params *p) {
     if (!p) return;
@@ -1220,50 +1262,35 @@ int cart_superpixels_create(cart_engine *e, const cart_superpixel_params *params
     const long blocks = (long)((g.w + block_w - 1) / block_w) * ((g.h + block_h - 1) / block_h);
     if (blocks >= kSpMaxLabels) return fail("too many superpixels: number of blocks must be < 16384 (increase block size)");
     HIP_TRY(hipSetDevice(e->params.device_id));
-    cart_superpixels *sp = new (std::nothrow) cart_superpixels;
+    cart_superpixels *sp = new (std::nothrow) cart_superpixels(e);
     if (!sp) return fail("out of host memory");
-    sp->engine = e; sp->params = *params; sp->block_w = block_w; sp->block_h = block_h; sp->max_label_id = (int)blocks;
+    sp->params = *params; sp->block_w = block_w; sp->block_h = block_h; sp->max_label_id = (int)blocks;
     const size_t stat_elems = (size_t)kSpStatRows * kSpMaxLabels;
-    bool ok = hipMalloc(reinterpret_cast<void **>(&sp->labels[0]), g.npx * 2) == hipSuccess &&
-              hipMalloc(reinterpret_cast<void **>(&sp->labels[1]), g.npx * 2) == hipSuccess &&
-              hipMalloc(reinterpret_cast<void **>(&sp->ycc), g.npx * 4) == hipSuccess &&
-              hipMalloc(reinterpret_cast<void **>(&sp->stats), 2 * stat_elems * 8) == hipSuccess &&   // statistics, then their per-sweep delta (one memset per call)
-              hipMalloc(reinterpret_cast<void **>(&sp->costs), (size_t)kSpChannels * kSpMaxLabels * 8) == hipSuccess &&
-              hipMalloc(reinterpret_cast<void **>(&sp->max_seen), sizeof(int)) == hipSuccess &&
-              hipEventCreateWithFlags(&sp->done, hipEventDisableTiming) == hipSuccess;
-    if (ok) {
+    bool failed = sp->alloc(&sp->labels[0], g.npx * 2) || sp->alloc(&sp->labels[1], g.npx * 2) || sp->alloc(&sp->ycc, g.npx * 4) ||
+                  sp->alloc(&sp->stats, 2 * stat_elems * 8) ||   // statistics, then their per-sweep delta (one memset per call)
+                  sp->alloc(&sp->costs, (size_t)kSpChannels * kSpMaxLabels * 8) || sp->alloc(&sp->max_seen, sizeof(int)) || sp->create_event();
+    if (!failed) {
         launch_sp_block_init(sp->labels[0], g.w, g.h, block_w, block_h, nullptr);
-        ok = hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess;
+        failed = hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess;
     }
-    if (!ok) {
-        cart_superpixels_destroy(sp);
+    if (failed) {
+        destroy_object(sp);
         return fail("allocating the superpixel state failed");
     }
     *out = sp;
     return 0;
 }
 
-void cart_superpixels_destroy(cart_superpixels *sp) {
-    if (!sp) return;
-    if (sp->engine) (void)hipSetDevice(sp->engine->params.device_id);
-    (void)hipDeviceSynchronize();
-    void *bufs[] = {sp->labels[0], sp->labels[1], sp->ycc, sp->stats, sp->costs, sp->max_seen};
-    for (void *b : bufs)
-        if (b) (void)hipFree(b);
-    if (sp->done) (void)hipEventDestroy(sp->done);
-    delete sp;
-}
+void cart_superpixels_destroy(cart_superpixels *sp) { destroy_object(sp); }
 
 int cart_superpixels_max_label(const cart_superpixels *sp) { return sp ? sp->max_label_id : -1; }
 
 int cart_superpixels_reset(cart_superpixels *sp, void *stream_) {
     if (!sp) return fail("superpixels is NULL");
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    const Geometry &g = sp->engine->g;
-    HIP_TRY(hipSetDevice(sp->engine->params.device_id));
-    std::lock_guard<std::mutex> lk(sp->mu);
-    if (sp_enter(sp, stream)) return -1;
-    SpScope scope{sp, stream};
+    const Geometry &g = sp->g;
+    ObjectCall call(*sp, stream);
+    if (call.begin()) return -1;
     launch_sp_block_init(sp->labels[sp->cur], g.w, g.h, sp->block_w, sp->block_h, stream);
     sp->max_label_id = ((g.w + sp->block_w - 1) / sp->block_w) * ((g.h + sp->block_h - 1) / sp->block_h);
     HIP_TRY(hipGetLastError());
@@ -1273,13 +1300,11 @@ int cart_superpixels_reset(cart_superpixels *sp, void *stream_) {
 int cart_superpixels_set_labels(cart_superpixels *sp, const uint16_t *labels, size_t labels_step, int max_label_id, void *stream_) {
     if (!sp || !labels) return fail("bad arguments");
     if (max_label_id < 1 || max_label_id >= kSpMaxLabels) return fail("max_label_id must be in [1, 16384)");
-    const Geometry &g = sp->engine->g;
+    const Geometry &g = sp->g;
     if (labels_step < (size_t)g.w * 2 || (labels_step & 1)) return fail("bad step");
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    HIP_TRY(hipSetDevice(sp->engine->params.device_id));
-    std::lock_guard<std::mutex> lk(sp->mu);
-    if (sp_enter(sp, stream)) return -1;
-    SpScope scope{sp, stream};
+    ObjectCall call(*sp, stream);
+    if (call.begin()) return -1;
     // the copy goes to the spare buffer and becomes the state only if every label is in range
     uint16_t *spare = sp->labels[sp->cur ^ 1];
     HIP_TRY(hipMemsetAsync(sp->max_seen, 0, sizeof(int), stream));
@@ -1299,7 +1324,7 @@ int cart_superpixels_relax(cart_superpixels *sp, const uint8_t *image, size_t im
     if (!image) return fail("NULL pointer");
     if (channels != 1 && channels != 3) return fail("channels must be 1 or 3");
     if (iterations < 0) return fail("iterations must be >= 0");
-    const Geometry &g = sp->engine->g;
+    const Geometry &g = sp->g;
     const cart_superpixel_params &p = sp->params;
     if (image_step < (size_t)g.w * channels) return fail("bad step");
     if (p.disparity_weight > 0) {
@@ -1308,10 +1333,8 @@ int cart_superpixels_relax(cart_superpixels *sp, const uint8_t *image, size_t im
     }
     if (labels_out && (labels_out_step < (size_t)g.w * 2 || (labels_out_step & 1))) return fail("bad step");
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    HIP_TRY(hipSetDevice(sp->engine->params.device_id));
-    std::lock_guard<std::mutex> lk(sp->mu);
-    if (sp_enter(sp, stream)) return -1;
-    SpScope scope{sp, stream};
+    ObjectCall call(*sp, stream);
+    if (call.begin()) return -1;
     const int ld = sp->max_label_id + 1;
     SpRelaxArgs a;
     std::memset(&a, 0, sizeof(a));
@@ -1381,8 +1404,8 @@ int cart_superpixel_plane_classify(cart_engine *e, const int16_t *deriv2, size_t
 }
 
 // ---- superpixel plane fitting ----
-struct cart_planefit {
-    cart_engine *engine = nullptr;
+struct cart_planefit : DeviceObject {
+    using DeviceObject::DeviceObject;
     int cap_L1 = 0, ntiles = 0;
     int32_t *cursor = nullptr;    // [ntiles][cap_L1] tile counts -> tile offsets
     int32_t *cnt = nullptr;       // [cap_L1][2]
@@ -1397,21 +1420,9 @@ struct cart_planefit {
     double *local = nullptr;      // [kPfMaxLocal][4]
     uint64_t *accept = nullptr;   // [cap_L1]
     int last_L1 = 0, last_pred = -1;
-    std::mutex mu;
-    hipEvent_t done = nullptr;
-    hipStream_t last_stream = nullptr;
-    bool used = false;
 };
 
 namespace {
-int pf_enter(cart_planefit *pf, hipStream_t stream) {   // orders calls on one object that arrive on different streams
-    if (pf->used && pf->last_stream != stream) HIP_TRY(hipStreamWaitEvent(stream, pf->done, 0));
-    return 0;
-}
-struct PfScope {
-    cart_planefit *pf; hipStream_t stream;
-    ~PfScope() { (void)hipEventRecord(pf->done, stream); pf->last_stream = stream; pf->used = true; }
-};
 int pf_grid_slots(int w, int h) {   // selectRandomSuperpixels(4, 3) positions (planefit.cu:333-351)
     const int ys = h / 5, xs = w / 6;
     return (ys > 0 && xs > 0) ? ((h - 1) / ys) * ((w - 1) / xs) : 0;
@@ -1424,33 +1435,23 @@ int cart_planefit_create(cart_engine *e, int max_label_capacity, cart_planefit *
     const Geometry &g = e->g;
     if (pf_grid_slots(g.w, g.h) > kPfMaxLocal) return fail("image too small for the planefit sampling grid");
     HIP_TRY(hipSetDevice(e->params.device_id));
-    cart_planefit *pf = new (std::nothrow) cart_planefit;
+    cart_planefit *pf = new (std::nothrow) cart_planefit(e);
     if (!pf) return fail("out of host memory");
-    pf->engine = e; pf->cap_L1 = max_label_capacity + 1; pf->ntiles = pf_tiles(g.w, g.h);
+    pf->cap_L1 = max_label_capacity + 1; pf->ntiles = pf_tiles(g.w, g.h);
     const size_t L1 = (size_t)pf->cap_L1;
-    auto al = [](auto **p, size_t bytes) { return hipMalloc(reinterpret_cast<void **>(p), bytes) == hipSuccess; };
-    bool ok = al(&pf->cursor, (size_t)pf->ntiles * L1 * 4) && al(&pf->cnt, L1 * 8) && al(&pf->npts, L1 * 4) && al(&pf->start, (L1 + 1) * 4) &&
-              al(&pf->err, 4) && al(&pf->pts, g.npx * sizeof(float4)) && al(&pf->planes17, L1 * 32) && al(&pf->adj_cnt, L1 * 4) &&
-              al(&pf->state, sizeof(PfFitState)) && al(&pf->local, (size_t)kPfMaxLocal * 32) && al(&pf->accept, L1 * 8) &&
-              hipMemset(pf->err, 0, 4) == hipSuccess && hipEventCreateWithFlags(&pf->done, hipEventDisableTiming) == hipSuccess;
-    if (!ok) {
-        cart_planefit_destroy(pf);
+    if (pf->alloc(&pf->cursor, (size_t)pf->ntiles * L1 * 4) || pf->alloc(&pf->cnt, L1 * 8) || pf->alloc(&pf->npts, L1 * 4) ||
+        pf->alloc(&pf->start, (L1 + 1) * 4) || pf->alloc(&pf->err, 4) || pf->alloc(&pf->pts, g.npx * sizeof(float4)) ||
+        pf->alloc(&pf->planes17, L1 * 32) || pf->alloc(&pf->adj_cnt, L1 * 4) || pf->alloc(&pf->state, sizeof(PfFitState)) ||
+        pf->alloc(&pf->local, (size_t)kPfMaxLocal * 32) || pf->alloc(&pf->accept, L1 * 8) || hipMemset(pf->err, 0, 4) != hipSuccess ||
+        pf->create_event()) {
+        destroy_object(pf);
         return fail("allocating the planefit workspaces failed");
     }
     *out = pf;
     return 0;
 }
 
-void cart_planefit_destroy(cart_planefit *pf) {
-    if (!pf) return;
-    if (pf->engine) (void)hipSetDevice(pf->engine->params.device_id);
-    (void)hipDeviceSynchronize();
-    void *bufs[] = {pf->cursor, pf->cnt, pf->npts, pf->start, pf->err, pf->pts, pf->planes17, pf->bits, pf->adj_cnt, pf->state, pf->local, pf->accept};
-    for (void *b : bufs)
-        if (b) (void)hipFree(b);
-    if (pf->done) (void)hipEventDestroy(pf->done);
-    delete pf;
-}
+void cart_planefit_destroy(cart_planefit *pf) { destroy_object(pf); }
 
 int cart_planefit_label_planes(cart_planefit *pf, const uint16_t *labels, size_t labels_step, int max_label, const float *xyz, size_t xyz_step,
                                int predicate, double thr, uint64_t seed, uint64_t frame_id, double *planes, int32_t *npoints, int32_t *counts,
@@ -1460,13 +1461,11 @@ int cart_planefit_label_planes(cart_planefit *pf, const uint16_t *labels, size_t
     if (max_label < 0 || max_label + 1 > pf->cap_L1) return fail("max_label must be in [0, max_label_capacity]");
     if (predicate != CART_PLANE_PREDICATE_PLANEFIT && predicate != CART_PLANE_PREDICATE_PLANECLUSTER) return fail("unknown predicate");
     if (!(thr > 0)) return fail("thr must be positive");
-    const Geometry &g = pf->engine->g;
+    const Geometry &g = pf->g;
     if (labels_step < (size_t)g.w * 2 || (labels_step & 1) || xyz_step < (size_t)g.w * 12 || (xyz_step & 3)) return fail("bad step");
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    HIP_TRY(hipSetDevice(pf->engine->params.device_id));
-    std::lock_guard<std::mutex> lk(pf->mu);
-    if (pf_enter(pf, stream)) return -1;
-    PfScope scope{pf, stream};
+    ObjectCall call(*pf, stream);
+    if (call.begin()) return -1;
     const int L1 = max_label + 1;
     HIP_TRY(hipMemsetAsync(pf->cursor, 0, (size_t)pf->ntiles * L1 * 4, stream));
     HIP_TRY(hipMemsetAsync(pf->cnt, 0, (size_t)L1 * 8, stream));
@@ -1488,10 +1487,8 @@ int cart_planefit_points(cart_planefit *pf, float *points, size_t capacity, int3
     if (!points || !offsets) return fail("NULL pointer");
     if (pf->last_L1 == 0) return fail("no label_planes call yet");
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    HIP_TRY(hipSetDevice(pf->engine->params.device_id));
-    std::lock_guard<std::mutex> lk(pf->mu);
-    if (pf_enter(pf, stream)) return -1;
-    PfScope scope{pf, stream};
+    ObjectCall call(*pf, stream);
+    if (call.begin()) return -1;
     int32_t total = 0;
     HIP_TRY(hipMemcpyAsync(&total, pf->start + pf->last_L1, 4, hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
@@ -1506,17 +1503,15 @@ int cart_planefit_adjacency(cart_planefit *pf, const uint16_t *labels, size_t la
     if (!pf) return fail("planefit is NULL");
     if (!labels || !offsets || !neighbours) return fail("NULL pointer");
     if (max_label < 0 || max_label + 1 > pf->cap_L1) return fail("max_label must be in [0, max_label_capacity]");
-    const Geometry &g = pf->engine->g;
+    const Geometry &g = pf->g;
     if (labels_step < (size_t)g.w * 2 || (labels_step & 1)) return fail("bad step");
     const size_t L1 = (size_t)max_label + 1;
     if (capacity < std::min(8 * g.npx, L1 * (L1 - 1))) return fail("capacity must be >= min(8 * width * height, (max_label + 1) * max_label)");
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    HIP_TRY(hipSetDevice(pf->engine->params.device_id));
-    std::lock_guard<std::mutex> lk(pf->mu);
+    ObjectCall call(*pf, stream);
+    if (call.begin()) return -1;
     const size_t words = ((size_t)pf->cap_L1 + 31) / 32;
-    if (!pf->bits) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&pf->bits), (size_t)pf->cap_L1 * words * 4));
-    if (pf_enter(pf, stream)) return -1;
-    PfScope scope{pf, stream};
+    if (!pf->bits && pf->alloc(&pf->bits, (size_t)pf->cap_L1 * words * 4)) return -1;
     const size_t used_words = (L1 + 31) / 32;
     HIP_TRY(hipMemsetAsync(pf->bits, 0, L1 * used_words * 4, stream));
     HIP_TRY(hipMemsetAsync(pf->err, 0, 4, stream));
@@ -1531,13 +1526,11 @@ int cart_planefit_fit(cart_planefit *pf, const uint16_t *labels, size_t labels_s
     if (!labels || !planes || !assignments || !n_planes) return fail("NULL pointer");
     if (pf->last_L1 == 0 || pf->last_pred != CART_PLANE_PREDICATE_PLANEFIT)
         return fail("cart_planefit_fit needs a preceding label_planes call with CART_PLANE_PREDICATE_PLANEFIT");
-    const Geometry &g = pf->engine->g;
+    const Geometry &g = pf->g;
     if (labels_step < (size_t)g.w * 2 || (labels_step & 1)) return fail("bad step");
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    HIP_TRY(hipSetDevice(pf->engine->params.device_id));
-    std::lock_guard<std::mutex> lk(pf->mu);
-    if (pf_enter(pf, stream)) return -1;
-    PfScope scope{pf, stream};
+    ObjectCall call(*pf, stream);
+    if (call.begin()) return -1;
     PfFitArgs a;
     std::memset(&a, 0, sizeof(a));
     a.labels = labels; a.lstep = labels_step; a.w = g.w; a.h = g.h; a.L1 = pf->last_L1; a.seed = seed; a.frame = frame_id;
@@ -1551,7 +1544,7 @@ int cart_planefit_fit(cart_planefit *pf, const uint16_t *labels, size_t labels_s
 
 int cart_planefit_status(cart_planefit *pf, int *bad_labels) {
     if (!pf || !bad_labels) return fail("bad arguments");
-    HIP_TRY(hipSetDevice(pf->engine->params.device_id));
+    HIP_TRY(hipSetDevice(pf->device_id));
     std::lock_guard<std::mutex> lk(pf->mu);
     int32_t err = 0;
     if (pf->used) HIP_TRY(hipEventSynchronize(pf->done));
@@ -1706,8 +1699,8 @@ int orb_cap(int w, int h) {   // strict NMS: at most one survivor per 2x2 block 
 }
 }  // namespace
 
-struct cart_orb {
-    cart_engine *engine = nullptr;
+struct cart_orb : DeviceObject {
+    using DeviceObject::DeviceObject;
     int max_w = 0, max_h = 0, nfeatures = 0;
     size_t pyr_off[kOrbLevels] = {}, cand_off[kOrbLevels] = {};
     int cap[kOrbLevels] = {};
@@ -1720,22 +1713,7 @@ struct cart_orb {
     char4 *pattern = nullptr;      // [30][256]
     OrbLayout last;                // of the last detect call
     int last_images = 0;
-    std::mutex mu;
-    hipEvent_t done = nullptr;
-    hipStream_t last_stream = nullptr;
-    bool used = false;
 };
-
-namespace {
-int orb_enter(cart_orb *o, hipStream_t stream) {   // orders calls on one object that arrive on different streams
-    if (o->used && o->last_stream != stream) HIP_TRY(hipStreamWaitEvent(stream, o->done, 0));
-    return 0;
-}
-struct OrbScope {
-    cart_orb *o; hipStream_t stream;
-    ~OrbScope() { (void)hipEventRecord(o->done, stream); o->last_stream = stream; o->used = true; }
-};
-}  // namespace
 
 int cart_orb_levels(int width, int height, int nfeatures, int *level_w, int *level_h, int *level_n) {
     if (width < 1 || height < 1 || width > 16384 || height > 16384) return fail("width / height must be in [1, 16384]");
@@ -1755,9 +1733,9 @@ int cart_orb_create(cart_engine *e, int max_width, int max_height, int nfeatures
     if (max_width < 1 || max_height < 1 || max_width > 16384 || max_height > 16384) return fail("max_width / max_height must be in [1, 16384]");
     if (nfeatures < 1 || nfeatures > CART_ORB_MAX_FEATURES) return fail("nfeatures must be in [1, 65536]");
     HIP_TRY(hipSetDevice(e->params.device_id));
-    cart_orb *o = new (std::nothrow) cart_orb;
+    cart_orb *o = new (std::nothrow) cart_orb(e);
     if (!o) return fail("out of host memory");
-    o->engine = e; o->max_w = max_width; o->max_h = max_height; o->nfeatures = nfeatures;
+    o->max_w = max_width; o->max_h = max_height; o->nfeatures = nfeatures;
     OrbLayout L;
     orb_layout(max_width, max_height, nfeatures, L);
     for (int l = 0; l < L.n_levels; ++l) {   // sizes only shrink with the image, so the create-size layout holds every call
@@ -1769,30 +1747,18 @@ int cart_orb_create(cart_engine *e, int max_width, int max_height, int nfeatures
     }
     std::vector<char4> pat;
     orb_steered_pattern(pat);
-    auto al = [](auto **p, size_t bytes) { return hipMalloc(reinterpret_cast<void **>(p), bytes ? bytes : 256) == hipSuccess; };
-    bool ok = al(&o->pyr, 2 * o->pyr_stride) && al(&o->cand, 2 * o->cand_stride * sizeof(OrbCand)) && al(&o->cand_cnt, 2 * kOrbLevels * 4) &&
-              al(&o->sel, 2 * (size_t)nfeatures * sizeof(OrbCand)) && al(&o->kpi, 2 * (size_t)nfeatures * sizeof(int4)) &&
-              al(&o->pattern, pat.size() * sizeof(char4)) &&
-              hipMemcpy(o->pattern, pat.data(), pat.size() * sizeof(char4), hipMemcpyHostToDevice) == hipSuccess &&
-              hipEventCreateWithFlags(&o->done, hipEventDisableTiming) == hipSuccess;
-    if (!ok) {
-        cart_orb_destroy(o);
+    if (o->alloc(&o->pyr, 2 * o->pyr_stride) || o->alloc(&o->cand, 2 * o->cand_stride * sizeof(OrbCand)) ||   // both 0 when no level is built
+        o->alloc(&o->cand_cnt, 2 * kOrbLevels * 4) || o->alloc(&o->sel, 2 * (size_t)nfeatures * sizeof(OrbCand)) ||
+        o->alloc(&o->kpi, 2 * (size_t)nfeatures * sizeof(int4)) || o->alloc(&o->pattern, pat.size() * sizeof(char4)) ||
+        hipMemcpy(o->pattern, pat.data(), pat.size() * sizeof(char4), hipMemcpyHostToDevice) != hipSuccess || o->create_event()) {
+        destroy_object(o);
         return fail("allocating the ORB workspaces failed");
     }
     *out = o;
     return 0;
 }
 
-void cart_orb_destroy(cart_orb *o) {
-    if (!o) return;
-    if (o->engine) (void)hipSetDevice(o->engine->params.device_id);
-    (void)hipDeviceSynchronize();
-    void *bufs[] = {o->pyr, o->cand, o->cand_cnt, o->sel, o->kpi, o->pattern};
-    for (void *b : bufs)
-        if (b) (void)hipFree(b);
-    if (o->done) (void)hipEventDestroy(o->done);
-    delete o;
-}
+void cart_orb_destroy(cart_orb *o) { destroy_object(o); }
 
 int cart_orb_detect(cart_orb *o, int n_images, const uint8_t *const *images, const size_t *steps, int channels, int width, int height,
                     cart_keypoint *const *keypoints, uint8_t *const *descriptors, const size_t *descriptor_steps, int32_t *counts, void *stream_) {
@@ -1836,10 +1802,8 @@ int cart_orb_detect(cart_orb *o, int n_images, const uint8_t *const *images, con
         v.scale = (float)L.s[l];
     }
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    HIP_TRY(hipSetDevice(o->engine->params.device_id));
-    std::lock_guard<std::mutex> lk(o->mu);
-    if (orb_enter(o, stream)) return -1;
-    OrbScope scope{o, stream};
+    ObjectCall call(*o, stream);
+    if (call.begin()) return -1;
     o->last = L;
     o->last_images = n_images;
     if (L.n_levels == 0) {   // no level is large enough: no keypoints
@@ -1862,10 +1826,8 @@ int cart_orb_debug_level(cart_orb *o, int image, int level, uint8_t *dst, size_t
     const int w = o->last.w[level], h = o->last.h[level];
     if (dst && dst_step < (size_t)w) return fail("bad step");
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    HIP_TRY(hipSetDevice(o->engine->params.device_id));
-    std::lock_guard<std::mutex> lk(o->mu);
-    if (orb_enter(o, stream)) return -1;
-    OrbScope scope{o, stream};
+    ObjectCall call(*o, stream);
+    if (call.begin()) return -1;
     if (dst) HIP_TRY(hipMemcpy2DAsync(dst, dst_step, o->pyr + (size_t)image * o->pyr_stride + o->pyr_off[level], (size_t)w, (size_t)w, (size_t)h,
                                       hipMemcpyDeviceToDevice, stream));
     if (n_candidates) {

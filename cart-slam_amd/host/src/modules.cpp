@@ -654,14 +654,17 @@ void HistogramPeakPlaneParameterProvider::updatePlaneParameters(System &, System
     verticalCenter = p.vertical_center;
 }
 
-// ---------------------------------------------------------------- superpixel plane fit / cluster (planefit.cu:182-445, planecluster.cpp:19-177)
-// The engine and the cart_planefit workspaces are made for the first frame's image size and kept: a free slot is leased
-// per frame, so frames of one run may overlap.  Every slot owns its device output buffer and a pinned host buffer for the
-// download; both only grow, and a slot's buffers are touched by one frame at a time (no allocation or free inside a frame).
-class PlaneFitPool {
+// ---------------------------------------------------------------- device-object slot pool (planefit / cluster, ORB)
+// The engine and the device objects are made for the first frame's image size and kept: a free slot is leased per frame, so
+// frames of one run may overlap.  Every slot owns one object, a device output buffer and a pinned host buffer for the download;
+// both buffers only grow, and a slot is touched by one frame at a time (no allocation or free inside a frame once it has grown).
+// The slots are destroyed before the engine they were made on.
+template <typename T, void (*Destroy)(T *)>
+class DeviceObjectPool {
    public:
+    using Create = std::function<int(cart_engine *, Size, T **)>;
     struct Slot {
-        cart_planefit *pf = nullptr;
+        T *obj = nullptr;
         void *dev = nullptr, *host = nullptr;
         size_t devBytes = 0, hostBytes = 0;
         void reserve(size_t dBytes, size_t hBytes) {
@@ -680,40 +683,44 @@ class PlaneFitPool {
         }
     };
     struct Lease {
-        PlaneFitPool &pool;
+        DeviceObjectPool &pool;
         Slot *slot;
         ~Lease() { std::lock_guard<std::mutex> lk(pool.mu); pool.idle.push_back(slot); }
     };
-    ~PlaneFitPool() {
+    DeviceObjectPool(const char *createName, Create create) : createName(createName), create(std::move(create)) {}
+    ~DeviceObjectPool() {
         for (auto &s : all) {
-            cart_planefit_destroy(s->pf);
+            Destroy(s->obj);
             if (s->dev) (void)hipFree(s->dev);
             if (s->host) (void)hipHostFree(s->host);
         }
     }
-    std::shared_ptr<EngineHandle> engineFor(const image_t &labels) {
-        std::lock_guard<std::mutex> lk(mu);
-        if (!engine) {
-            Size res; res.width = labels.cols; res.height = labels.rows;
-            engine = std::make_shared<EngineHandle>(res, paramsFor(res, 0, 0, -1, 0, 0, 10, 120, 12));
-        }
-        return engine;
-    }
-    Slot *acquire(const image_t &labels) {
-        auto eng = engineFor(labels);
+    std::shared_ptr<EngineHandle> engineFor(const image_t &image) { return postEngine(mu, engine, image); }
+    Slot *acquire(const image_t &image) {
+        auto eng = engineFor(image);
         std::lock_guard<std::mutex> lk(mu);
         if (!idle.empty()) { Slot *s = idle.back(); idle.pop_back(); return s; }
+        if (all.empty()) { res.width = image.cols; res.height = image.rows; }
         auto s = std::make_unique<Slot>();
-        if (cart_planefit_create(eng->get(), 16383, &s->pf) != 0) eng->fail("cart_planefit_create");
+        if (create(eng->get(), res, &s->obj) != 0) eng->fail(createName);
         all.push_back(std::move(s));
         return all.back().get();
     }
 
    private:
     std::mutex mu;
+    Size res;   // the first frame's: every object is made for it
     std::shared_ptr<EngineHandle> engine;
     std::vector<std::unique_ptr<Slot>> all;
     std::vector<Slot *> idle;
+    const char *const createName;
+    const Create create;
+};
+
+// ---------------------------------------------------------------- superpixel plane fit / cluster (planefit.cu:182-445, planecluster.cpp:19-177)
+class PlaneFitPool : public DeviceObjectPool<cart_planefit, cart_planefit_destroy> {
+   public:
+    PlaneFitPool() : DeviceObjectPool("cart_planefit_create", [](cart_engine *e, Size, cart_planefit **pf) { return cart_planefit_create(e, 16383, pf); }) {}
 };
 
 namespace {
@@ -763,10 +770,10 @@ system_data_t SuperPixelPlaneFitModule::runInternal(System &, SystemRunData &dat
     uint64_t *assignDev = reinterpret_cast<uint64_t *>(planesDev + CART_PLANEFIT_MAX_PLANES * 4);
     int32_t *nDev = reinterpret_cast<int32_t *>(assignDev + L1);
     ScopedStream stream;
-    if (cart_planefit_label_planes(sl.pf, in.labels->ptr<uint16_t>(), in.labels->step, (int)in.maxLabel, in.depth->ptr<float>(), in.depth->step,
+    if (cart_planefit_label_planes(sl.obj, in.labels->ptr<uint16_t>(), in.labels->step, (int)in.maxLabel, in.depth->ptr<float>(), in.depth->step,
                                    CART_PLANE_PREDICATE_PLANEFIT, CART_PLANEFIT_THRESHOLD, seed, data.id, labelPlanesDev, nullptr, nullptr, stream.s) != 0)
         eng->fail("cart_planefit_label_planes");
-    if (cart_planefit_fit(sl.pf, in.labels->ptr<uint16_t>(), in.labels->step, seed, data.id, planesDev, assignDev, nDev, nullptr, stream.s) != 0)
+    if (cart_planefit_fit(sl.obj, in.labels->ptr<uint16_t>(), in.labels->step, seed, data.id, planesDev, assignDev, nDev, nullptr, stream.s) != 0)
         eng->fail("cart_planefit_fit");
     hipCheck(hipMemcpyAsync(sl.host, sl.dev, bytes, hipMemcpyDeviceToHost, stream.s), "hipMemcpyAsync of the planefit outputs");
     stream.wait();   // the frame's only blocking synchronisation
@@ -805,10 +812,10 @@ system_data_t SuperPixelPlaneClusterModule::runInternal(System &, SystemRunData 
     int32_t *offDev = reinterpret_cast<int32_t *>(planesDev + L1 * 4);
     int32_t *nbDev = offDev + L1 + 1;
     ScopedStream stream;
-    if (cart_planefit_label_planes(sl.pf, in.labels->ptr<uint16_t>(), in.labels->step, (int)in.maxLabel, in.depth->ptr<float>(), in.depth->step,
+    if (cart_planefit_label_planes(sl.obj, in.labels->ptr<uint16_t>(), in.labels->step, (int)in.maxLabel, in.depth->ptr<float>(), in.depth->step,
                                    CART_PLANE_PREDICATE_PLANECLUSTER, CART_PLANEFIT_THRESHOLD, seed, data.id, planesDev, nullptr, nullptr, stream.s) != 0)
         eng->fail("cart_planefit_label_planes");
-    if (cart_planefit_adjacency(sl.pf, in.labels->ptr<uint16_t>(), in.labels->step, (int)in.maxLabel, offDev, nbDev, cap, stream.s) != 0)
+    if (cart_planefit_adjacency(sl.obj, in.labels->ptr<uint16_t>(), in.labels->step, (int)in.maxLabel, offDev, nbDev, cap, stream.s) != 0)
         eng->fail("cart_planefit_adjacency");
     hipCheck(hipMemcpyAsync(sl.host, sl.dev, head, hipMemcpyDeviceToHost, stream.s), "hipMemcpyAsync of the plane tables");
     stream.wait();
@@ -821,7 +828,7 @@ system_data_t SuperPixelPlaneClusterModule::runInternal(System &, SystemRunData 
         stream.wait();
     }
     int bad = 0;
-    if (cart_planefit_status(sl.pf, &bad) != 0) eng->fail("cart_planefit_status");
+    if (cart_planefit_status(sl.obj, &bad) != 0) eng->fail("cart_planefit_status");
     if (bad) throw std::runtime_error("superpixel label above superpixels_max_label");
     std::vector<double> planesOut(L1 * 4);
     std::vector<uint64_t> assign(L1);
@@ -844,56 +851,16 @@ double SuperPixelPlaneClusterModule::meanMergeMs() const {
     return n ? 1e-6 * (double)mergeNs.load() / (double)n : 0.0;
 }
 // ---------------------------------------------------------------- ORB features (features.cpp:10-66)
-// The engine and the cart_orb workspaces are made for the first frame's image size and kept; a free slot is leased per
-// frame.  Every slot owns its device keypoint / count buffer and the pinned host buffer of the download (no allocation or
-// free inside a frame; the descriptors are the frame's own output images, like every other module's outputs).
-class OrbPool {
+// A slot's device buffer holds the frame's counts and keypoints, downloaded through its pinned buffer; the descriptors are the
+// frame's own output images, like every other module's outputs.
+class OrbPool : public DeviceObjectPool<cart_orb, cart_orb_destroy> {
    public:
-    struct Slot {
-        cart_orb *orb = nullptr;
-        void *dev = nullptr, *host = nullptr;   // counts [2] int32 + 8 B padding | keypoints [2][nfeatures]
-    };
-    struct Lease {
-        OrbPool &pool;
-        Slot *slot;
-        ~Lease() { std::lock_guard<std::mutex> lk(pool.mu); pool.idle.push_back(slot); }
-    };
-    explicit OrbPool(int nfeatures) : nfeatures(nfeatures) {}
-    ~OrbPool() {
-        for (auto &s : all) {
-            cart_orb_destroy(s->orb);
-            if (s->dev) (void)hipFree(s->dev);
-            if (s->host) (void)hipHostFree(s->host);
-        }
-    }
-    size_t bytes() const { return 16 + 2 * (size_t)nfeatures * sizeof(KeyPoint); }
-    std::shared_ptr<EngineHandle> engineFor(const image_t &image) {
-        std::lock_guard<std::mutex> lk(mu);
-        if (!engine) {
-            res.width = image.cols; res.height = image.rows;
-            engine = std::make_shared<EngineHandle>(res, paramsFor(res, 0, 0, -1, 0, 0, 10, 120, 12));
-        }
-        return engine;
-    }
-    Slot *acquire(const image_t &image) {
-        auto eng = engineFor(image);
-        std::lock_guard<std::mutex> lk(mu);
-        if (!idle.empty()) { Slot *s = idle.back(); idle.pop_back(); return s; }
-        auto s = std::make_unique<Slot>();
-        if (cart_orb_create(eng->get(), res.width, res.height, nfeatures, &s->orb) != 0) eng->fail("cart_orb_create");
-        hipCheck(hipMalloc(&s->dev, bytes()), "hipMalloc");
-        hipCheck(hipHostMalloc(&s->host, bytes(), hipHostMallocDefault), "hipHostMalloc");
-        all.push_back(std::move(s));
-        return all.back().get();
-    }
+    explicit OrbPool(int nfeatures)
+        : DeviceObjectPool("cart_orb_create",
+                           [nfeatures](cart_engine *e, Size res, cart_orb **o) { return cart_orb_create(e, res.width, res.height, nfeatures, o); }),
+          nfeatures(nfeatures) {}
+    size_t bytes() const { return 16 + 2 * (size_t)nfeatures * sizeof(KeyPoint); }   // counts [2] int32 + 8 B padding | keypoints [2][nfeatures]
     const int nfeatures;
-
-   private:
-    std::mutex mu;
-    Size res;
-    std::shared_ptr<EngineHandle> engine;
-    std::vector<std::unique_ptr<Slot>> all;
-    std::vector<Slot *> idle;
 };
 
 std::pair<ImageFeatures, ImageFeatures> detectOrbFeatures(OrbPool &pool, const image_t &left, const image_t &right) {
@@ -903,6 +870,7 @@ std::pair<ImageFeatures, ImageFeatures> detectOrbFeatures(OrbPool &pool, const i
     auto eng = pool.engineFor(left);
     OrbPool::Lease lease{pool, pool.acquire(left)};
     OrbPool::Slot &sl = *lease.slot;
+    sl.reserve(pool.bytes(), pool.bytes());
     const int n = pool.nfeatures;
     image_t desc[2] = {image_t(n, CART_ORB_DESCRIPTOR_BYTES, CV_8UC1), image_t(n, CART_ORB_DESCRIPTOR_BYTES, CV_8UC1)};
     int32_t *countsDev = static_cast<int32_t *>(sl.dev);
@@ -912,7 +880,7 @@ std::pair<ImageFeatures, ImageFeatures> detectOrbFeatures(OrbPool &pool, const i
     cart_keypoint *kps[2] = {kpDev, kpDev + n};
     uint8_t *descs[2] = {desc[0].ptr<uint8_t>(), desc[1].ptr<uint8_t>()};
     ScopedStream stream;
-    if (cart_orb_detect(sl.orb, 2, images, steps, channels, left.cols, left.rows, kps, descs, descSteps, countsDev, stream.s) != 0)
+    if (cart_orb_detect(sl.obj, 2, images, steps, channels, left.cols, left.rows, kps, descs, descSteps, countsDev, stream.s) != 0)
         eng->fail("cart_orb_detect");
     hipCheck(hipMemcpyAsync(sl.host, sl.dev, pool.bytes(), hipMemcpyDeviceToHost, stream.s), "hipMemcpyAsync of the keypoints");
     stream.wait();   // the frame's only blocking synchronisation (the reference's orb->convert)

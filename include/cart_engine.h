@@ -306,6 +306,7 @@ typedef struct cart_superpixels cart_superpixels;
  * label = (y / block_h) * ceil(w / block_w) + x / block_w, max_label_id = #blocks (must be < 16384). */
 int cart_superpixels_create(cart_engine *engine, const cart_superpixel_params *params, int block_w, int block_h,
                             cart_superpixels **out);
+/* Keeps the device and image size it was created with, so it may be destroyed after its engine (as the plane schedule may). */
 void cart_superpixels_destroy(cart_superpixels *sp);
 /* Re-runs the block initialisation (the reset every `reset_iterations` frames, superpixels.cu:104-112). */
 int cart_superpixels_reset(cart_superpixels *sp, void *stream);
@@ -359,6 +360,7 @@ enum { CART_PLANE_PREDICATE_PLANEFIT = 0,       /* isfinite(z) && z <= 40 && z >
 typedef struct cart_planefit cart_planefit;
 /* Workspaces for labels 0..max_label_capacity (<= 16383, cart_superpixels' limit) at the engine's image size. */
 int cart_planefit_create(cart_engine *engine, int max_label_capacity, cart_planefit **out);
+/* Keeps the device and image size it was created with, so it may be destroyed after its engine (as the plane schedule may). */
 void cart_planefit_destroy(cart_planefit *pf);
 /* S17 for every label 0..max_label (replaces planefit.cu:366-384 + plane.cpp:102-180, planecluster.cpp:31-67).  labels =
  * CV_16UC1, xyz = CV_32FC3 "depth" (device, steps in bytes).  Keeps the per-label statistics, point lists and planes in the
@@ -418,6 +420,7 @@ typedef struct cart_orb cart_orb;
 /* Workspaces (pyramids, candidate lists, counters, the steered pattern) for two images up to max_width x max_height and
  * nfeatures in [1, 65536]; nothing is allocated per call.  Works on an engine of any disparity setting (0 / 0 included). */
 int cart_orb_create(cart_engine *engine, int max_width, int max_height, int nfeatures, cart_orb **out);
+/* Keeps the device and image size it was created with, so it may be destroyed after its engine (as the plane schedule may). */
 void cart_orb_destroy(cart_orb *orb);
 /* Host only, no GPU (features.cpp's orb object's level layout): level sizes and quotas of all 8 levels into the arrays
  * (each CART_ORB_LEVELS long, any may be NULL).  Returns the number of levels built (0..8), or -1 on bad arguments. */
