@@ -1,123 +1,24 @@
-// cart_engine.hip -- C-ABI implementation (include/cart_engine.h): workspace pool, stage
-// sequencing and the host-side peak finder.  No exceptions cross the ABI and nothing exits.
-#include <algorithm>
+// cart_engine.hip -- C-ABI implementation (include/cart_engine.h): the engine itself -- creation, options, the slot and slab
+// pools, the placement tuner, stage timing, the disparity entry points and the debug reads.  The later stages and the device
+// objects live in engine_*.hip.  No exceptions cross the ABI and nothing exits.
 #include <chrono>
-#include <cmath>
-#include <condition_variable>
 #include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <mutex>
-#include <new>
-#include <set>
-#include <string>
-#include <vector>
 
-#include "engine_internal.h"
+#include "engine_host.h"
 
 using namespace cart_amd;
 
-namespace {
+namespace cart_amd {
 
 thread_local std::string g_last_error;
-thread_local int g_last_slot = 0;  // first slot of this thread's most recent compute lease
+thread_local int g_last_slot = 0;
 
 int fail(const std::string &msg) {
     g_last_error = msg;
     return -1;
 }
 
-#define HIP_TRY(expr)                                                                               \
-    do {                                                                                            \
-        hipError_t _e = (expr);                                                                     \
-        if (_e != hipSuccess)                                                                       \
-            return fail(std::string(#expr) + ": " + hipGetErrorString(_e) + " (" + __FILE__ + ":" + \
-                        std::to_string(__LINE__) + ")");                                           \
-    } while (0)
-
-struct Slot {
-    bool busy = false;
-    hipEvent_t done = nullptr;          // recorded only on the FIRST slot of a lease ...
-    int owner = -1;                     // ... every slot of the lease points at that slot
-    hipStream_t last_stream = nullptr;
-    bool used = false;
-    unsigned long long released_seq = 0;  // order of the last release (guarded by mu)
-};
-
-constexpr int kMaxTimings = 8;
-constexpr int kTimingRing = 256;
-
-struct TimingRec {
-    hipEvent_t ev[kMaxTimings + 1] = {};
-    const char *names[kMaxTimings] = {};
-    int n = 0;
-};
-
-}  // namespace
-
-// The slab workspace: one plain hipMalloc per GROUP of workspace slots, no group larger than kSlabChunkBytes (see slab_pool_alloc).
-// Slot s lives at base[s / group_slots] + (s % group_slots) * slot_bytes; the kernels of a launch get the slab pointers of their
-// frames as a table (SlabTable), so a launch may span groups.
-static_assert(kMaxLaunchFrames == 64, "cart_engine_set_option(CART_OPT_CHUNK_FRAMES) documents 1..64");
-struct SlabPool {
-    std::vector<uint8_t *> base;   // one device allocation per group
-    int group_slots = 0;           // slots per group (the last group may hold fewer)
-    int slots = 0;
-    size_t slot_bytes = 0;         // P path slabs of one frame
-    int groups() const { return (int)base.size(); }
-    int slots_of(int gi) const { return std::min(group_slots, slots - gi * group_slots); }
-    size_t bytes_of(int gi) const { return (size_t)slots_of(gi) * slot_bytes; }
-    uint8_t *slot_ptr(int s) const { return base[s / group_slots] + (size_t)(s % group_slots) * slot_bytes; }
-};
-
-struct cart_engine {
-    cart_engine_params params;
-    Geometry g;
-    float uniq;
-    uint16_t *uniq_thr = nullptr;   // device: integer uniqueness threshold of every best cost 0..2047 for this engine's ratio (WTA kernels)
-    // workspaces, each [max_inflight][...]
-    uint8_t *gray_l = nullptr, *gray_r = nullptr;
-    uint32_t *cen_l = nullptr, *cen_r = nullptr;      // point `cen_slack` elements into their allocations
-    uint32_t *cen_l_alloc = nullptr, *cen_r_alloc = nullptr;
-    size_t cen_slack = 0;
-    uint16_t *wta_l = nullptr;
-    uint32_t *right_pk = nullptr;
-    int16_t *tmp_a = nullptr, *tmp_b = nullptr;  // tight s16 planes (interpolate ping-pong)
-    int32_t *ccl_work = nullptr;
-    uint32_t *rv_partial = nullptr; // [max_inflight][wta_fused_partial_elems], allocated by the first fused batch
-    uint8_t *flow_ws = nullptr;     // [max_inflight][flow_ws_bytes]: gray x2, census x2, scratch; first cart_optical_flow allocates
-    int32_t *ccl_stats_ws = nullptr; // component-table workspace (ensure_ccl_stats_ws): [max_inflight][npx][5] scratch + [max_inflight][h][tile columns]; first table call allocates
-    unsigned *sp_votes = nullptr;   // [max_inflight][kSpMaxLabels*3], allocated by the first cart_superpixel_plane_classify
-    AggArgs agg;
-    AggArgs agg_fused;              // the same launch without the "up" direction (computed inside wta_fused_kernel)
-    SlabPool slab_pool;             // the cost slabs of every slot (slab_pool_alloc / slab_pool_free / cart_engine_tune_placement)
-    int auto_fused_min_frames = 1 << 30; // CART_OPT_PLAN = auto: launches of at least this many frames take the fused WTA
-    int opt_plan = CART_PLAN_AUTO;       // cart_engine_set_option
-    int opt_plan_min_frames = 1;         // with a forced plan: launches of fewer frames still take CART_PLAN_SLABS
-    int opt_spec = 0;                    // CART_OPT_SPEC_* bits: upstream variants of S8 / S7 (default: the oracle's spec)
-    std::mutex mu;
-    std::condition_variable cv;
-    std::vector<Slot> slots;
-    unsigned long long release_counter = 0;    // guarded by mu
-    int chunk_frames = kLaunchFrames;          // frames per launch sequence inside one batched call
-    bool post_only = false;         // no SGM workspaces (num_disparities == 0)
-    bool timing = false;
-    int timing_every = 1;           // stage events on every timing_every-th compute call (cart_engine_set_timing)
-    unsigned long long timing_calls = 0;   // compute calls seen while timing is on (guarded by mu)
-    std::vector<TimingRec> ring;  // stage events of the last kTimingRing compute calls (guarded by mu)
-    size_t ring_calls = 0;
-};
-
-namespace {
-
-struct Lease {
-    cart_engine *e;
-    int s0, n;
-    hipStream_t stream;
-};
-
-// Leases `n` contiguous slots; makes `stream` wait for earlier work on them from other streams.
-int acquire(cart_engine *e, int n, hipStream_t stream, Lease *out) {
+int SlotLease::begin(cart_engine *e, int n, hipStream_t stream) {
     if (n <= 0 || n > (int)e->slots.size()) return fail("n_frames must be in [1, max_inflight]");
     std::unique_lock<std::mutex> lk(e->mu);
     int s0 = -1;
@@ -166,26 +67,43 @@ int acquire(cart_engine *e, int n, hipStream_t stream, Lease *out) {
             waited = s.owner;
         }
     }
-    out->e = e; out->s0 = s0; out->n = n; out->stream = stream;
+    this->e = e; this->s0 = s0; this->n = n; this->stream = stream;
     return 0;
 }
 
-void release(const Lease &l) {
-    cart_engine *e = l.e;
-    (void)hipEventRecord(e->slots[l.s0].done, l.stream);  // ONE in-queue marker per lease (16 of them cost ~80 us of GPU idle)
-    for (int k = 0; k < l.n; ++k) {
-        Slot &s = e->slots[l.s0 + k];
-        s.owner = l.s0;
-        s.last_stream = l.stream;
+SlotLease::~SlotLease() {
+    if (!e) return;
+    (void)hipEventRecord(e->slots[s0].done, stream);  // ONE in-queue marker per lease (16 of them cost ~80 us of GPU idle)
+    for (int k = 0; k < n; ++k) {
+        Slot &s = e->slots[s0 + k];
+        s.owner = s0;
+        s.last_stream = stream;
         s.used = true;
     }
     {
         std::lock_guard<std::mutex> lk(e->mu);
         const unsigned long long seq = ++e->release_counter;
-        for (int k = 0; k < l.n; ++k) { e->slots[l.s0 + k].busy = false; e->slots[l.s0 + k].released_seq = seq; }
+        for (int k = 0; k < n; ++k) { e->slots[s0 + k].busy = false; e->slots[s0 + k].released_seq = seq; }
     }
     e->cv.notify_all();
 }
+
+int ensure_ws_locked(cart_engine *e, void **ws, size_t bytes_per_slot, bool zero) {
+    if (*ws) return 0;
+    const size_t bytes = e->slots.size() * bytes_per_slot;
+    void *p = nullptr;
+    HIP_TRY(hipMalloc(&p, bytes));
+    if (zero && (hipMemset(p, 0, bytes) != hipSuccess || hipDeviceSynchronize() != hipSuccess)) { (void)hipFree(p); return fail("hipMemset of the component-table workspace failed"); }
+    e->bufs.push_back(p);
+    *ws = p;
+    return 0;
+}
+
+}  // namespace cart_amd
+
+static_assert(kMaxLaunchFrames == 64, "cart_engine_set_option(CART_OPT_CHUNK_FRAMES) documents 1..64");
+
+namespace {
 
 void build_agg_args(cart_engine *e, AggArgs &a, unsigned keep) {
     const Geometry &g = e->g;
@@ -250,6 +168,17 @@ int dev_alloc(T **p, size_t count) {
     return 0;
 }
 
+template <typename T>
+int engine_alloc(cart_engine *e, T **p, size_t count) {   // a workspace of the engine's lifetime: recorded in e->bufs
+    if (dev_alloc(p, count)) return -1;
+    e->bufs.push_back(*p);
+    return 0;
+}
+
+int ensure_rv_partial(cart_engine *e) {   // the fused WTA's right-view partials; the caller holds e->mu
+    return ensure_ws_locked(e, reinterpret_cast<void **>(&e->rv_partial), wta_fused_partial_elems(e->g) * sizeof(uint32_t), false);
+}
+
 // The slab workspace.  Measured on MI355X (profiles/r03_alloc.txt): the aggregation launch writes its slabs 8-9 % faster into a device
 // allocation of at most 8 GiB than into a larger one (1.41-1.43 against 1.53-1.55 ms per 16 pairs at 1242x375 D=128 P=8; the L2's write
 // requests to the fabric stall 20-30x as often in the larger one; TLB counters and clock are the same) -- whatever the physical layout
@@ -311,68 +240,21 @@ SlabTable slab_table(const SlabPool &sp, int s0, int n, const std::vector<uint8_
     return t;
 }
 
-// The lifecycle of the stateful device objects (cart_superpixels, cart_planefit, cart_orb).  An object keeps the device and
-// geometry of the engine it was made on, not the engine, so that it may be destroyed after its engine.  Calls on one object are
-// serialised by `mu` (superpixels.cu:97-99); a call that arrives on another stream than the previous one first waits for
-// `done`, which every call records on its stream (ObjectCall).
-struct DeviceObject {
-    int device_id;
-    Geometry g;
-    std::mutex mu;
-    hipEvent_t done = nullptr;
-    hipStream_t last_stream = nullptr;
-    bool used = false;
-    std::vector<void *> bufs;   // every device allocation, freed by destroy_object
-
-    explicit DeviceObject(const cart_engine *e) : device_id(e->params.device_id), g(e->g) {}
-    // hipMalloc recorded in bufs; a zero-byte request gets a small real buffer (hipMalloc would hand back no pointer)
-    template <typename T>
-    int alloc(T **p, size_t bytes) {
-        HIP_TRY(hipMalloc(reinterpret_cast<void **>(p), bytes ? bytes : 256));
-        bufs.push_back(*p);
-        return 0;
-    }
-    int create_event() {
-        HIP_TRY(hipEventCreateWithFlags(&done, hipEventDisableTiming));
-        return 0;
-    }
-};
-
-// One entry point's hold on an object: begin() makes the object's device current, takes its lock and orders the call after
-// the previous one if that came on another stream; once begin() has succeeded, every way out of the call, early error
-// returns included, records `done` on the call's stream.
-class ObjectCall {
-   public:
-    ObjectCall(DeviceObject &o, hipStream_t stream) : o(o), stream(stream) {}
-    int begin() {
-        HIP_TRY(hipSetDevice(o.device_id));
-        lk = std::unique_lock<std::mutex>(o.mu);
-        if (o.used && o.last_stream != stream) HIP_TRY(hipStreamWaitEvent(stream, o.done, 0));
-        entered = true;
-        return 0;
-    }
-    ~ObjectCall() {
-        if (!entered) return;
-        (void)hipEventRecord(o.done, stream);
-        o.last_stream = stream;
-        o.used = true;
-    }
-
-   private:
-    DeviceObject &o;
-    hipStream_t stream;
-    std::unique_lock<std::mutex> lk;   // released after the record above
-    bool entered = false;
-};
-
-template <typename T>
-void destroy_object(T *o) {
-    if (!o) return;
-    (void)hipSetDevice(o->device_id);   // the caller's current device may be another one
-    (void)hipDeviceSynchronize();
-    for (void *b : o->bufs) (void)hipFree(b);
-    if (o->done) (void)hipEventDestroy(o->done);
-    delete o;
+// The aggregation + WTA launches of `n` frames at slots [s0, s0 + n) with their slabs at `slabs`, on stream `st`: what a compute
+// call runs between its census and post stages, and what the placement probe times.  `between` runs between the two launches.
+template <typename F>
+void launch_agg_wta(cart_engine *e, const Options &opt, const SlabTable &slabs, size_t s0, int n, hipStream_t st, F between) {
+    const Geometry &g = e->g;
+    uint32_t *cl = e->cen_l + s0 * g.census_elems, *cr = e->cen_r + s0 * g.census_elems;
+    uint16_t *wl = e->wta_l + s0 * g.npx;
+    uint32_t *rpk = e->right_pk + s0 * g.npx;
+    const bool fused = plan_for(e, opt, n) == CART_PLAN_FUSED_UP && e->rv_partial;
+    AggArgs a = fused ? e->agg_fused : e->agg;
+    a.cen_l = cl; a.cen_r = cr; a.slabs = slabs;
+    launch_aggregate(a, n, st);
+    between();
+    if (fused) launch_wta_fused(cl, cr, slabs, wl, rpk, e->rv_partial + s0 * wta_fused_partial_elems(g), g, e->uniq_thr, n, st);
+    else launch_wta(slabs, wl, rpk, g, e->uniq_thr, n, st, (opt.spec & 4) != 0);
 }
 
 }  // namespace
@@ -415,38 +297,29 @@ int cart_engine_create(const cart_engine_params *params, cart_engine **out) {
     e->uniq = (float)(100 - params->uniqueness_ratio) / 100.0f;  // oracle S5
     const size_t n = (size_t)params->max_inflight;
     int rc = 0;
-    e->post_only = g.D == 0;
-    if (e->post_only) {  // geometry-only engine: interpolate ping-pong and CCL links are all the post stages need
-        rc |= dev_alloc(&e->tmp_a, n * g.npx);
-        rc |= dev_alloc(&e->tmp_b, n * g.npx);
-        rc |= dev_alloc(&e->ccl_work, n * g.npx);
-        if (rc) { cart_engine_destroy(e); return -1; }
-        e->slots.resize(n);
-        for (auto &s : e->slots)
-            if (hipEventCreateWithFlags(&s.done, hipEventDisableTiming) != hipSuccess) { cart_engine_destroy(e); return fail("hipEventCreate failed"); }
-        *out = e;
-        return 0;
+    e->post_only = g.D == 0;   // geometry-only engine: interpolate ping-pong and CCL links are all the post stages need
+    if (!e->post_only) {
+        rc |= engine_alloc(e, &e->gray_l, n * g.npx);
+        rc |= engine_alloc(e, &e->gray_r, n * g.npx);
+        // the cooperative window loads of waves whose leading scan lines are still outside the image touch
+        // addresses up to (h + D + min_disp + 64) features before / after a frame's census plane
+        // and the software-pipelined prefetches run up to 3 rows past the first / last step
+        e->cen_slack = (size_t)4 * g.cpitch + g.h + 1024;
+        rc |= engine_alloc(e, &e->cen_l_alloc, n * g.census_elems + 2 * e->cen_slack);
+        rc |= engine_alloc(e, &e->cen_r_alloc, n * g.census_elems + 2 * e->cen_slack);
+        rc |= slab_pool_alloc(e->slab_pool, (size_t)g.P * g.slab_bytes, (int)n);
+        rc |= engine_alloc(e, &e->wta_l, n * g.npx);
+        rc |= engine_alloc(e, &e->right_pk, n * g.npx);
     }
-    rc |= dev_alloc(&e->gray_l, n * g.npx);
-    rc |= dev_alloc(&e->gray_r, n * g.npx);
-    // the cooperative window loads of waves whose leading scan lines are still outside the image touch
-    // addresses up to (h + D + min_disp + 64) features before / after a frame's census plane
-    // and the software-pipelined prefetches run up to 3 rows past the first / last step
-    e->cen_slack = (size_t)4 * g.cpitch + g.h + 1024;
-    rc |= dev_alloc(&e->cen_l_alloc, n * g.census_elems + 2 * e->cen_slack);
-    rc |= dev_alloc(&e->cen_r_alloc, n * g.census_elems + 2 * e->cen_slack);
-    rc |= slab_pool_alloc(e->slab_pool, (size_t)g.P * g.slab_bytes, (int)n);
-    rc |= dev_alloc(&e->wta_l, n * g.npx);
-    rc |= dev_alloc(&e->right_pk, n * g.npx);
-    rc |= dev_alloc(&e->tmp_a, n * g.npx);
-    rc |= dev_alloc(&e->tmp_b, n * g.npx);
-    rc |= dev_alloc(&e->ccl_work, n * g.npx);
+    rc |= engine_alloc(e, &e->tmp_a, n * g.npx);
+    rc |= engine_alloc(e, &e->tmp_b, n * g.npx);
+    rc |= engine_alloc(e, &e->ccl_work, n * g.npx);
     if (rc) { cart_engine_destroy(e); return -1; }
     e->cen_l = e->cen_l_alloc + e->cen_slack;
     e->cen_r = e->cen_r_alloc + e->cen_slack;
     // the census padding columns are never written again: out-of-image right features read as 0 (oracle S3)
-    if (hipMemset(e->cen_l_alloc, 0, (n * g.census_elems + 2 * e->cen_slack) * 4) != hipSuccess ||
-        hipMemset(e->cen_r_alloc, 0, (n * g.census_elems + 2 * e->cen_slack) * 4) != hipSuccess) {
+    if (!e->post_only && (hipMemset(e->cen_l_alloc, 0, (n * g.census_elems + 2 * e->cen_slack) * 4) != hipSuccess ||
+                          hipMemset(e->cen_r_alloc, 0, (n * g.census_elems + 2 * e->cen_slack) * 4) != hipSuccess)) {
         cart_engine_destroy(e);
         return fail("hipMemset of census workspace failed");
     }
@@ -456,8 +329,9 @@ int cart_engine_create(const cart_engine_params *params, cart_engine **out) {
             cart_engine_destroy(e);
             return fail("hipEventCreate failed");
         }
+    if (e->post_only) { *out = e; return 0; }
     // the WTA kernels' uniqueness test as a table: uniq_threshold() evaluated once per cost by the device function itself
-    if (dev_alloc(&e->uniq_thr, 2048)) { cart_engine_destroy(e); return -1; }
+    if (engine_alloc(e, &e->uniq_thr, 2048)) { cart_engine_destroy(e); return -1; }
     launch_uniq_table(e->uniq, e->uniq_thr, nullptr);
     if (hipGetLastError() != hipSuccess || hipStreamSynchronize(nullptr) != hipSuccess) { cart_engine_destroy(e); return fail("building the uniqueness table failed"); }
     build_agg_args(e, e->agg, 0xffu);
@@ -480,9 +354,7 @@ void cart_engine_destroy(cart_engine *e) {
     (void)hipSetDevice(e->params.device_id);   // the caller's current device may be another one
     (void)hipDeviceSynchronize();
     slab_pool_free(e->slab_pool);
-    void *bufs[] = {e->gray_l, e->gray_r, e->cen_l_alloc, e->cen_r_alloc, e->wta_l, e->right_pk, e->tmp_a, e->tmp_b, e->ccl_work, e->sp_votes, e->rv_partial, e->flow_ws, e->ccl_stats_ws, e->uniq_thr};
-    for (void *b : bufs)
-        if (b) (void)hipFree(b);
+    for (void *b : e->bufs) (void)hipFree(b);
     for (auto &s : e->slots) {
         if (s.done) (void)hipEventDestroy(s.done);
     }
@@ -560,19 +432,12 @@ namespace {
 float probe_placement(cart_engine *e, const Options &opt, const SlabTable &slabs, size_t s0, int n, hipEvent_t ev0, hipEvent_t ev1) {
     const Geometry &g = e->g;
     if (!slabs.frame[0]) return -1.f;   // slot range outside the pool (slab_table)
-    uint32_t *cl = e->cen_l + s0 * g.census_elems, *cr = e->cen_r + s0 * g.census_elems;
-    uint16_t *wl = e->wta_l + s0 * g.npx;
     uint32_t *rpk = e->right_pk + s0 * g.npx;
-    const bool fused = plan_for(e, opt, n) == CART_PLAN_FUSED_UP && e->rv_partial;
     float best = -1.f;
     for (int rep = 0; rep < 4; ++rep) {   // one warm-up (first touch of a fresh allocation), three timed: the fastest counts
         if (hipMemsetAsync(rpk, 0xff, (size_t)n * g.npx * sizeof(uint32_t), nullptr) != hipSuccess) return -1.f;   // what launch_census leaves there
         if (hipEventRecord(ev0, nullptr) != hipSuccess) return -1.f;
-        AggArgs a = fused ? e->agg_fused : e->agg;
-        a.cen_l = cl; a.cen_r = cr; a.slabs = slabs;
-        launch_aggregate(a, n, nullptr);
-        if (fused) launch_wta_fused(cl, cr, slabs, wl, rpk, e->rv_partial + s0 * wta_fused_partial_elems(g), g, e->uniq_thr, n, nullptr);
-        else launch_wta(slabs, wl, rpk, g, e->uniq_thr, n, nullptr, false);
+        launch_agg_wta(e, opt, slabs, s0, n, nullptr, [] {});
         if (hipEventRecord(ev1, nullptr) != hipSuccess || hipEventSynchronize(ev1) != hipSuccess || hipGetLastError() != hipSuccess) return -1.f;
         float ms = 0.f;
         if (hipEventElapsedTime(&ms, ev0, ev1) != hipSuccess) return -1.f;
@@ -594,14 +459,13 @@ int cart_engine_tune_placement(cart_engine *e, int n_frames, int max_tries, size
     const Options opt = snapshot_options(e);
     HIP_TRY(hipDeviceSynchronize());
     const int n = std::min(n_frames, opt.chunk_frames);
-    if (plan_for(e, opt, n) == CART_PLAN_FUSED_UP && !e->rv_partial)
-        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&e->rv_partial), e->slots.size() * wta_fused_partial_elems(e->g) * sizeof(uint32_t)));
+    if (plan_for(e, opt, n) == CART_PLAN_FUSED_UP && ensure_rv_partial(e)) return -1;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     HIP_TRY(hipEventCreate(&ev0));
     if (hipEventCreate(&ev1) != hipSuccess) { (void)hipEventDestroy(ev0); return fail("hipEventCreate failed"); }
     SlabPool &sp = e->slab_pool;
     // The search runs per UNIT = the groups behind the slots [k n, (k + 1) n) of one n-frame call, for the first (at most four) such
-    // ranges: a lease takes the lowest free range its stream used last (acquire), so a caller with one call in flight lives in unit 0
+    // ranges: a lease takes the lowest free range its stream used last (SlotLease::begin), so a caller with one call in flight lives in unit 0
     // and one with several walks up the units.  A group already settled by an earlier unit is not touched again.  A group that holds
     // more slots than the launch has frames (32-slot groups, 16-frame launches) is scored on the slots of its first launch only.
     const int units = std::max(1, std::min(4, (int)e->slots.size() / n));
@@ -749,15 +613,6 @@ int cart_engine_collect_timing(cart_engine *e, const char **names, float *mean_m
     return n;
 }
 
-#define STAGE(name)                                                        \
-    do {                                                                   \
-        if (rec && nt < kMaxTimings) {                                     \
-            (void)hipEventRecord(rec->ev[nt], stream);                     \
-            rec->names[nt] = name;                                         \
-            ++nt;                                                          \
-        }                                                                  \
-    } while (0)
-
 namespace {
 // Where the frames of one call live: a base + stride per image (the batch entry point) or one pointer per frame (multi).
 struct FrameSet {
@@ -793,12 +648,11 @@ int compute_disparity_impl(cart_engine *e, int n_frames, const FrameSet &fr, int
     {
         std::lock_guard<std::mutex> lk(e->mu);
         opt = snapshot_options(e);
-        const int launch_plan = plan_for(e, opt, std::min(n_frames, opt.chunk_frames));   // later (shorter) launches of the call never need more
-        if (launch_plan == CART_PLAN_FUSED_UP && !e->rv_partial)
-            HIP_TRY(hipMalloc(reinterpret_cast<void **>(&e->rv_partial), e->slots.size() * wta_fused_partial_elems(g) * sizeof(uint32_t)));
+        // later (shorter) launches of the call never need more
+        if (plan_for(e, opt, std::min(n_frames, opt.chunk_frames)) == CART_PLAN_FUSED_UP && ensure_rv_partial(e)) return -1;
     }
-    Lease l;
-    if (acquire(e, n_frames, stream, &l)) return -1;
+    SlotLease l;
+    if (l.begin(e, n_frames, stream)) return -1;
     g_last_slot = l.s0;
     TimingRec *rec = nullptr;
     if (opt.timing) {
@@ -806,6 +660,11 @@ int compute_disparity_impl(cart_engine *e, int n_frames, const FrameSet &fr, int
         if (!e->ring.empty() && e->timing_calls++ % (unsigned long long)e->timing_every == 0) { rec = &e->ring[e->ring_calls++ % kTimingRing]; rec->n = 0; }
     }
     int nt = 0;
+    auto stage = [&](const char *name, hipStream_t st) {   // a stage of this call begins on `st`
+        if (!rec || nt >= kMaxTimings) return;
+        (void)hipEventRecord(rec->ev[nt], st);
+        rec->names[nt++] = name;
+    };
     const int radius = e->params.smoothing_radius, iters = e->params.smoothing_iterations;
     const bool smooth = radius > 0 && iters > 0;  // disparity.cu:73
     const size_t tight_step = (size_t)g.w * 2, tight_fs = g.npx * 2;
@@ -813,29 +672,21 @@ int compute_disparity_impl(cart_engine *e, int n_frames, const FrameSet &fr, int
     bool bad_slots = false;
     auto enqueue = [&](int f0, int n, hipStream_t st, bool timed) {
         const size_t s0 = (size_t)l.s0 + f0;
-        if (!slab_table(e->slab_pool, (int)s0, n).frame[0]) { bad_slots = true; return; }   // nothing is launched on a slot range the pool does not hold
+        const SlabTable slabs = slab_table(e->slab_pool, (int)s0, n);
+        if (!slabs.frame[0]) { bad_slots = true; return; }   // nothing is launched on a slot range the pool does not hold
         uint8_t *gl = e->gray_l + s0 * g.npx, *gr = e->gray_r + s0 * g.npx;
         uint32_t *cl = e->cen_l + s0 * g.census_elems, *cr = e->cen_r + s0 * g.census_elems;
-        const SlabTable slabs = slab_table(e->slab_pool, (int)s0, n);
         uint16_t *wl = e->wta_l + s0 * g.npx;
         uint32_t *rpk = e->right_pk + s0 * g.npx;
         int16_t *ta = e->tmp_a + s0 * g.npx, *tb = e->tmp_b + s0 * g.npx;
         const OutBatch o = fr.output(f0, n);
-        hipStream_t stream = st;  // STAGE records on the stream the kernels are launched on
         TimingRec *rec_save = rec;
         if (!timed) rec = nullptr;
-        STAGE("census");
+        stage("census", st);
         launch_census(fr.images(false, f0, n), fr.images(true, f0, n), channels, n, gl, gr, cl, cr, rpk, g, st);
-        const int launch_plan = plan_for(e, opt, n);
-        const bool fused = launch_plan == CART_PLAN_FUSED_UP && e->rv_partial;
-        STAGE("aggregate");
-        AggArgs a = fused ? e->agg_fused : e->agg;
-        a.cen_l = cl; a.cen_r = cr; a.slabs = slabs;
-        launch_aggregate(a, n, st);
-        STAGE("wta");
-        if (fused) launch_wta_fused(cl, cr, slabs, wl, rpk, e->rv_partial + s0 * wta_fused_partial_elems(g), g, e->uniq_thr, n, st);
-        else launch_wta(slabs, wl, rpk, g, e->uniq_thr, n, st, (opt.spec & 4) != 0);
-        STAGE("post");
+        stage("aggregate", st);
+        launch_agg_wta(e, opt, slabs, s0, n, st, [&] { stage("wta", st); });
+        stage("post", st);
         // disparity.hpp:27-28: minDisparity = cfg*16, maxDisparity = image width (not x16)
         const int min16 = e->params.min_disparity * 16, maxd = g.w;
         if (!smooth) {
@@ -849,7 +700,7 @@ int compute_disparity_impl(cart_engine *e, int n_frames, const FrameSet &fr, int
             } else {
                 launch_post(wl, rpk, gl, strided_out(ta, tight_step, tight_fs), g, n, st, opt.spec);
             }
-            if (it < iters) STAGE("interpolate");
+            if (it < iters) stage("interpolate", st);
             for (; it < iters; ++it) {
                 const bool last = it == iters - 1;
                 launch_interpolate(src, tight_step, tight_fs, last ? o : strided_out(dst, tight_step, tight_fs), g.w, g.h, radius, min16, maxd, n, st);
@@ -868,8 +719,7 @@ int compute_disparity_impl(cart_engine *e, int n_frames, const FrameSet &fr, int
     // slower per frame than 4 x 16).  Two-stream overlap of sub-batches was measured and buys nothing.
     const int chunk = fr.lefts ? std::min(opt.chunk_frames, kLaunchFrames) : opt.chunk_frames;  // pointer tables hold kLaunchFrames entries
     for (int f0 = 0; f0 < n_frames; f0 += chunk) enqueue(f0, std::min(chunk, n_frames - f0), stream, f0 == 0);
-    hipError_t err = hipGetLastError();
-    release(l);
+    const hipError_t err = hipGetLastError();
     if (bad_slots) return fail("internal error: a launch's slot range lies outside the slab pool");
     if (err != hipSuccess) return fail(std::string("kernel launch failed: ") + hipGetErrorString(err));
     return 0;
@@ -907,1055 +757,6 @@ int cart_compute_disparity(cart_engine *e, const uint8_t *left, size_t left_step
     return cart_compute_disparity_batch(e, 1, left, left_step, 0, right, right_step, 0, channels, out, out_step, 0, stream);
 }
 
-int cart_interpolate(cart_engine *e, int n_frames, int16_t *disp, size_t step, size_t frame_stride, int radius,
-                     int iterations, int min_disp16, int max_disp, void *stream_) {
-    if (!e) return fail("engine is NULL");
-    if (!disp) return fail("NULL image pointer");
-    if (radius <= 0 || iterations <= 0) return 0;
-    if (radius > 8) return fail("radius must be <= 8");
-    const Geometry &g = e->g;
-    if (step < (size_t)g.w * 2 || (step & 1) || (frame_stride & 1)) return fail("bad step");
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    HIP_TRY(hipSetDevice(e->params.device_id));
-    Lease l;
-    if (acquire(e, n_frames, stream, &l)) return -1;
-    int16_t *ta = e->tmp_a + (size_t)l.s0 * g.npx, *tb = e->tmp_b + (size_t)l.s0 * g.npx;
-    const size_t ts = (size_t)g.w * 2, tfs = g.npx * 2;
-    // pass 0 reads the caller's buffer, the last pass writes it; an extra tight copy keeps Jacobi semantics
-    launch_interpolate(disp, step, frame_stride, strided_out(ta, ts, tfs), g.w, g.h, radius, min_disp16, max_disp, n_frames, stream);
-    int16_t *src = ta, *dst = tb;
-    for (int it = 1; it < iterations; ++it) {
-        launch_interpolate(src, ts, tfs, strided_out(dst, ts, tfs), g.w, g.h, radius, min_disp16, max_disp, n_frames, stream);
-        std::swap(src, dst);
-    }
-    hipError_t err = hipSuccess;
-    for (int f = 0; f < n_frames && err == hipSuccess; ++f)
-        err = hipMemcpy2DAsync(reinterpret_cast<uint8_t *>(disp) + (size_t)f * frame_stride, step, src + (size_t)f * g.npx, ts, ts,
-                               g.h, hipMemcpyDeviceToDevice, stream);
-    if (err == hipSuccess) err = hipGetLastError();
-    release(l);
-    if (err != hipSuccess) return fail(std::string("interpolate failed: ") + hipGetErrorString(err));
-    return 0;
-}
-
-int cart_disparity_derivative(cart_engine *e, int n_frames, const int16_t *disp, size_t disp_step,
-                              size_t disp_frame_stride, int16_t *out, size_t out_step, size_t out_frame_stride,
-                              int32_t *hist512, void *stream_) {
-    if (!e) return fail("engine is NULL");
-    if (!disp || !out || !hist512) return fail("NULL pointer");
-    if (n_frames <= 0) return fail("n_frames must be positive");
-    const Geometry &g = e->g;
-    if (disp_step < (size_t)g.w * 2 || out_step < (size_t)g.w * 4 || (out_step & 3) || (out_frame_stride & 3) || (disp_step & 1) || (disp_frame_stride & 1))
-        return fail("bad step (derivative rows must be 4-byte aligned)");
-    HIP_TRY(hipSetDevice(e->params.device_id));
-    launch_dir_derivative(disp, disp_step, disp_frame_stride, out, out_step, out_frame_stride, hist512, g.w, g.h, n_frames,
-                          static_cast<hipStream_t>(stream_));
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-int cart_plane_derivative_hist(cart_engine *e, int n_frames, const int16_t *disp, size_t disp_step,
-                               size_t disp_frame_stride, int16_t *out, size_t out_step, size_t out_frame_stride,
-                               int32_t *hist256, size_t hist_frame_stride_elems, void *stream_) {
-    if (!e) return fail("engine is NULL");
-    if (!disp || !out || !hist256) return fail("NULL pointer");
-    if (n_frames <= 0) return fail("n_frames must be positive");
-    const Geometry &g = e->g;
-    if (disp_step < (size_t)g.w * 2 || out_step < (size_t)g.w * 2 || (disp_step & 1) || (out_step & 1) || (disp_frame_stride & 1) || (out_frame_stride & 1))
-        return fail("bad step");
-    HIP_TRY(hipSetDevice(e->params.device_id));
-    launch_plane_derivative(disp, disp_step, disp_frame_stride, out, out_step, out_frame_stride, hist256,
-                            hist_frame_stride_elems, g.w, g.h, n_frames, static_cast<hipStream_t>(stream_));
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-int cart_plane_classify(cart_engine *e, int n_frames, const int16_t *deriv, size_t deriv_step, size_t deriv_frame_stride,
-                        const cart_plane_params *params, int params_per_frame, uint8_t *planes, size_t planes_step,
-                        size_t planes_frame_stride, void *stream_) {
-    if (!e) return fail("engine is NULL");
-    if (!deriv || !planes || !params) return fail("NULL pointer");
-    if (n_frames <= 0) return fail("n_frames must be positive");
-    const Geometry &g = e->g;
-    if (deriv_step < (size_t)g.w * 2 || planes_step < (size_t)g.w || (deriv_step & 1) || (deriv_frame_stride & 1)) return fail("bad step");
-    HIP_TRY(hipSetDevice(e->params.device_id));
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    for (int f0 = 0; f0 < n_frames; f0 += kMaxBatchArgs) {
-        const int n = std::min(kMaxBatchArgs, n_frames - f0);
-        ClassifyParams cp;
-        if (params_per_frame) std::memcpy(cp.p, params + f0, sizeof(cart_plane_params) * (size_t)n);
-        else cp.p[0] = params[0];
-        launch_classify(reinterpret_cast<const int16_t *>(reinterpret_cast<const uint8_t *>(deriv) + (size_t)f0 * deriv_frame_stride),
-                        deriv_step, deriv_frame_stride, cp, params_per_frame, planes + (size_t)f0 * planes_frame_stride,
-                        planes_step, planes_frame_stride, g.w, g.h, n, stream);
-    }
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-int cart_plane_derivative_hist_multi(cart_engine *e, int n_frames, const int16_t *const *disp, size_t disp_step, int16_t *const *out,
-                                     size_t out_step, int32_t *hist256, size_t hist_frame_stride_elems, void *stream_) {
-    if (!e) return fail("engine is NULL");
-    if (!disp || !out || !hist256) return fail("NULL pointer");
-    if (n_frames <= 0) return fail("n_frames must be positive");
-    const Geometry &g = e->g;
-    if (disp_step < (size_t)g.w * 2 || out_step < (size_t)g.w * 2 || (disp_step & 1) || (out_step & 1)) return fail("bad step");
-    for (int f = 0; f < n_frames; ++f)
-        if (!disp[f] || !out[f]) return fail("NULL image pointer in a pointer table");
-    HIP_TRY(hipSetDevice(e->params.device_id));
-    for (int f0 = 0; f0 < n_frames; f0 += kLaunchFrames) {
-        const int n = std::min(kLaunchFrames, n_frames - f0);
-        FrameTable dt{}, ot{};
-        dt.scattered = ot.scattered = 1;
-        for (int f = 0; f < n; ++f) { dt.p[f] = disp[f0 + f]; ot.p[f] = out[f0 + f]; }
-        launch_plane_derivative(nullptr, disp_step, 0, nullptr, out_step, 0, hist256 + (size_t)f0 * hist_frame_stride_elems, hist_frame_stride_elems, g.w, g.h, n,
-                                static_cast<hipStream_t>(stream_), &dt, &ot);
-    }
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-int cart_plane_classify_multi(cart_engine *e, int n_frames, const int16_t *const *deriv, size_t deriv_step, const cart_plane_params *params,
-                              int params_per_frame, uint8_t *const *planes, size_t planes_step, void *stream_) {
-    if (!e) return fail("engine is NULL");
-    if (!deriv || !planes || !params) return fail("NULL pointer");
-    if (n_frames <= 0) return fail("n_frames must be positive");
-    const Geometry &g = e->g;
-    if (deriv_step < (size_t)g.w * 2 || planes_step < (size_t)g.w || (deriv_step & 1)) return fail("bad step");
-    for (int f = 0; f < n_frames; ++f)
-        if (!deriv[f] || !planes[f]) return fail("NULL image pointer in a pointer table");
-    HIP_TRY(hipSetDevice(e->params.device_id));
-    static_assert(kMaxBatchArgs >= kLaunchFrames, "one ClassifyParams covers a launch");
-    for (int f0 = 0; f0 < n_frames; f0 += kLaunchFrames) {
-        const int n = std::min(kLaunchFrames, n_frames - f0);
-        ClassifyParams cp;
-        if (params_per_frame) std::memcpy(cp.p, params + f0, sizeof(cart_plane_params) * (size_t)n);
-        else cp.p[0] = params[0];
-        FrameTable dt{}, pt{};
-        dt.scattered = pt.scattered = 1;
-        for (int f = 0; f < n; ++f) { dt.p[f] = deriv[f0 + f]; pt.p[f] = planes[f0 + f]; }
-        launch_classify(nullptr, deriv_step, 0, cp, params_per_frame, nullptr, planes_step, 0, g.w, g.h, n, static_cast<hipStream_t>(stream_), &dt, &pt);
-    }
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-int cart_plane_ccl(cart_engine *e, int n_frames, const uint8_t *planes, size_t planes_step, size_t planes_frame_stride,
-                   int32_t *ids, size_t ids_step, size_t ids_frame_stride, int32_t *n_components, void *stream_) {
-    if (!e) return fail("engine is NULL");
-    if (!planes || !ids) return fail("NULL pointer");
-    const Geometry &g = e->g;
-    if (planes_step < (size_t)g.w || ids_step < (size_t)g.w * 4 || (ids_step & 3) || (ids_frame_stride & 3)) return fail("bad step");
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    HIP_TRY(hipSetDevice(e->params.device_id));
-    Lease l;
-    if (acquire(e, n_frames, stream, &l)) return -1;
-    launch_ccl(planes, planes_step, planes_frame_stride, e->ccl_work + (size_t)l.s0 * g.npx, ids, ids_step, ids_frame_stride,
-               n_components, g.w, g.h, n_frames, stream);
-    hipError_t err = hipGetLastError();
-    release(l);
-    if (err != hipSuccess) return fail(std::string("ccl failed: ") + hipGetErrorString(err));
-    return 0;
-}
-
-namespace {
-// The component-table workspace: [slots][npx][5] statistics scratch, then [slots][h][tile columns] root counts (post_kernels.hip).  The
-// scratch is zeroed ONCE, here: every call returns it to zero (ccl_table_kernel collects and clears exactly the entries the call grew).
-int ensure_ccl_stats_ws(cart_engine *e) {
-    std::lock_guard<std::mutex> lk(e->mu);
-    if (e->ccl_stats_ws) return 0;
-    const size_t bytes = e->slots.size() * ccl_stats_ws_ints(e->g.w, e->g.h) * sizeof(int32_t);
-    int32_t *ws = nullptr;
-    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&ws), bytes));
-    if (hipMemset(ws, 0, bytes) != hipSuccess || hipDeviceSynchronize() != hipSuccess) { (void)hipFree(ws); return fail("hipMemset of the component-table workspace failed"); }
-    e->ccl_stats_ws = ws;
-    return 0;
-}
-int32_t *ccl_stat_of(cart_engine *e, int slot) { return e->ccl_stats_ws + (size_t)slot * e->g.npx * 5; }
-int32_t *ccl_seg_of(cart_engine *e, int slot) {
-    return e->ccl_stats_ws + e->slots.size() * e->g.npx * 5 + (size_t)slot * (ccl_stats_ws_ints(e->g.w, e->g.h) - e->g.npx * 5);
-}
-}  // namespace
-
-int cart_plane_ccl_stats(cart_engine *e, int n_frames, const uint8_t *planes, size_t planes_step, size_t planes_frame_stride,
-                         const int32_t *ids, size_t ids_step, size_t ids_frame_stride, cart_component *table, int max_components,
-                         int32_t *n_components, void *stream_) {
-    if (!e) return fail("engine is NULL");
-    if (!planes || !ids || !table) return fail("NULL pointer");
-    if (max_components < 1) return fail("max_components must be positive");
-    const Geometry &g = e->g;
-    if (planes_step < (size_t)g.w || ids_step < (size_t)g.w * 4 || (ids_step & 3) || (ids_frame_stride & 3)) return fail("bad step");
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    HIP_TRY(hipSetDevice(e->params.device_id));
-    if (ensure_ccl_stats_ws(e)) return -1;
-    Lease l;
-    if (acquire(e, n_frames, stream, &l)) return -1;
-    launch_ccl_stats(planes, planes_step, planes_frame_stride, ids, ids_step, ids_frame_stride, ccl_stat_of(e, l.s0), ccl_seg_of(e, l.s0), table, max_components,
-                     n_components, g.w, g.h, n_frames, stream);
-    hipError_t err = hipGetLastError();
-    release(l);
-    if (err != hipSuccess) return fail(std::string("ccl stats failed: ") + hipGetErrorString(err));
-    return 0;
-}
-
-int cart_plane_ccl_table(cart_engine *e, int n_frames, const uint8_t *planes, size_t planes_step, size_t planes_frame_stride, int32_t *ids, size_t ids_step,
-                         size_t ids_frame_stride, cart_component *table, int max_components, int32_t *n_components, void *stream_) {
-    if (!e) return fail("engine is NULL");
-    if (!planes || !ids || !table) return fail("NULL pointer");
-    if (max_components < 1) return fail("max_components must be positive");
-    const Geometry &g = e->g;
-    if (planes_step < (size_t)g.w || ids_step < (size_t)g.w * 4 || (ids_step & 3) || (ids_frame_stride & 3)) return fail("bad step");
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    HIP_TRY(hipSetDevice(e->params.device_id));
-    if (ensure_ccl_stats_ws(e)) return -1;
-    Lease l;
-    if (acquire(e, n_frames, stream, &l)) return -1;
-    launch_ccl(planes, planes_step, planes_frame_stride, e->ccl_work + (size_t)l.s0 * g.npx, ids, ids_step, ids_frame_stride, n_components, g.w, g.h, n_frames, stream,
-               ccl_stat_of(e, l.s0), ccl_seg_of(e, l.s0), table, max_components);
-    hipError_t err = hipGetLastError();
-    release(l);
-    if (err != hipSuccess) return fail(std::string("ccl failed: ") + hipGetErrorString(err));
-    return 0;
-}
-
-struct cart_plane_schedule {
-    int device_id;         // the engine's; kept here so that the schedule can outlive the engine it was created on
-    ScheduleState *state;  // device
-    int provider, update_interval, reset_interval;
-};
-
-int cart_plane_schedule_create(cart_engine *e, int provider, const cart_plane_params *initial, int update_interval,
-                               int reset_interval, cart_plane_schedule **out) {
-    if (!e || !out) return fail("bad arguments");
-    if (provider != 0 && provider != 1) return fail("Unknown parameter provider type.");
-    if (update_interval < 1 || reset_interval < 1) return fail("intervals must be >= 1");
-    HIP_TRY(hipSetDevice(e->params.device_id));
-    cart_plane_schedule *s = new (std::nothrow) cart_plane_schedule{e->params.device_id, nullptr, provider, update_interval, reset_interval};
-    if (!s) return fail("out of host memory");
-    ScheduleState init;
-    std::memset(&init, 0, sizeof(init));
-    if (initial) init.params = *initial;
-    if (hipMalloc(reinterpret_cast<void **>(&s->state), sizeof(ScheduleState)) != hipSuccess ||
-        hipMemcpy(s->state, &init, sizeof(init), hipMemcpyHostToDevice) != hipSuccess) {
-        cart_plane_schedule_destroy(s);
-        return fail("hipMalloc/hipMemcpy of the schedule state failed");
-    }
-    *out = s;
-    return 0;
-}
-
-void cart_plane_schedule_destroy(cart_plane_schedule *s) {
-    if (!s) return;
-    (void)hipSetDevice(s->device_id);   // the caller's current device may be another one
-    if (s->state) (void)hipFree(s->state);
-    delete s;
-}
-
-int cart_plane_schedule_advance(cart_plane_schedule *s, int first_id, int n_frames, const int32_t *hists,
-                                cart_plane_params *params_out, void *stream) {
-    if (!s || !hists || !params_out) return fail("bad arguments");
-    if (n_frames <= 0 || first_id < 1) return fail("n_frames must be positive and ids are 1-based");
-    HIP_TRY(hipSetDevice(s->device_id));
-    launch_plane_schedule(s->state, s->provider, first_id, n_frames, s->update_interval, s->reset_interval, hists, params_out,
-                          static_cast<hipStream_t>(stream));
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-int cart_plane_schedule_read(cart_plane_schedule *s, cart_plane_params *params_host, int32_t cum_hist_host[256]) {
-    if (!s) return fail("bad arguments");
-    HIP_TRY(hipSetDevice(s->device_id));
-    HIP_TRY(hipDeviceSynchronize());
-    ScheduleState st;
-    HIP_TRY(hipMemcpy(&st, s->state, sizeof(st), hipMemcpyDeviceToHost));
-    if (params_host) *params_host = st.params;
-    if (cum_hist_host) std::memcpy(cum_hist_host, st.cum, sizeof(st.cum));
-    return 0;
-}
-
-int cart_plane_classify_dev(cart_engine *e, int n_frames, const int16_t *deriv, size_t deriv_step, size_t deriv_frame_stride,
-                            const cart_plane_params *params_dev, int params_stride, uint8_t *planes, size_t planes_step,
-                            size_t planes_frame_stride, void *stream_) {
-    if (!e) return fail("engine is NULL");
-    if (!deriv || !planes || !params_dev) return fail("NULL pointer");
-    if (n_frames <= 0) return fail("n_frames must be positive");
-    const Geometry &g = e->g;
-    if (deriv_step < (size_t)g.w * 2 || planes_step < (size_t)g.w || (deriv_step & 1) || (deriv_frame_stride & 1)) return fail("bad step");
-    HIP_TRY(hipSetDevice(e->params.device_id));
-    launch_classify_dev(deriv, deriv_step, deriv_frame_stride, params_dev, params_stride ? 1 : 0, planes, planes_step, planes_frame_stride,
-                        g.w, g.h, n_frames, static_cast<hipStream_t>(stream_));
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-int cart_plane_temporal_vote(cart_engine *e, const uint8_t *planes, size_t planes_step, int n_prev, const uint8_t *const *prev_planes,
-                             const size_t *prev_steps, const int16_t *const *flows, const size_t *flow_steps, uint8_t *smoothed,
-                             size_t smoothed_step, void *stream_) {
-    if (!e) return fail("engine is NULL");
-    if (!planes || !smoothed) return fail("NULL pointer");
-    if (n_prev < 0 || n_prev > CART_MAX_TEMPORAL) return fail("n_prev must be in [0, CART_MAX_TEMPORAL]");
-    if (n_prev > 0 && (!prev_planes || !prev_steps || !flows || !flow_steps)) return fail("NULL table");
-    const Geometry &g = e->g;
-    if (planes_step < (size_t)g.w || smoothed_step < (size_t)g.w) return fail("bad step");
-    TemporalArgs t;
-    std::memset(&t, 0, sizeof(t));
-    t.n_prev = n_prev;
-    for (int k = 0; k < n_prev; ++k) {
-        if (!prev_planes[k] || !flows[k]) return fail("NULL entry in the temporal tables");
-        if (prev_steps[k] < (size_t)g.w || flow_steps[k] < (size_t)g.w * 4 || (flow_steps[k] & 3)) return fail("bad step in the temporal tables");
-        t.prev[k] = prev_planes[k]; t.prev_step[k] = prev_steps[k]; t.flow[k] = flows[k]; t.flow_step[k] = flow_steps[k];
-    }
-    HIP_TRY(hipSetDevice(e->params.device_id));
-    launch_temporal_vote(planes, planes_step, t, smoothed, smoothed_step, g.w, g.h, static_cast<hipStream_t>(stream_));
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-int cart_reproject_depth(cart_engine *e, int n_frames, const int16_t *disp, size_t disp_step, size_t disp_frame_stride, const float Q[16],
-                         float *xyz, size_t xyz_step, size_t xyz_frame_stride, void *stream_) {
-    if (!e) return fail("engine is NULL");
-    if (!disp || !xyz || !Q) return fail("NULL pointer");
-    if (n_frames <= 0) return fail("n_frames must be positive");
-    const Geometry &g = e->g;
-    if (disp_step < (size_t)g.w * 2 || (disp_step & 1) || (disp_frame_stride & 1) || xyz_step < (size_t)g.w * 12 || (xyz_step & 3) || (xyz_frame_stride & 3))
-        return fail("bad step");
-    HIP_TRY(hipSetDevice(e->params.device_id));
-    QMatrix q;
-    std::memcpy(q.q, Q, sizeof(q.q));
-    launch_reproject(disp, disp_step, disp_frame_stride, q, xyz, xyz_step, xyz_frame_stride, g.w, g.h, n_frames, static_cast<hipStream_t>(stream_));
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-// ---- superpixels (replaces ContourRelaxation + SuperPixelModule's device work; oracle S13/S14) ----
-struct cart_superpixels : DeviceObject {
-    using DeviceObject::DeviceObject;
-    cart_superpixel_params params;
-    int block_w = 0, block_h = 0;
-    int max_label_id = 0;        // number of initial blocks (labels are < max_label_id)
-    uint16_t *labels[2] = {nullptr, nullptr};  // tight [h][w]; labels[cur] is the state
-    int cur = 0;
-    uint32_t *ycc = nullptr;
-    long long *stats = nullptr;  // [kSpStatRows][ld] statistics followed by [kSpStatRows][ld] of per-sweep delta (capacity 2 x kSpStatRows x kSpMaxLabels)
-    double *costs = nullptr;
-    int *max_seen = nullptr;
-};
-
-void cart_superpixel_default_params(cart_superpixel_params *p) {
-    if (!p) return;
-    p->direct_clique_cost = 0.5;                       // cartconfig.cpp:128
-    p->diagonal_clique_cost = 0.5 / std::sqrt(2.0);    // cartconfig.cpp:129
-    p->compactness_weight = 0.1;                       // cartconfig.cpp:130
-    p->progressive_compactness_cost = 0.0;             // cartconfig.cpp:131
-    p->image_weight = 1.5;                             // cartconfig.cpp:132
-    p->disparity_weight = 1.0;                         // cartconfig.cpp:133
-}
-
-int cart_superpixels_create(cart_engine *e, const cart_superpixel_params *params, int block_w, int block_h, cart_superpixels **out) {
-    if (!e || !params || !out) return fail("bad arguments");
-    if (block_w < 1 || block_h < 1) return fail("blockSize must be more than 1");                      // superpixels.cu:37-39
-    if (params->direct_clique_cost < 0) return fail("directCliqueCost must be non-negative");          // superpixels.cu:41-43
-    if (params->compactness_weight < 0 || params->image_weight < 0 || params->disparity_weight < 0)
-        return fail("weight must be non-negative");                                                    // superpixels.cu:45-47
-    const Geometry &g = e->g;
-    if (g.w < block_w || g.h < block_h) return fail("image smaller than one block");                   // initialization.cu:42
-    const long blocks = (long)((g.w + block_w - 1) / block_w) * ((g.h + block_h - 1) / block_h);
-    if (blocks >= kSpMaxLabels) return fail("too many superpixels: number of blocks must be < 16384 (increase block size)");
-    HIP_TRY(hipSetDevice(e->params.device_id));
-    cart_superpixels *sp = new (std::nothrow) cart_superpixels(e);
-    if (!sp) return fail("out of host memory");
-    sp->params = *params; sp->block_w = block_w; sp->block_h = block_h; sp->max_label_id = (int)blocks;
-    const size_t stat_elems = (size_t)kSpStatRows * kSpMaxLabels;
-    bool failed = sp->alloc(&sp->labels[0], g.npx * 2) || sp->alloc(&sp->labels[1], g.npx * 2) || sp->alloc(&sp->ycc, g.npx * 4) ||
-                  sp->alloc(&sp->stats, 2 * stat_elems * 8) ||   // statistics, then their per-sweep delta (one memset per call)
-                  sp->alloc(&sp->costs, (size_t)kSpChannels * kSpMaxLabels * 8) || sp->alloc(&sp->max_seen, sizeof(int)) || sp->create_event();
-    if (!failed) {
-        launch_sp_block_init(sp->labels[0], g.w, g.h, block_w, block_h, nullptr);
-        failed = hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess;
-    }
-    if (failed) {
-        destroy_object(sp);
-        return fail("allocating the superpixel state failed");
-    }
-    *out = sp;
-    return 0;
-}
-
-void cart_superpixels_destroy(cart_superpixels *sp) { destroy_object(sp); }
-
-int cart_superpixels_max_label(const cart_superpixels *sp) { return sp ? sp->max_label_id : -1; }
-
-int cart_superpixels_reset(cart_superpixels *sp, void *stream_) {
-    if (!sp) return fail("superpixels is NULL");
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    const Geometry &g = sp->g;
-    ObjectCall call(*sp, stream);
-    if (call.begin()) return -1;
-    launch_sp_block_init(sp->labels[sp->cur], g.w, g.h, sp->block_w, sp->block_h, stream);
-    sp->max_label_id = ((g.w + sp->block_w - 1) / sp->block_w) * ((g.h + sp->block_h - 1) / sp->block_h);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-int cart_superpixels_set_labels(cart_superpixels *sp, const uint16_t *labels, size_t labels_step, int max_label_id, void *stream_) {
-    if (!sp || !labels) return fail("bad arguments");
-    if (max_label_id < 1 || max_label_id >= kSpMaxLabels) return fail("max_label_id must be in [1, 16384)");
-    const Geometry &g = sp->g;
-    if (labels_step < (size_t)g.w * 2 || (labels_step & 1)) return fail("bad step");
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    ObjectCall call(*sp, stream);
-    if (call.begin()) return -1;
-    // the copy goes to the spare buffer and becomes the state only if every label is in range
-    uint16_t *spare = sp->labels[sp->cur ^ 1];
-    HIP_TRY(hipMemsetAsync(sp->max_seen, 0, sizeof(int), stream));
-    launch_sp_copy(labels, labels_step, spare, (size_t)g.w * 2, g.w, g.h, sp->max_seen, stream);
-    int seen = 0;
-    HIP_TRY(hipMemcpyAsync(&seen, sp->max_seen, sizeof(int), hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    if (seen >= max_label_id) return fail("label image holds a label >= max_label_id");
-    sp->cur ^= 1;
-    sp->max_label_id = max_label_id;
-    return 0;
-}
-
-int cart_superpixels_relax(cart_superpixels *sp, const uint8_t *image, size_t image_step, int channels, const int16_t *deriv2,
-                           size_t deriv2_step, int iterations, uint16_t *labels_out, size_t labels_out_step, void *stream_) {
-    if (!sp) return fail("superpixels is NULL");
-    if (!image) return fail("NULL pointer");
-    if (channels != 1 && channels != 3) return fail("channels must be 1 or 3");
-    if (iterations < 0) return fail("iterations must be >= 0");
-    const Geometry &g = sp->g;
-    const cart_superpixel_params &p = sp->params;
-    if (image_step < (size_t)g.w * channels) return fail("bad step");
-    if (p.disparity_weight > 0) {
-        if (!deriv2) return fail("the disparity feature needs the 2-channel disparity derivative image");
-        if (deriv2_step < (size_t)g.w * 4 || (deriv2_step & 3) || (reinterpret_cast<uintptr_t>(deriv2) & 3)) return fail("bad step");
-    }
-    if (labels_out && (labels_out_step < (size_t)g.w * 2 || (labels_out_step & 1))) return fail("bad step");
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    ObjectCall call(*sp, stream);
-    if (call.begin()) return -1;
-    const int ld = sp->max_label_id + 1;
-    SpRelaxArgs a;
-    std::memset(&a, 0, sizeof(a));
-    a.ycc = sp->ycc; a.deriv = p.disparity_weight > 0 ? deriv2 : nullptr; a.deriv_step = deriv2_step;
-    a.stats = sp->stats; a.costs = sp->costs; a.delta = sp->stats + (size_t)kSpStatRows * ld; a.ld = ld; a.w = g.w; a.h = g.h;
-    a.ch_mask = (p.compactness_weight > 0 ? 0x03u : 0u) | (p.disparity_weight > 0 ? 0x0cu : 0u) | (p.image_weight > 0 ? 0x70u : 0u);
-    a.direct = p.direct_clique_cost; a.diagonal = p.diagonal_clique_cost; a.w_comp = p.compactness_weight;
-    a.prog = p.progressive_compactness_cost; a.w_img = p.image_weight; a.w_disp = p.disparity_weight;
-    if (iterations > 0) {   // the colour planes and the label statistics only serve the sweeps; every call rebuilds them from the image and the labels
-        launch_sp_ycrcb(image, image_step, channels, sp->ycc, g.w, g.h, stream);
-        HIP_TRY(hipMemsetAsync(sp->stats, 0, 2 * (size_t)kSpStatRows * ld * 8, stream));
-        a.cur = sp->labels[sp->cur]; a.next = sp->labels[sp->cur ^ 1];
-        launch_sp_stats(a, stream);
-        launch_sp_fold(a.stats, a.delta, sp->costs, ld, a.ch_mask, stream);
-    }
-    for (int it = 0; it < iterations; ++it) {
-        a.cur = sp->labels[sp->cur]; a.next = sp->labels[sp->cur ^ 1];
-        launch_sp_relax(a, stream);
-        if (it + 1 < iterations) launch_sp_fold(a.stats, a.delta, sp->costs, ld, a.ch_mask, stream);   // the last sweep's delta has no reader
-        sp->cur ^= 1;
-    }
-    if (labels_out) launch_sp_copy(sp->labels[sp->cur], (size_t)g.w * 2, labels_out, labels_out_step, g.w, g.h, nullptr, stream);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-int cart_superpixel_plane_classify(cart_engine *e, const int16_t *deriv2, size_t deriv2_step, const uint16_t *labels, size_t labels_step,
-                                   int max_label, const cart_plane_params *params, int n_prev, const uint8_t *const *prev_planes,
-                                   const size_t *prev_steps, const int16_t *const *flows, const size_t *flow_steps,
-                                   uint8_t *planes_unsmoothed, size_t planes_unsmoothed_step, uint8_t *planes, size_t planes_step,
-                                   void *stream_) {
-    if (!e) return fail("engine is NULL");
-    if (!deriv2 || !labels || !params || !planes_unsmoothed || !planes) return fail("NULL pointer");
-    if (max_label < 1 || max_label > kSpMaxLabels) return fail("max_label must be in [1, 16384]");
-    if (n_prev < 0 || n_prev > CART_MAX_TEMPORAL) return fail("n_prev must be in [0, CART_MAX_TEMPORAL]");
-    if (n_prev > 0 && (!prev_planes || !prev_steps || !flows || !flow_steps)) return fail("NULL table");
-    const Geometry &g = e->g;
-    if (deriv2_step < (size_t)g.w * 4 || (deriv2_step & 3) || labels_step < (size_t)g.w * 2 || (labels_step & 1) ||
-        planes_unsmoothed_step < (size_t)g.w || planes_step < (size_t)g.w)
-        return fail("bad step");
-    SpClassifyArgs a;
-    std::memset(&a, 0, sizeof(a));
-    a.t.n_prev = n_prev;
-    for (int k = 0; k < n_prev; ++k) {
-        if (!prev_planes[k] || !flows[k]) return fail("NULL entry in the temporal tables");
-        if (prev_steps[k] < (size_t)g.w || flow_steps[k] < (size_t)g.w * 4 || (flow_steps[k] & 3)) return fail("bad step in the temporal tables");
-        a.t.prev[k] = prev_planes[k]; a.t.prev_step[k] = prev_steps[k]; a.t.flow[k] = flows[k]; a.t.flow_step[k] = flow_steps[k];
-    }
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    HIP_TRY(hipSetDevice(e->params.device_id));
-    {
-        std::lock_guard<std::mutex> lk(e->mu);
-        if (!e->sp_votes) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&e->sp_votes), e->slots.size() * (size_t)kSpMaxLabels * 3 * sizeof(unsigned)));
-    }
-    Lease lease;
-    if (acquire(e, 1, stream, &lease)) return -1;
-    a.deriv = deriv2; a.deriv_step = deriv2_step; a.labels = labels; a.labels_step = labels_step;
-    a.w = g.w; a.h = g.h; a.max_label = max_label; a.p = *params;
-    a.unsmoothed = planes_unsmoothed; a.unsmoothed_step = planes_unsmoothed_step; a.planes = planes; a.planes_step = planes_step;
-    a.votes = e->sp_votes + (size_t)lease.s0 * kSpMaxLabels * 3;
-    hipError_t err = hipMemsetAsync(a.votes, 0, (size_t)max_label * 3 * sizeof(unsigned), stream);
-    if (err == hipSuccess) launch_sp_classify(a, stream);
-    release(lease);
-    if (err != hipSuccess) return fail(std::string("hipMemsetAsync: ") + hipGetErrorString(err));
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-// ---- superpixel plane fitting ----
-struct cart_planefit : DeviceObject {
-    using DeviceObject::DeviceObject;
-    int cap_L1 = 0, ntiles = 0;
-    int32_t *cursor = nullptr;    // [ntiles][cap_L1] tile counts -> tile offsets
-    int32_t *cnt = nullptr;       // [cap_L1][2]
-    int32_t *npts = nullptr;      // [cap_L1]
-    int32_t *start = nullptr;     // [cap_L1 + 1]
-    int32_t *err = nullptr;       // label out of range (bit 0), adjacency capacity (bit 1)
-    float4 *pts = nullptr;        // [w*h]
-    double *planes17 = nullptr;   // [cap_L1][4]
-    uint32_t *bits = nullptr;     // [cap_L1][words] adjacency bitmap (allocated by the first adjacency call)
-    int32_t *adj_cnt = nullptr;   // [cap_L1]
-    PfFitState *state = nullptr;
-    double *local = nullptr;      // [kPfMaxLocal][4]
-    uint64_t *accept = nullptr;   // [cap_L1]
-    int last_L1 = 0, last_pred = -1;
-};
-
-namespace {
-int pf_grid_slots(int w, int h) {   // selectRandomSuperpixels(4, 3) positions (planefit.cu:333-351)
-    const int ys = h / 5, xs = w / 6;
-    return (ys > 0 && xs > 0) ? ((h - 1) / ys) * ((w - 1) / xs) : 0;
-}
-}  // namespace
-
-int cart_planefit_create(cart_engine *e, int max_label_capacity, cart_planefit **out) {
-    if (!e || !out) return fail("bad arguments");
-    if (max_label_capacity < 0 || max_label_capacity >= kSpMaxLabels) return fail("max_label_capacity must be in [0, 16383]");
-    const Geometry &g = e->g;
-    if (pf_grid_slots(g.w, g.h) > kPfMaxLocal) return fail("image too small for the planefit sampling grid");
-    HIP_TRY(hipSetDevice(e->params.device_id));
-    cart_planefit *pf = new (std::nothrow) cart_planefit(e);
-    if (!pf) return fail("out of host memory");
-    pf->cap_L1 = max_label_capacity + 1; pf->ntiles = pf_tiles(g.w, g.h);
-    const size_t L1 = (size_t)pf->cap_L1;
-    if (pf->alloc(&pf->cursor, (size_t)pf->ntiles * L1 * 4) || pf->alloc(&pf->cnt, L1 * 8) || pf->alloc(&pf->npts, L1 * 4) ||
-        pf->alloc(&pf->start, (L1 + 1) * 4) || pf->alloc(&pf->err, 4) || pf->alloc(&pf->pts, g.npx * sizeof(float4)) ||
-        pf->alloc(&pf->planes17, L1 * 32) || pf->alloc(&pf->adj_cnt, L1 * 4) || pf->alloc(&pf->state, sizeof(PfFitState)) ||
-        pf->alloc(&pf->local, (size_t)kPfMaxLocal * 32) || pf->alloc(&pf->accept, L1 * 8) || hipMemset(pf->err, 0, 4) != hipSuccess ||
-        pf->create_event()) {
-        destroy_object(pf);
-        return fail("allocating the planefit workspaces failed");
-    }
-    *out = pf;
-    return 0;
-}
-
-void cart_planefit_destroy(cart_planefit *pf) { destroy_object(pf); }
-
-int cart_planefit_label_planes(cart_planefit *pf, const uint16_t *labels, size_t labels_step, int max_label, const float *xyz, size_t xyz_step,
-                               int predicate, double thr, uint64_t seed, uint64_t frame_id, double *planes, int32_t *npoints, int32_t *counts,
-                               void *stream_) {
-    if (!pf) return fail("planefit is NULL");
-    if (!labels || !xyz) return fail("NULL image pointer");
-    if (max_label < 0 || max_label + 1 > pf->cap_L1) return fail("max_label must be in [0, max_label_capacity]");
-    if (predicate != CART_PLANE_PREDICATE_PLANEFIT && predicate != CART_PLANE_PREDICATE_PLANECLUSTER) return fail("unknown predicate");
-    if (!(thr > 0)) return fail("thr must be positive");
-    const Geometry &g = pf->g;
-    if (labels_step < (size_t)g.w * 2 || (labels_step & 1) || xyz_step < (size_t)g.w * 12 || (xyz_step & 3)) return fail("bad step");
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    ObjectCall call(*pf, stream);
-    if (call.begin()) return -1;
-    const int L1 = max_label + 1;
-    HIP_TRY(hipMemsetAsync(pf->cursor, 0, (size_t)pf->ntiles * L1 * 4, stream));
-    HIP_TRY(hipMemsetAsync(pf->cnt, 0, (size_t)L1 * 8, stream));
-    HIP_TRY(hipMemsetAsync(pf->err, 0, 4, stream));
-    launch_pf_points(labels, labels_step, xyz, xyz_step, g.w, g.h, L1, predicate, pf->cursor, pf->ntiles, pf->cnt, pf->npts, pf->start,
-                     pf->pts, pf->err, stream);
-    launch_pf_ransac(pf->pts, pf->start, pf->npts, L1, thr, seed, frame_id, pf->planes17, stream);
-    HIP_TRY(hipGetLastError());
-    if (planes) HIP_TRY(hipMemcpyAsync(planes, pf->planes17, (size_t)L1 * 32, hipMemcpyDeviceToDevice, stream));
-    if (npoints) HIP_TRY(hipMemcpyAsync(npoints, pf->npts, (size_t)L1 * 4, hipMemcpyDeviceToDevice, stream));
-    if (counts) HIP_TRY(hipMemcpyAsync(counts, pf->cnt, (size_t)L1 * 8, hipMemcpyDeviceToDevice, stream));
-    pf->last_L1 = L1;
-    pf->last_pred = predicate;
-    return 0;
-}
-
-int cart_planefit_points(cart_planefit *pf, float *points, size_t capacity, int32_t *offsets, void *stream_) {
-    if (!pf) return fail("planefit is NULL");
-    if (!points || !offsets) return fail("NULL pointer");
-    if (pf->last_L1 == 0) return fail("no label_planes call yet");
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    ObjectCall call(*pf, stream);
-    if (call.begin()) return -1;
-    int32_t total = 0;
-    HIP_TRY(hipMemcpyAsync(&total, pf->start + pf->last_L1, 4, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    if ((size_t)total > capacity) return fail("capacity is smaller than the number of points");
-    HIP_TRY(hipMemcpyAsync(points, pf->pts, (size_t)total * sizeof(float4), hipMemcpyDeviceToDevice, stream));
-    HIP_TRY(hipMemcpyAsync(offsets, pf->start, ((size_t)pf->last_L1 + 1) * 4, hipMemcpyDeviceToDevice, stream));
-    return 0;
-}
-
-int cart_planefit_adjacency(cart_planefit *pf, const uint16_t *labels, size_t labels_step, int max_label, int32_t *offsets, int32_t *neighbours,
-                            size_t capacity, void *stream_) {
-    if (!pf) return fail("planefit is NULL");
-    if (!labels || !offsets || !neighbours) return fail("NULL pointer");
-    if (max_label < 0 || max_label + 1 > pf->cap_L1) return fail("max_label must be in [0, max_label_capacity]");
-    const Geometry &g = pf->g;
-    if (labels_step < (size_t)g.w * 2 || (labels_step & 1)) return fail("bad step");
-    const size_t L1 = (size_t)max_label + 1;
-    if (capacity < std::min(8 * g.npx, L1 * (L1 - 1))) return fail("capacity must be >= min(8 * width * height, (max_label + 1) * max_label)");
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    ObjectCall call(*pf, stream);
-    if (call.begin()) return -1;
-    const size_t words = ((size_t)pf->cap_L1 + 31) / 32;
-    if (!pf->bits && pf->alloc(&pf->bits, (size_t)pf->cap_L1 * words * 4)) return -1;
-    const size_t used_words = (L1 + 31) / 32;
-    HIP_TRY(hipMemsetAsync(pf->bits, 0, L1 * used_words * 4, stream));
-    HIP_TRY(hipMemsetAsync(pf->err, 0, 4, stream));
-    launch_pf_adjacency(labels, labels_step, g.w, g.h, (int)L1, pf->bits, pf->adj_cnt, offsets, neighbours, capacity, pf->err, stream);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-int cart_planefit_fit(cart_planefit *pf, const uint16_t *labels, size_t labels_step, uint64_t seed, uint64_t frame_id, double *planes,
-                      uint64_t *assignments, int32_t *n_planes, int *launches, void *stream_) {
-    if (!pf) return fail("planefit is NULL");
-    if (!labels || !planes || !assignments || !n_planes) return fail("NULL pointer");
-    if (pf->last_L1 == 0 || pf->last_pred != CART_PLANE_PREDICATE_PLANEFIT)
-        return fail("cart_planefit_fit needs a preceding label_planes call with CART_PLANE_PREDICATE_PLANEFIT");
-    const Geometry &g = pf->g;
-    if (labels_step < (size_t)g.w * 2 || (labels_step & 1)) return fail("bad step");
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    ObjectCall call(*pf, stream);
-    if (call.begin()) return -1;
-    PfFitArgs a;
-    std::memset(&a, 0, sizeof(a));
-    a.labels = labels; a.lstep = labels_step; a.w = g.w; a.h = g.h; a.L1 = pf->last_L1; a.seed = seed; a.frame = frame_id;
-    a.cnt = pf->cnt; a.npts = pf->npts; a.start = pf->start; a.err = pf->err; a.pts = pf->pts; a.planes17 = pf->planes17;
-    a.state = pf->state; a.local = pf->local; a.accept = pf->accept; a.planes_out = planes; a.assign = assignments; a.nplanes_out = n_planes;
-    const int n = launch_pf_fit(a, stream);
-    HIP_TRY(hipGetLastError());
-    if (launches) *launches = n;
-    return 0;
-}
-
-int cart_planefit_status(cart_planefit *pf, int *bad_labels) {
-    if (!pf || !bad_labels) return fail("bad arguments");
-    HIP_TRY(hipSetDevice(pf->device_id));
-    std::lock_guard<std::mutex> lk(pf->mu);
-    int32_t err = 0;
-    if (pf->used) HIP_TRY(hipEventSynchronize(pf->done));
-    HIP_TRY(hipMemcpy(&err, pf->err, 4, hipMemcpyDeviceToHost));
-    if (err & 2) return fail("internal error: adjacency capacity exceeded");
-    *bad_labels = err & 1;
-    return 0;
-}
-
-int cart_plane_cluster(const double *planes, int max_label, const int32_t *offsets, const int32_t *neighbours, double *planes_out,
-                       uint64_t *assignments, int *n_planes) {
-    if (!planes || !offsets || !neighbours || !planes_out || !assignments || !n_planes) return fail("NULL pointer");
-    if (max_label < 0 || max_label >= kSpMaxLabels) return fail("max_label must be in [0, 16383]");
-    const int L1 = max_label + 1;
-    if (offsets[0] != 0) return fail("offsets[0] must be 0");
-    for (int l = 0; l < L1; ++l)
-        if (offsets[l] > offsets[l + 1]) return fail("offsets are not ascending");
-    for (int32_t k = offsets[0]; k < offsets[L1]; ++k)
-        if (neighbours[k] < 0 || neighbours[k] >= L1) return fail("neighbour label out of range");
-    struct Stats { double d, ys, yc, ps, pc; };   // planecluster.cpp:8-17 (the fields the merge reads)
-    std::vector<Stats> st(L1);
-    std::vector<char> zero(L1);
-    for (int l = 0; l < L1; ++l) {
-        const double *p = planes + (size_t)l * 4;
-        zero[l] = p[0] == 0 && p[1] == 0 && p[2] == 0 && p[3] == 0;
-        if (zero[l]) continue;
-        const double length = std::sqrt((p[0] * p[0] + p[1] * p[1]) + p[2] * p[2]);   // planecluster.cpp:58-66
-        const double yaw = std::atan2(p[1], p[0]), pitch = std::atan2(p[2], length);
-        st[l] = Stats{p[3], std::sin(yaw), std::cos(yaw), std::sin(pitch), std::cos(pitch)};
-    }
-    std::vector<int> seeds;          // seed label of every plane, in order
-    std::fill(assignments, assignments + L1, (uint64_t)0);
-    std::vector<char> seen(L1);
-    std::vector<int> similar;
-    std::set<int> frontier;
-    for (int l = 0; l < L1; ++l) {   // planecluster.cpp:98-167 with one thread: ascending seeds
-        if (assignments[l] != 0 || zero[l]) continue;
-        const Stats &s = st[l];
-        similar.assign(1, l);
-        std::fill(seen.begin(), seen.end(), 0);
-        seen[l] = 1;
-        frontier.clear();
-        frontier.insert(neighbours + offsets[l], neighbours + offsets[l + 1]);
-        while (!frontier.empty()) {
-            const int o = *frontier.begin();
-            frontier.erase(frontier.begin());
-            seen[o] = 1;
-            if (zero[o]) continue;
-            const Stats &t = st[o];
-            const double yawd = std::abs(s.ys - t.ys) + std::abs(s.yc - t.yc);
-            const double pitchd = std::abs(s.ps - t.ps) + std::abs(s.pc - t.pc);
-            const double dd = std::abs(s.d - t.d);
-            if (yawd < 0.2 && pitchd < 0.2 && dd < 3) {
-                const uint64_t cur = assignments[o];
-                if (cur != 0) {   // kept literally: dDiff on both sides (planecluster.cpp:137)
-                    const Stats &u = st[seeds[cur - 1]];
-                    const double cy = std::abs(u.ys - t.ys) + std::abs(u.yc - t.yc);
-                    const double cp = std::abs(u.ps - t.ps) + std::abs(u.pc - t.pc);
-                    if (cy + cp + dd < yawd + pitchd + dd) continue;
-                }
-                similar.push_back(o);
-                for (int32_t k = offsets[o]; k < offsets[o + 1]; ++k)
-                    if (!seen[neighbours[k]]) frontier.insert(neighbours[k]);
-            }
-        }
-        if (similar.size() < 32) continue;
-        seeds.push_back(l);
-        for (int q : similar) assignments[q] = seeds.size();
-    }
-    for (size_t k = 0; k < seeds.size(); ++k)
-        for (int j = 0; j < 4; ++j) planes_out[k * 4 + j] = planes[(size_t)seeds[k] * 4 + j];
-    *n_planes = (int)seeds.size();
-    return 0;
-}
-
-// ---- ORB features ----
-namespace {
-struct OrbLayout {
-    int n_levels = 0;
-    int w[kOrbLevels], h[kOrbLevels], n[kOrbLevels];
-    double s[kOrbLevels];
-};
-// Level sizes, scales and quotas (S20): doubles and rint only, no libm transcendentals.
-void orb_layout(int width, int height, int nfeatures, OrbLayout &L) {
-    L = OrbLayout();
-    double s = 1.0;
-    bool built = true;
-    for (int l = 0; l < kOrbLevels; ++l) {
-        L.s[l] = s;
-        L.w[l] = (int)std::nearbyint((double)width / s);
-        L.h[l] = (int)std::nearbyint((double)height / s);
-        built = built && L.w[l] >= 2 * kOrbEdge + 1 && L.h[l] >= 2 * kOrbEdge + 1;
-        if (built) L.n_levels = l + 1;
-        s *= 1.2;
-    }
-    const double f = 1.0 / 1.2;
-    double f8 = 1.0;
-    for (int l = 0; l < kOrbLevels; ++l) f8 *= f;
-    double nd = (double)nfeatures * (1.0 - f) / (1.0 - f8);
-    int sum = 0;
-    for (int l = 0; l < kOrbLevels - 1; ++l) {
-        L.n[l] = std::min((int)std::nearbyint(nd), nfeatures - sum);
-        sum += L.n[l];
-        nd *= f;
-    }
-    L.n[kOrbLevels - 1] = nfeatures - sum;
-}
-uint64_t orb_mix(uint64_t z) {   // S17's splitmix64 finaliser
-    z += 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-int orb_rnd20(long long v) { return (int)(v < 0 ? -((-v + (1LL << 19)) >> 20) : ((v + (1LL << 19)) >> 20)); }
-// The 256 pairs (S20: stream(0, 3, i, attempt, 0), 16 draws, index rule of S17) steered to the 30 bins: [30][256] char4.
-void orb_steered_pattern(std::vector<char4> &out) {
-    static const int kSteer[15][2] = {{1048576, 0}, {1025662, 218011}, {957922, 426494}, {848316, 616338}, {701634, 779244},
-                                      {524288, 908093}, {324028, 997255}, {109606, 1042832}, {-109606, 1042832}, {-324028, 997255},
-                                      {-524288, 908093}, {-701634, 779244}, {-848316, 616338}, {-957922, 426494}, {-1025662, 218011}};
-    int pat[256][4];
-    for (uint64_t i = 0; i < 256; ++i)
-        for (uint64_t a = 0;; ++a) {
-            const uint64_t st = orb_mix(orb_mix(orb_mix(orb_mix(0 ^ 3) ^ i) ^ a) ^ 0);
-            int v[4];
-            for (int t = 0; t < 4; ++t) {
-                int sum = 0;
-                for (int d = 0; d < 4; ++d) sum += (int)(((orb_mix(st + (uint64_t)(4 * t + d)) >> 32) * 27ull) >> 32);
-                v[t] = (sum + 2) / 4 - 13;
-            }
-            if (v[0] != v[2] || v[1] != v[3]) {
-                for (int t = 0; t < 4; ++t) pat[i][t] = v[t];
-                break;
-            }
-        }
-    out.assign(30 * 256, char4());
-    for (int k = 0; k < 30; ++k) {
-        const long long C = k < 15 ? kSteer[k][0] : -kSteer[k - 15][0], S = k < 15 ? kSteer[k][1] : -kSteer[k - 15][1];
-        for (int i = 0; i < 256; ++i) {
-            int r[4];
-            for (int t = 0; t < 4; t += 2) {
-                const long long x = pat[i][t], y = pat[i][t + 1];
-                r[t] = orb_rnd20(x * C - y * S);
-                r[t + 1] = orb_rnd20(x * S + y * C);
-            }
-            out[k * 256 + i] = make_char4((signed char)r[0], (signed char)r[1], (signed char)r[2], (signed char)r[3]);
-        }
-    }
-}
-int orb_cap(int w, int h) {   // strict NMS: at most one survivor per 2x2 block of the candidate region
-    const int iw = w - 2 * kOrbEdge, ih = h - 2 * kOrbEdge;
-    return (iw > 0 && ih > 0) ? ((iw + 1) / 2) * ((ih + 1) / 2) : 0;
-}
-}  // namespace
-
-struct cart_orb : DeviceObject {
-    using DeviceObject::DeviceObject;
-    int max_w = 0, max_h = 0, nfeatures = 0;
-    size_t pyr_off[kOrbLevels] = {}, cand_off[kOrbLevels] = {};
-    int cap[kOrbLevels] = {};
-    size_t pyr_stride = 0, cand_stride = 0;
-    uint8_t *pyr = nullptr;        // [2][pyr_stride]
-    OrbCand *cand = nullptr;       // [2][cand_stride]
-    int32_t *cand_cnt = nullptr;   // [2][8]
-    OrbCand *sel = nullptr;        // [2][nfeatures]
-    int4 *kpi = nullptr;           // [2][nfeatures] (x_l, y_l, level, response bits)
-    char4 *pattern = nullptr;      // [30][256]
-    OrbLayout last;                // of the last detect call
-    int last_images = 0;
-};
-
-int cart_orb_levels(int width, int height, int nfeatures, int *level_w, int *level_h, int *level_n) {
-    if (width < 1 || height < 1 || width > 16384 || height > 16384) return fail("width / height must be in [1, 16384]");
-    if (nfeatures < 1 || nfeatures > CART_ORB_MAX_FEATURES) return fail("nfeatures must be in [1, 65536]");
-    OrbLayout L;
-    orb_layout(width, height, nfeatures, L);
-    for (int l = 0; l < kOrbLevels; ++l) {
-        if (level_w) level_w[l] = L.w[l];
-        if (level_h) level_h[l] = L.h[l];
-        if (level_n) level_n[l] = L.n[l];
-    }
-    return L.n_levels;
-}
-
-int cart_orb_create(cart_engine *e, int max_width, int max_height, int nfeatures, cart_orb **out) {
-    if (!e || !out) return fail("bad arguments");
-    if (max_width < 1 || max_height < 1 || max_width > 16384 || max_height > 16384) return fail("max_width / max_height must be in [1, 16384]");
-    if (nfeatures < 1 || nfeatures > CART_ORB_MAX_FEATURES) return fail("nfeatures must be in [1, 65536]");
-    HIP_TRY(hipSetDevice(e->params.device_id));
-    cart_orb *o = new (std::nothrow) cart_orb(e);
-    if (!o) return fail("out of host memory");
-    o->max_w = max_width; o->max_h = max_height; o->nfeatures = nfeatures;
-    OrbLayout L;
-    orb_layout(max_width, max_height, nfeatures, L);
-    for (int l = 0; l < L.n_levels; ++l) {   // sizes only shrink with the image, so the create-size layout holds every call
-        o->pyr_off[l] = o->pyr_stride;
-        o->pyr_stride += ((size_t)L.w[l] * L.h[l] + 255) & ~(size_t)255;
-        o->cap[l] = orb_cap(L.w[l], L.h[l]);
-        o->cand_off[l] = o->cand_stride;
-        o->cand_stride += (size_t)o->cap[l];
-    }
-    std::vector<char4> pat;
-    orb_steered_pattern(pat);
-    if (o->alloc(&o->pyr, 2 * o->pyr_stride) || o->alloc(&o->cand, 2 * o->cand_stride * sizeof(OrbCand)) ||   // both 0 when no level is built
-        o->alloc(&o->cand_cnt, 2 * kOrbLevels * 4) || o->alloc(&o->sel, 2 * (size_t)nfeatures * sizeof(OrbCand)) ||
-        o->alloc(&o->kpi, 2 * (size_t)nfeatures * sizeof(int4)) || o->alloc(&o->pattern, pat.size() * sizeof(char4)) ||
-        hipMemcpy(o->pattern, pat.data(), pat.size() * sizeof(char4), hipMemcpyHostToDevice) != hipSuccess || o->create_event()) {
-        destroy_object(o);
-        return fail("allocating the ORB workspaces failed");
-    }
-    *out = o;
-    return 0;
-}
-
-void cart_orb_destroy(cart_orb *o) { destroy_object(o); }
-
-int cart_orb_detect(cart_orb *o, int n_images, const uint8_t *const *images, const size_t *steps, int channels, int width, int height,
-                    cart_keypoint *const *keypoints, uint8_t *const *descriptors, const size_t *descriptor_steps, int32_t *counts, void *stream_) {
-    if (!o) return fail("orb is NULL");
-    if (n_images != 1 && n_images != 2) return fail("n_images must be 1 or 2");
-    if (!images || !steps || !keypoints || !descriptors || !counts) return fail("NULL pointer");
-    if (channels != 1 && channels != 3) return fail("channels must be 1 or 3");
-    if (width < 1 || height < 1 || width > o->max_w || height > o->max_h) return fail("image size outside [1, create size]");
-    OrbOut out;
-    std::memset(&out, 0, sizeof(out));
-    out.channels = channels;
-    out.counts = counts;
-    for (int i = 0; i < n_images; ++i) {
-        if (!images[i] || !keypoints[i] || !descriptors[i]) return fail("NULL image / output pointer");
-        if (steps[i] < (size_t)width * channels) return fail("bad step");
-        if (reinterpret_cast<uintptr_t>(keypoints[i]) & 3) return fail("keypoints must be 4-byte aligned");
-        out.src[i] = images[i]; out.src_step[i] = steps[i];
-        out.kp[i] = keypoints[i]; out.desc[i] = descriptors[i];
-        out.desc_step[i] = descriptor_steps ? descriptor_steps[i] : CART_ORB_DESCRIPTOR_BYTES;
-        if (out.desc_step[i] < CART_ORB_DESCRIPTOR_BYTES) return fail("descriptor step must be >= 32");
-    }
-    OrbLayout L;
-    orb_layout(width, height, o->nfeatures, L);
-    OrbPlan p;
-    std::memset(&p, 0, sizeof(p));
-    p.n_images = n_images; p.n_levels = L.n_levels; p.nfeatures = o->nfeatures;
-    p.pyr_stride = o->pyr_stride; p.cand_stride = o->cand_stride;
-    for (int l = 0; l < L.n_levels; ++l) {
-        OrbLevel &v = p.lev[l];
-        v.w = L.w[l]; v.h = L.h[l];
-        v.tiles_x = (L.w[l] - 2 * kOrbEdge + kOrbTileW - 1) / kOrbTileW;
-        v.tile0 = p.total_tiles;
-        p.total_tiles += v.tiles_x * ((L.h[l] - 2 * kOrbEdge + kOrbTileH - 1) / kOrbTileH);
-        v.quota = L.n[l];
-        v.cap = o->cap[l];
-        v.pyr_off = o->pyr_off[l]; v.cand_off = o->cand_off[l];
-        if (l > 0) {
-            v.fx = (float)((double)L.w[l - 1] / (double)L.w[l]);
-            v.fy = (float)((double)L.h[l - 1] / (double)L.h[l]);
-        }
-        v.scale = (float)L.s[l];
-    }
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    ObjectCall call(*o, stream);
-    if (call.begin()) return -1;
-    o->last = L;
-    o->last_images = n_images;
-    if (L.n_levels == 0) {   // no level is large enough: no keypoints
-        HIP_TRY(hipMemsetAsync(counts, 0, (size_t)n_images * 4, stream));
-        return 0;
-    }
-    for (int l = 0; l < L.n_levels; ++l) launch_orb_pyramid_level(p, l, out, o->pyr, stream);
-    HIP_TRY(hipMemsetAsync(o->cand_cnt, 0, 2 * kOrbLevels * 4, stream));
-    launch_orb_detect(p, o->pyr, o->cand, o->cand_cnt, stream);
-    launch_orb_select(p, o->cand, o->cand_cnt, o->sel, o->kpi, counts, stream);
-    launch_orb_describe(p, o->pyr, o->kpi, o->pattern, out, stream);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-int cart_orb_debug_level(cart_orb *o, int image, int level, uint8_t *dst, size_t dst_step, int32_t *n_candidates, void *stream_) {
-    if (!o) return fail("orb is NULL");
-    if (image < 0 || image >= o->last_images) return fail("image not part of the last detect call");
-    if (level < 0 || level >= o->last.n_levels) return fail("level not built by the last detect call");
-    const int w = o->last.w[level], h = o->last.h[level];
-    if (dst && dst_step < (size_t)w) return fail("bad step");
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    ObjectCall call(*o, stream);
-    if (call.begin()) return -1;
-    if (dst) HIP_TRY(hipMemcpy2DAsync(dst, dst_step, o->pyr + (size_t)image * o->pyr_stride + o->pyr_off[level], (size_t)w, (size_t)w, (size_t)h,
-                                      hipMemcpyDeviceToDevice, stream));
-    if (n_candidates) {
-        HIP_TRY(hipMemcpyAsync(n_candidates, o->cand_cnt + image * kOrbLevels + level, 4, hipMemcpyDeviceToHost, stream));
-        HIP_TRY(hipStreamSynchronize(stream));
-    }
-    return 0;
-}
-
-// ---- optical flow (oracle S15) ----
-int cart_optical_flow(cart_engine *e, const uint8_t *cur, size_t cur_step, const uint8_t *prev, size_t prev_step, int channels,
-                      int radius, int block, int16_t *flow, size_t flow_step, void *stream_) {
-    if (!e) return fail("engine is NULL");
-    if (!cur || !prev || !flow) return fail("NULL image pointer");
-    if (channels != 1 && channels != 3) return fail("channels must be 1 (gray) or 3 (BGR)");
-    if (radius < 1 || radius > 16) return fail("radius must be in [1, 16]");
-    if (block < 1 || block > 3) return fail("block must be in [1, 3]");
-    const Geometry &g = e->g;
-    if (cur_step < (size_t)g.w * channels || prev_step < (size_t)g.w * channels) return fail("input step smaller than a row");
-    if (flow_step < (size_t)g.w * 4 || (flow_step & 3) || (reinterpret_cast<uintptr_t>(flow) & 3)) return fail("bad step");
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    HIP_TRY(hipSetDevice(e->params.device_id));
-    const size_t cen_bytes = g.census_elems * sizeof(uint32_t);
-    const size_t ws_bytes = ((2 * g.npx + 255) & ~(size_t)255) + 2 * cen_bytes + g.npx * sizeof(uint32_t);
-    {
-        std::lock_guard<std::mutex> lk(e->mu);
-        if (!e->flow_ws) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&e->flow_ws), e->slots.size() * ws_bytes));
-    }
-    Lease l;
-    if (acquire(e, 1, stream, &l)) return -1;
-    uint8_t *ws = e->flow_ws + (size_t)l.s0 * ws_bytes;
-    uint8_t *gray_c = ws, *gray_p = ws + g.npx;
-    uint32_t *cen_c = reinterpret_cast<uint32_t *>(ws + ((2 * g.npx + 255) & ~(size_t)255));
-    uint32_t *cen_p = cen_c + g.census_elems;
-    uint32_t *scratch = cen_p + g.census_elems;   // census_kernel also resets a right-view plane: unused here
-    const ImageBatch cb = strided_images(cur, cur_step, 0), pb = strided_images(prev, prev_step, 0);
-    launch_census(cb, pb, channels, 1, gray_c, gray_p, cen_c, cen_p, scratch, g, stream);
-    launch_block_flow(cen_c, cen_p, g, radius, block, flow, flow_step, stream);
-    hipError_t err = hipGetLastError();
-    release(l);
-    if (err != hipSuccess) return fail(std::string("kernel launch failed: ") + hipGetErrorString(err));
-    return 0;
-}
-
-int cart_resize_linear(int device_id, const uint8_t *src, size_t src_step, int sw, int sh, int channels, uint8_t *dst, size_t dst_step, int dw,
-                       int dh, void *stream_) {
-    if (!src || !dst) return fail("NULL image pointer");
-    if (channels != 1 && channels != 3) return fail("channels must be 1 or 3");
-    if (sw < 1 || sh < 1 || dw < 1 || dh < 1 || sw > 16384 || sh > 16384 || dw > 16384 || dh > 16384) return fail("unsupported image size");
-    if (src_step < (size_t)sw * channels || dst_step < (size_t)dw * channels) return fail("step smaller than a row");
-    HIP_TRY(hipSetDevice(device_id));
-    launch_resize_linear(src, src_step, sw, sh, channels, dst, dst_step, dw, dh, static_cast<hipStream_t>(stream_));
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-int cart_copy_narrow(cart_engine *e, void *dst, const void *src, size_t bytes, int workgroups, void *stream_) {
-    if (!e) return fail("engine is NULL");
-    if (!dst || !src) return fail("NULL pointer");
-    if ((reinterpret_cast<uintptr_t>(dst) | reinterpret_cast<uintptr_t>(src)) & 15) return fail("buffers must be 16-byte aligned");
-    if (workgroups < 0 || workgroups > 1024) return fail("workgroups must be in [0, 1024]");
-    if (bytes == 0) return 0;
-    HIP_TRY(hipSetDevice(e->params.device_id));
-    launch_narrow_copy(src, dst, bytes, workgroups ? workgroups : 8, static_cast<hipStream_t>(stream_));
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-// ---- host-side peak finder (replaces src/utils/peaks.cpp:12-72 and planeseg.cu:405-458) ----
-int cart_find_peaks(const int32_t *data, int n, int *born, int *died, int *left, int *right) {
-    if (!data || n <= 0 || !born || !died || !left || !right) return fail("bad arguments");
-    try {
-    std::vector<int> order(n), owner(n, -1);
-    for (int i = 0; i < n; ++i) order[i] = i;
-    // descending value, ties by ascending index (oracle S11; the reference's std::sort leaves ties open)
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return data[a] > data[b]; });
-    int np = 0;
-    for (int idx : order) {
-        const int il = (idx > 0) ? owner[idx - 1] : -1;
-        const int ir = (idx < n - 1) ? owner[idx + 1] : -1;
-        if (il < 0 && ir < 0) {  // a new component is born at a local maximum
-            born[np] = left[np] = right[np] = idx; died[np] = -1;
-            owner[idx] = np++;
-        } else if (il >= 0 && ir < 0) {
-            right[il] += 1; owner[idx] = il;
-        } else if (il < 0 && ir >= 0) {
-            left[ir] -= 1; owner[idx] = ir;
-        } else if (data[born[il]] > data[born[ir]]) {  // the younger (lower) peak dies at this saddle
-            died[ir] = idx; right[il] = right[ir];
-            owner[right[il]] = owner[idx] = il;
-        } else {
-            died[il] = idx; left[ir] = left[il];
-            owner[left[ir]] = owner[idx] = ir;
-        }
-    }
-    std::vector<int> perm(np);
-    for (int i = 0; i < np; ++i) perm[i] = i;
-    auto persistence = [&](int k) -> long long { return died[k] < 0 ? (long long)INT32_MAX : (long long)data[born[k]] - data[died[k]]; };
-    std::stable_sort(perm.begin(), perm.end(), [&](int a, int b) { return persistence(a) > persistence(b); });
-    std::vector<int> b2(np), d2(np), l2(np), r2(np);
-    for (int i = 0; i < np; ++i) { b2[i] = born[perm[i]]; d2[i] = died[perm[i]]; l2[i] = left[perm[i]]; r2[i] = right[perm[i]]; }
-    for (int i = 0; i < np; ++i) { born[i] = b2[i]; died[i] = d2[i]; left[i] = l2[i]; right[i] = r2[i]; }
-    return np;
-    } catch (const std::bad_alloc &) { return fail("out of host memory"); }   // nothing is thrown across the C ABI
-}
-
-int cart_find_plane_params(const int32_t hist[256], cart_plane_params *io) {
-    if (!hist || !io) return fail("bad arguments");
-    int born[256], died[256], left[256], right[256];
-    const int np = cart_find_peaks(hist, 256, born, died, left, right);
-    if (np < 2) return 0;  // planeseg.cu:408-411
-    int pv = born[0], ph = born[1];
-    if (std::abs(pv - 128) > std::abs(ph - 128)) std::swap(pv, ph);  // vertical = nearer to zero derivative (:414-416)
-    io->vertical_center = pv - 128;
-    io->horizontal_center = ph - 128;
-    int valley = std::min(pv, ph);
-    for (int i = valley; i < std::max(pv, ph); ++i)
-        if (hist[i] < hist[valley]) valley = i;  // :422-428
-    const int vdist = std::abs(valley - pv), hdist = std::abs(valley - ph);
-    if (vdist == 0 || hdist == 0) return 0;  // :436-439
-    const int vslope = (hist[pv] - hist[valley]) / vdist, hslope = (hist[ph] - hist[valley]) / hdist;
-    if (vslope == 0 || hslope == 0) return 0;  // :444-447
-    const int vwidth = hist[pv] / vslope, hwidth = hist[ph] / hslope;
-    io->vertical_min = pv - vwidth - 128; io->vertical_max = valley - 127;      // :452
-    io->horizontal_min = valley - 127; io->horizontal_max = ph + hwidth - 127;  // :453
-    return 1;
-}
-
 int cart_debug_slab_layout(cart_engine *e, int *group_slots, int *n_groups, size_t *slot_bytes, size_t *group_bytes) {
     if (!e) return fail("engine is NULL");
     if (e->post_only) return fail("this engine was created without SGM workspaces (num_disparities = 0)");
@@ -1974,7 +775,7 @@ int cart_debug_ccl_scratch_nonzero(cart_engine *e, size_t *nonzero) {
     HIP_TRY(hipSetDevice(e->params.device_id));
     HIP_TRY(hipDeviceSynchronize());
     try {
-        const size_t per_slot = e->g.npx * 5;   // the statistics scratch of one slot (the segment counts behind it are overwritten, not accumulated)
+        const size_t per_slot = e->g.npx * kCclStatInts;   // the statistics scratch of one slot (the segment counts behind it are overwritten, not accumulated)
         std::vector<int32_t> host(per_slot);
         for (size_t sl = 0; sl < e->slots.size(); ++sl) {
             HIP_TRY(hipMemcpy(host.data(), e->ccl_stats_ws + sl * per_slot, per_slot * sizeof(int32_t), hipMemcpyDeviceToHost));

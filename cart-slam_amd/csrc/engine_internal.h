@@ -38,7 +38,7 @@ struct DirDesc {
 };
 
 // Where the cost slabs of the frames of ONE launch live: frame f's P path slabs are frame[f] + path * slab_bytes, each [h][w][D].
-// The slab workspace is a set of separate device allocations of at most 8 GiB (cart_engine.hip, SlabPool), so the frames of a
+// The slab workspace is a set of separate device allocations of at most 8 GiB (engine_host.h, SlabPool), so the frames of a
 // launch need not be one address range; every SGM kernel takes this table by value (wave-uniform index: one scalar load).
 constexpr int kMaxLaunchFrames = 64;   // upper bound of CART_OPT_CHUNK_FRAMES
 struct SlabTable { uint8_t *frame[kMaxLaunchFrames]; };
@@ -127,6 +127,7 @@ void launch_ccl(const uint8_t *planes, size_t pstep, size_t pfs, int32_t *work, 
 // component table (S12) of a given id map
 void launch_ccl_stats(const uint8_t *planes, size_t pstep, size_t pfs, const int32_t *ids, size_t istep, size_t ifs, int32_t *stat, int32_t *seg,
                       cart_component *table, int max_components, int32_t *ncomp, int w, int h, int n_frames, hipStream_t s);
+constexpr int kCclStatInts = 5;   // int32 fields of one component's entry in the statistics scratch
 size_t ccl_stats_ws_ints(int w, int h);   // int32 elements of the table workspace per slot: scratch + segment counts
 
 void launch_classify_dev(const int16_t *deriv, size_t step, size_t fs, const cart_plane_params *params_dev, int params_stride,

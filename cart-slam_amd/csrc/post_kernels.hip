@@ -583,7 +583,6 @@ __global__ __launch_bounds__(256) void ccl_border_kernel(const uint8_t *planes, 
 // -- no pass over the id map: it only opens the 64-pixel segments that hold a root -- moves every root's scratch entry into its
 // table row and ZEROES the entry again.  The scratch ([slot][npx] x 5 ints, zero-neutral encoding: area, w - x0, h - y0, x1 + 1,
 // y1 + 1, every field grown by atomicAdd / atomicMax from 0) is therefore all zeros between calls: no memset, no initialised table.
-constexpr int kCclStatInts = 5;
 constexpr int kCclHash = 256;   // entries of a tile's component hash (a tile with more components than fit adds their pieces to the scratch directly)
 struct CclHash { int key[kCclHash], area[kCclHash], x0[kCclHash], y0[kCclHash], x1[kCclHash], y1[kCclHash]; };
 

@@ -52,7 +52,7 @@ def report(v):
         for bit, (opt, var, what) in OPTIONS.items():
             if v["best"] & bit:
                 lines.append(f"  cart_engine_set_option(engine, {opt}, 1);   oracle: variants |= {var}   ({what})")
-        lines.append("  to make them the defaults: `opt_spec`'s initial value in cart-slam_amd/csrc/cart_engine.hip (struct cart_engine), the default `variants` in "
+        lines.append("  to make them the defaults: `opt_spec`'s initial value in cart-slam_amd/csrc/engine_host.h (struct cart_engine), the default `variants` in "
                      "oracle/cart_oracle.c::cart_oracle_sgm and in tests/oracle_lib.py; then python tests/golden/make_golden.py and both test suites")
         return lines, 3
     worst_case = max(v["per_case"], key=lambda c: v["per_case"][c][v["best"]])
