@@ -32,8 +32,9 @@ class LaunchPlan(C.Structure):
     _fields_ = [("frames_per_launch", C.c_int), ("plan", C.c_int), ("slabs_written", C.c_int)]
 
 
-PLAN_AUTO, PLAN_SLABS, PLAN_FUSED_UP = -1, 0, 1      # CART_PLAN_*
+PLAN_AUTO, PLAN_SLABS, PLAN_FUSED_UP, PLAN_BAND_UP = -1, 0, 1, 2      # CART_PLAN_*
 OPT_PLAN, OPT_PLAN_MIN_FRAMES, OPT_CHUNK_FRAMES = 0, 1, 2           # CART_OPT_*
+OPT_BAND_ROWS, OPT_BAND_PROBE = 6, 7
 OPT_SPEC_S8_ZERO_INVALID, OPT_SPEC_S7_REPLICATE_BORDER, OPT_SPEC_S5_TOP2 = 3, 4, 5   # CART_OPT_SPEC_*: upstream variants of oracle S8 / S7 / S5
 
 

@@ -79,8 +79,8 @@ class Engine:
 
     # ---- launch plan (every plan gives the same bits; include/cart_engine.h CART_PLAN_*) ----
     def set_plan(self, plan, min_frames=1):
-        """plan: "auto" | "slabs" | "fused_up"; a forced plan applies to launches of >= min_frames frames."""
-        code = {"auto": _lib.PLAN_AUTO, "slabs": _lib.PLAN_SLABS, "fused_up": _lib.PLAN_FUSED_UP}[plan]
+        """plan: "auto" | "slabs" | "fused_up" | "band_up"; a forced plan applies to launches of >= min_frames frames."""
+        code = {"auto": _lib.PLAN_AUTO, "slabs": _lib.PLAN_SLABS, "fused_up": _lib.PLAN_FUSED_UP, "band_up": _lib.PLAN_BAND_UP}[plan]
         self._check(self._lib.cart_engine_set_option(self._h, _lib.OPT_PLAN, code), "cart_engine_set_option")
         self._check(self._lib.cart_engine_set_option(self._h, _lib.OPT_PLAN_MIN_FRAMES, int(min_frames)), "cart_engine_set_option")
 
@@ -90,6 +90,12 @@ class Engine:
         self._check(self._lib.cart_engine_set_option(self._h, _lib.OPT_SPEC_S8_ZERO_INVALID, 1 if s8_zero_invalid else 0), "cart_engine_set_option")
         self._check(self._lib.cart_engine_set_option(self._h, _lib.OPT_SPEC_S7_REPLICATE_BORDER, 1 if s7_replicate_border else 0), "cart_engine_set_option")
 
+    def set_band_rows(self, k, probe=False):
+        """K of plan "band_up" (4, 8 or 16 rows per band).  probe: measurement only -- the plan then stores and reads all P slabs and
+        recomputes nothing (K = 1 allowed), which times the banded tile's read pattern against the two-kernel WTA's."""
+        self._check(self._lib.cart_engine_set_option(self._h, _lib.OPT_BAND_ROWS, int(k)), "cart_engine_set_option")
+        self._check(self._lib.cart_engine_set_option(self._h, _lib.OPT_BAND_PROBE, 1 if probe else 0), "cart_engine_set_option")
+
     def set_chunk_frames(self, n):
         self._check(self._lib.cart_engine_set_option(self._h, _lib.OPT_CHUNK_FRAMES, int(n)), "cart_engine_set_option")
 
@@ -97,7 +103,7 @@ class Engine:
         """-> dict(frames_per_launch, plan, slabs_written) of a batched call of n_frames."""
         lp = _lib.LaunchPlan()
         self._check(self._lib.cart_engine_describe_plan(self._h, int(n_frames), C.byref(lp)), "cart_engine_describe_plan")
-        return {"frames_per_launch": lp.frames_per_launch, "plan": {0: "slabs", 1: "fused_up"}[lp.plan],
+        return {"frames_per_launch": lp.frames_per_launch, "plan": {0: "slabs", 1: "fused_up", 2: "band_up"}[lp.plan],
                 "slabs_written": lp.slabs_written}
 
     def copy_narrow(self, dst, src, workgroups=0):

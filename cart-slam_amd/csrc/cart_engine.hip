@@ -136,14 +136,23 @@ struct Options {
     int plan, plan_min_frames, chunk_frames;
     bool timing;
     int spec;
+    int band_rows;
+    bool band_probe;
 };
-Options snapshot_options(const cart_engine *e) { return Options{e->opt_plan, e->opt_plan_min_frames, e->chunk_frames, e->timing, e->opt_spec}; }   // caller holds e->mu
+Options snapshot_options(const cart_engine *e) {   // caller holds e->mu
+    return Options{e->opt_plan, e->opt_plan_min_frames, e->chunk_frames, e->timing, e->opt_spec, e->opt_band_rows, e->opt_band_probe != 0};
+}
 
 // The launch plan of `n` frames handed to one launch sequence (include/cart_engine.h, CART_PLAN_*).
 int plan_for(const cart_engine *e, const Options &o, int n) {
     if (o.spec & 4) return CART_PLAN_SLABS;   // the S5 variant exists in the two-kernel WTA only
-    if (o.plan == CART_PLAN_AUTO) return n >= e->auto_fused_min_frames ? CART_PLAN_FUSED_UP : CART_PLAN_SLABS;
+    const bool band_ok = wta_band_supported(e->g, o.band_rows, o.band_probe);
+    if (o.plan == CART_PLAN_AUTO) {
+        if (band_ok && !o.band_probe && n >= e->auto_band_min_frames) return CART_PLAN_BAND_UP;
+        return n >= e->auto_fused_min_frames ? CART_PLAN_FUSED_UP : CART_PLAN_SLABS;
+    }
     if (n < o.plan_min_frames) return CART_PLAN_SLABS;
+    if (o.plan == CART_PLAN_BAND_UP && !band_ok) return CART_PLAN_SLABS;   // the banded WTA exists for D = 128 with 8 paths
     return o.plan;
 }
 
@@ -248,12 +257,15 @@ void launch_agg_wta(cart_engine *e, const Options &opt, const SlabTable &slabs, 
     uint32_t *cl = e->cen_l + s0 * g.census_elems, *cr = e->cen_r + s0 * g.census_elems;
     uint16_t *wl = e->wta_l + s0 * g.npx;
     uint32_t *rpk = e->right_pk + s0 * g.npx;
-    const bool fused = plan_for(e, opt, n) == CART_PLAN_FUSED_UP && e->rv_partial;
+    const int plan = plan_for(e, opt, n);
+    const bool fused = plan == CART_PLAN_FUSED_UP && e->rv_partial, band = plan == CART_PLAN_BAND_UP;
     AggArgs a = fused ? e->agg_fused : e->agg;
     a.cen_l = cl; a.cen_r = cr; a.slabs = slabs;
+    a.ckpt_rows = band && !opt.band_probe ? opt.band_rows : 0;   // the "up" scan stores its checkpoint rows only
     launch_aggregate(a, n, st);
     between();
-    if (fused) launch_wta_fused(cl, cr, slabs, wl, rpk, e->rv_partial + s0 * wta_fused_partial_elems(g), g, e->uniq_thr, n, st);
+    if (band) launch_wta_band(cl, cr, slabs, wl, rpk, g, e->uniq_thr, n, opt.band_rows, opt.band_probe, st);
+    else if (fused) launch_wta_fused(cl, cr, slabs, wl, rpk, e->rv_partial + s0 * wta_fused_partial_elems(g), g, e->uniq_thr, n, st);
     else launch_wta(slabs, wl, rpk, g, e->uniq_thr, n, st, (opt.spec & 4) != 0);
 }
 
@@ -345,6 +357,9 @@ int cart_engine_create(const cart_engine_params *params, cart_engine **out) {
         const int nblk = (g.w + 15) / 16;
         e->auto_fused_min_frames = g.D >= 256 ? std::max(2, (448 + nblk - 1) / nblk) : 1 << 30;
     }
+    // Banded WTA with the "up" path recomputed from checkpoint rows: D = 128 with 8 paths, launches of at least kBandAutoMinFrames frames
+    // (engine_host.h: the measured basis is in DESIGN.md 4.1)
+    e->auto_band_min_frames = wta_band_supported(g, kBandRowsDefault, false) ? kBandAutoMinFrames : 1 << 30;
     *out = e;
     return 0;
 }
@@ -377,7 +392,7 @@ int cart_engine_set_option(cart_engine *e, int option, int value) {
     std::lock_guard<std::mutex> lk(e->mu);
     switch (option) {
         case CART_OPT_PLAN:
-            if (value < CART_PLAN_AUTO || value > CART_PLAN_FUSED_UP) return fail("unknown plan");
+            if (value < CART_PLAN_AUTO || value > CART_PLAN_BAND_UP) return fail("unknown plan");
             e->opt_plan = value;
             return 0;
         case CART_OPT_PLAN_MIN_FRAMES:
@@ -387,6 +402,14 @@ int cart_engine_set_option(cart_engine *e, int option, int value) {
         case CART_OPT_CHUNK_FRAMES:
             if (value < 1 || value > kMaxLaunchFrames) return fail("chunk frames must be in [1, 64]");   // 64 = entries of the per-launch slab table (SlabTable); pointer-table (multi) calls stay at kLaunchFrames
             e->chunk_frames = value;
+            return 0;
+        case CART_OPT_BAND_ROWS:
+            if (value != 1 && value != 4 && value != 8 && value != 16) return fail("band rows must be 4, 8 or 16 (1 with the probe)");
+            e->opt_band_rows = value;
+            return 0;
+        case CART_OPT_BAND_PROBE:
+            if (value != 0 && value != 1) return fail("the band probe is 0 or 1");
+            e->opt_band_probe = value;
             return 0;
         case CART_OPT_SPEC_S8_ZERO_INVALID:
         case CART_OPT_SPEC_S7_REPLICATE_BORDER:
@@ -407,6 +430,8 @@ int cart_engine_get_option(cart_engine *e, int option, int *value) {
         case CART_OPT_PLAN: *value = e->opt_plan; return 0;
         case CART_OPT_PLAN_MIN_FRAMES: *value = e->opt_plan_min_frames; return 0;
         case CART_OPT_CHUNK_FRAMES: *value = e->chunk_frames; return 0;
+        case CART_OPT_BAND_ROWS: *value = e->opt_band_rows; return 0;
+        case CART_OPT_BAND_PROBE: *value = e->opt_band_probe; return 0;
         case CART_OPT_SPEC_S8_ZERO_INVALID: *value = (e->opt_spec & 1) ? 1 : 0; return 0;
         case CART_OPT_SPEC_S7_REPLICATE_BORDER: *value = (e->opt_spec & 2) ? 1 : 0; return 0;
         case CART_OPT_SPEC_S5_TOP2: *value = (e->opt_spec & 4) ? 1 : 0; return 0;
@@ -422,7 +447,8 @@ int cart_engine_describe_plan(cart_engine *e, int n_frames, cart_launch_plan *ou
     const Options o = snapshot_options(e);
     out->frames_per_launch = std::min(n_frames, o.chunk_frames);
     out->plan = plan_for(e, o, out->frames_per_launch);
-    out->slabs_written = out->plan == CART_PLAN_FUSED_UP ? e->g.P - 1 : e->g.P;
+    // (BAND_UP: P - 1 whole slabs + the checkpoint rows, 1/K of one more; the probe stores all P)
+    out->slabs_written = out->plan == CART_PLAN_FUSED_UP || (out->plan == CART_PLAN_BAND_UP && !o.band_probe) ? e->g.P - 1 : e->g.P;
     return 0;
 }
 

@@ -52,6 +52,7 @@ struct AggArgs {
     int n_frames;        // filled by launch_aggregate
     int xcd_frames;      // filled by launch_aggregate: decode the grid per XCD (frames x, x + 8, ... on XCD x)
     int hsplit;          // filled by launch_aggregate: horizontal scans run as producer / consumer wave pairs (2 P rows per workgroup)
+    int ckpt_rows;       // plan BAND_UP: K, the "up" scan stores only the rows y % K == 0, y > 0 (a power of two); 0 = every row of every scan
     DirDesc dirs[kMaxPaths];
 };
 
@@ -95,6 +96,12 @@ constexpr int kFusedUpPath = 1;
 size_t wta_fused_partial_elems(const Geometry &g);  // u32 elements of the per-frame right-view partial buffer
 void launch_wta_fused(const uint32_t *cen_l, const uint32_t *cen_r, const SlabTable &slabs, uint16_t *wta_l, uint32_t *right_pk,
                       uint32_t *partial, const Geometry &g, const uint16_t *thr, int n_frames, hipStream_t s);
+// WTA over bands of K rows that recomputes the "up" path from the checkpoint rows a launch_aggregate with ckpt_rows = K left in slab
+// kFusedUpPath (plan BAND_UP: D = 128, 8 paths, K = 4, 8 or 16)
+// probe: the read-rate probe -- all P slabs are read (the aggregation launch stored every row), nothing is recomputed; K = 1 allowed
+bool wta_band_supported(const Geometry &g, int K, bool probe);
+void launch_wta_band(const uint32_t *cen_l, const uint32_t *cen_r, const SlabTable &slabs, uint16_t *wta_l, uint32_t *right_pk,
+                     const Geometry &g, const uint16_t *thr, int n_frames, int K, bool probe, hipStream_t s);
 void launch_uniq_table(float u, uint16_t *out_dev, hipStream_t s);   // test access to the integer uniqueness threshold
 void uniq_table_host(float u, uint16_t *out);
 void launch_post(const uint16_t *wta_l, const uint32_t *right_pk, const uint8_t *gray_l, const OutBatch &out, const Geometry &g, int n_frames, hipStream_t s,

@@ -322,9 +322,18 @@ __device__ __forceinline__ void agg_xor(const CensusRegs &c, uint32_t (&xr)[16])
     for (int k = 0; k < 16; ++k) xr[k] = c.fl ^ c.r[k];
 }
 
+// min over the pixel's D path costs (split-halves registers), replicated into both halves: the (m,m) operand of the next step
+template <int LPP>
+__device__ __forceinline__ uint32_t path_min(const uint32_t (&n)[8]) {
+    uint32_t x = pk_min(pk_min3(n[0], n[1], n[2]), pk_min3(n[3], n[4], pk_min3(n[5], n[6], n[7])));
+    x = pk_min(x, __builtin_amdgcn_alignbit(x, x, 16));
+    return group_allmin<LPP>(x);
+}
+
+// store_row (wave-uniform): false skips the slab store of this step -- the checkpointed "up" scan of plan BAND_UP
 template <int LPP, bool STORE = true>
 __device__ __forceinline__ void agg_step(uint32_t (&a)[8], uint32_t &mm, const uint32_t (&xr)[16], uint32_t sel_lo,
-                                         uint32_t sel_hi, uint32_t p1p1, uint32_t p2p2, CART_GLOBAL uint8_t *po) {
+                                         uint32_t sel_hi, uint32_t p1p1, uint32_t p2p2, CART_GLOBAL uint8_t *po, bool store_row = true) {
     // Issue cost on gfx950 (profiles/tools/valu_rate.hip): v_add/v_sub/v_xor ~2.7 clk, packed ops / v_perm / v_bcnt /
     // shifts ~4.5 clk.  Wherever a packed op cannot carry or borrow between the halves, the plain 32-bit one is used.
     const uint32_t mp2 = mm + p2p2;  // halves stay < 2^15
@@ -356,14 +365,11 @@ __device__ __forceinline__ void agg_step(uint32_t (&a)[8], uint32_t &mm, const u
         // write-once streaming data: non-temporal so the slabs do not evict the census planes from L2
         typedef uint32_t v4u __attribute__((ext_vector_type(4)));
         const v4u q = {o.x, o.y, o.z, o.w};
-        __builtin_nontemporal_store(q, (CART_GLOBAL v4u *)po);
+        if (store_row) __builtin_nontemporal_store(q, (CART_GLOBAL v4u *)po);
     } else {
-        (void)po;  // the fused WTA consumes the new costs from the registers
+        (void)po; (void)store_row;  // the fused and banded WTA consume the new costs from the registers
     }
-    // min over the pixel's D disparities, replicated into both halves
-    uint32_t x = pk_min(pk_min3(n[0], n[1], n[2]), pk_min3(n[3], n[4], pk_min3(n[5], n[6], n[7])));
-    x = pk_min(x, __builtin_amdgcn_alignbit(x, x, 16));
-    mm = group_allmin<LPP>(x);
+    mm = path_min<LPP>(n);
 #pragma unroll
     for (int i = 0; i < 8; ++i) a[i] = n[i];
 }
@@ -616,7 +622,11 @@ template <int LPP> constexpr int v_depth() { return LPP == 4 ? 4 : 2; }
 constexpr int kAggWaves = 4;   // waves per workgroup: nothing in the kernel is shared between waves (1-2: 1.85 instead of 1.58 ms at the headline; 8: slower but at D=64)
 // HS: the launch runs its horizontal scans as producer / consumer wave pairs (hsplit_*); a separate instantiation, so that the plain launch keeps its
 // 70 VGPRs (7 waves per SIMD) and the split one gets the registers its producer needs without spilling
-template <int LPP, bool HS = false>
+// CKPT: the launch of plan BAND_UP (AggArgs::ckpt_rows = K): the "up" scan runs on every row but stores only the rows y % K == 0, y > 0, in place in
+// its slab -- the state wta_band_kernel restarts from.  A separate instantiation: the scan loop exists twice in it (the store of the "up" waves
+// sits behind a wave-uniform branch, every other direction keeps its unconditional stores and exact counted vmcnt waits), the other plans' kernels
+// are what they were.
+template <int LPP, bool HS = false, bool CKPT = false>
 __global__ __launch_bounds__(64 * kAggWaves, (LPP >= 8 && !HS) ? 6 : 4) void aggregate_kernel(AggArgs a) {
     using WN = Win<LPP>;
     constexpr int P = WN::P;
@@ -803,7 +813,9 @@ __global__ __launch_bounds__(64 * kAggWaves, (LPP >= 8 && !HS) ? 6 : 4) void agg
         }
     };
     ragged(tb, tm0);
-    if (tm0 < tm1) {
+    // ck: this wave's scan stores checkpoint rows only (vertical scans have no ragged steps: every store of the "up" scan is in here)
+    auto scan = [&](auto ck) {
+        constexpr bool CK = decltype(ck)::value;
         const uint32_t *pw = pw_base + tm0 * cstride, *pl = pl_u + tm0 * cstride;
         uint8_t *po = po_u + tm0 * ostride;
         // K register sets of prefetched windows: the loads of step t+K are issued at the start of step t.  vmcnt retires in
@@ -838,7 +850,9 @@ __global__ __launch_bounds__(64 * kAggWaves, (LPP >= 8 && !HS) ? 6 : 4) void agg
             __builtin_amdgcn_sched_barrier(0);
             win_read<LPP>(cur, rbase, ca.r);
             agg_xor(ca, xr);
-            agg_step<LPP>(st, mm, xr, sel_lo, sel_hi, p1p1, p2p2, sgpr(po + J * ostride) + pin_v(lo_o));
+            bool store_row = true;
+            if constexpr (CK) { const int yy = ys + (t + J) * dy; store_row = yy > 0 && (yy & (a.ckpt_rows - 1)) == 0; }   // wave-uniform
+            agg_step<LPP>(st, mm, xr, sel_lo, sel_hi, p1p1, p2p2, sgpr(po + J * ostride) + pin_v(lo_o), store_row);
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int i = 0; i < WN::NLD; ++i) nxt[lslot[i]] = gs[(J + 1) % K][i];   // window of step t+J+1
@@ -865,6 +879,14 @@ __global__ __launch_bounds__(64 * kAggWaves, (LPP >= 8 && !HS) ? 6 : 4) void agg
         if constexpr (K > 4) {
             if (t + 3 < tm1) sub(std::integral_constant<int, 3>{}, std::false_type{});
             if (t + 4 < tm1) sub(std::integral_constant<int, 4>{}, std::false_type{});
+        }
+    };
+    if (tm0 < tm1) {
+        if constexpr (CKPT) {
+            if (a.dirs[di].path == kFusedUpPath) scan(std::true_type{});
+            else scan(std::false_type{});
+        } else {
+            scan(std::false_type{});
         }
     }
     ragged(tm1, te);
@@ -938,6 +960,11 @@ void launch_aggregate(const AggArgs &a_in, int n_frames, hipStream_t s) {
     const size_t static_lds = sizeof(uint32_t) * (kAggWaves * 2 * (lpp == 4 ? Win<4>::BUF : lpp == 8 ? Win<8>::BUF : Win<16>::BUF) + (a.hsplit ? (kAggWaves / 2) * kHsCostDwords : 4));
     // (never more than 64 KB per workgroup in all, the limit that needs no opt-in: two of those per CU are still two)
     const size_t pad = resident ? std::min<size_t>(kLdsPerCu / resident - kLdsGranule, 64 * 1024) - static_lds : 0;
+    if (a.ckpt_rows) {   // plan BAND_UP (D = 128 only: cart_engine.hip, band_plan_ok)
+        if (a.hsplit) hipLaunchKernelGGL((aggregate_kernel<8, true, true>), grid, block, pad, s, a);
+        else hipLaunchKernelGGL((aggregate_kernel<8, false, true>), grid, block, pad, s, a);
+        return;
+    }
     if (a.hsplit) {
         switch (a.g.D) {
             case 64: hipLaunchKernelGGL((aggregate_kernel<4, true>), grid, block, pad, s, a); break;
@@ -1212,6 +1239,224 @@ void launch_wta(const SlabTable &slabs, uint16_t *wta_l, uint32_t *right_pk, con
         case 64: hipLaunchKernelGGL(wta_kernel<4>, grid, block, lds, s, a); break;
         case 128: hipLaunchKernelGGL(wta_kernel<8>, grid, block, lds, s, a); break;
         default: hipLaunchKernelGGL(wta_kernel<16>, grid, block, lds, s, a); break;
+    }
+}
+
+// ------------------------------------------------------------------ winner takes all over row bands, "up" path recomputed (plan BAND_UP)
+// The "up" path of a pixel depends only on the pixel below it, so a tile of 64 columns x K consecutive rows can recompute it in registers from the
+// path's state on the row under the band: the aggregation launch stores that slab only on the rows y % K == 0 (AggArgs::ckpt_rows), and this kernel
+// reads the other P-1 slabs -- 2 (P-1 + 1/K) D slab bytes per pixel and launch pair instead of 2 P D -- with wta_kernel's access structure: short-lived
+// blocks in address order, each reading 8 KB runs of every slab.  Block = 64 columns x the rows [bK, min(h, bK+K)) of one frame, walked bottom to top,
+// 64 LPP threads: one pixel per lane group, wave w on columns P w .. P w + P-1 like a wave of aggregate_kernel, so the right-census window goes through
+// the same wave-private LDS staging (Win / WinLane) and the step is the same agg_step.  Per row
+//   * census window of the row (prefetched a row ahead) -> LDS -> one agg_step<LPP, false>: the row's "up" costs, in registers,
+//   * + the P-1 stored slabs; their loads for row y-1 are issued as soon as row y has been summed, before anything else of row y,
+//   * the row's WTA exactly as wta_kernel (packed keys, uniqueness table, sub-pixel from the LDS sum tile, right view through s_rv).
+// One LDS-only barrier per row (lds_barrier: the prefetched loads stay in flight across it): s_rv alternates between two buffers, the sum tile is only
+// read by the wave that wrote it, and the uniqueness table is copied to LDS so that no load the row has to wait for queues behind the prefetch (vmcnt
+// retires in order).  Columns past the image compute on census padding and the clamped last slab column and write nothing.
+struct BandArgs {
+    const uint32_t *cen_l, *cen_r;
+    SlabTable slabs;
+    uint16_t *wta_l;
+    uint32_t *right_pk;
+    Geometry g;
+    const uint16_t *thr;   // as WtaArgs::thr
+};
+
+// RECOMP = false is the read-rate probe of the design: the same walk over all P stored slabs with no recompute, i.e. wta_kernel's work
+// in K-row tiles (CART_OPT_BAND_PROBE; K = 1 is wta_kernel's tiling).
+template <int LPP, int K, bool RECOMP = true>
+__global__ __launch_bounds__(64 * LPP, 4) void wta_band_kernel(BandArgs a) {
+    using WN = Win<LPP>;
+    typedef uint32_t v4u __attribute__((ext_vector_type(4)));
+    constexpr int D = WN::D, P = WN::P, NT = 64 * LPP, NP = kMaxPaths, NS = RECOMP ? NP - 1 : NP;
+    constexpr int DP = D + 8;                    // LDS pitch of a pixel's sum row (as wta_kernel)
+    constexpr int NRV = kWtaTileX + D;
+    static_assert(P * LPP == 64 && NT / LPP == kWtaTileX, "one pixel of the tile per lane group");
+    __shared__ __attribute__((aligned(16))) uint16_t s_sum[kWtaTileX * DP];
+    __shared__ uint32_t s_rv[2][NRV];
+    __shared__ uint32_t s_win[RECOMP ? LPP : 1][WN::BUF];     // one window buffer per wave
+    __shared__ uint16_t s_thr[2048];
+    const Geometry &g = a.g;
+    keep_f16_denormals();
+    const int x0 = blockIdx.x * kWtaTileX, frame = blockIdx.z;
+    const int y0 = (int)blockIdx.y * K, y1 = min(g.h, y0 + K);   // the band's rows [y0, y1)
+    const int lane = threadIdx.x & 63, wid = uniform((int)(threadIdx.x >> 6));
+    const int gl = lane % LPP, pg = lane / LPP, d0 = gl * 16;
+    const int xl = wid * P + pg, x = x0 + xl;
+    const int xw0 = x0 + wid * P;                // the wave's first column (uniform)
+    const bool valid = x < g.w;
+    const uint32_t p1p1 = (uint32_t)g.p1 * 0x10001u, p2p2 = (uint32_t)g.p2 * 0x10001u;
+    const uint32_t sel_lo = gl == 0 ? 0x05040d0du : 0x05040302u;
+    const uint32_t sel_hi = gl == LPP - 1 ? 0x0d0d0302u : 0x05040302u;
+
+    for (int i = threadIdx.x; i < 2 * NRV; i += NT) (&s_rv[0][0])[i] = 0xffffffffu;
+    for (int i = threadIdx.x; i < 2048; i += NT) s_thr[i] = a.thr[i];
+
+    WinLane<LPP> wlane;
+    wlane.init(lane);
+    unsigned (&goff)[WN::NLD] = wlane.goff;
+    const int (&lslot)[WN::NLD] = wlane.lslot;
+    const int rbase = wlane.rbase;
+    uint32_t *wbuf = &s_win[RECOMP ? wid : 0][0];
+
+    // row-0 bases (wave-uniform, SGPRs) + constant per-lane byte offsets, as wta_fused_kernel
+    const ptrdiff_t cen0 = (ptrdiff_t)frame * (ptrdiff_t)g.census_elems + g.cpadl + xw0;
+    const uint32_t *pw0 = a.cen_r + uniform(cen0 - g.min_disp - (D - 1));
+    const uint32_t *pl0 = a.cen_l + uniform(cen0);
+    unsigned lo_l = (unsigned)pg * 4u;
+    const int xbase = min(xw0, g.w - 1), xc = min(x, g.w - 1);   // xbase <= xc
+    const uint8_t *ps0 = a.slabs.frame[frame] + uniform((ptrdiff_t)xbase * D);
+    unsigned lo_s = (unsigned)((xc - xbase) * D + d0);
+    const ptrdiff_t row_bytes = (ptrdiff_t)g.w * D;
+
+    uint32_t cw[WN::NLD], cfl, sv[NS][4];
+    auto load_census_row = [&](int y) {
+        const uint32_t *pw = pw0 + (ptrdiff_t)y * g.cpitch;
+#pragma unroll
+        for (int i = 0; i < WN::NLD; ++i) cw[i] = ld_u32(pw, goff[i]);
+        cfl = ld_u32(pl0 + (ptrdiff_t)y * g.cpitch, lo_l);
+    };
+    auto load_slab = [&](int y, int p) {
+        const uint8_t *ps = ps0 + (ptrdiff_t)y * row_bytes + (ptrdiff_t)p * (ptrdiff_t)g.slab_bytes;
+        return __builtin_nontemporal_load((const CART_GLOBAL v4u *)((const CART_GLOBAL char *)sgpr(ps) + pin_v(lo_s)));
+    };
+    auto load_slab_row = [&](int y) {
+#pragma unroll
+        for (int p = 0; p < NP; ++p) {
+            if (RECOMP && p == kFusedUpPath) continue;
+            const int k = RECOMP && p > kFusedUpPath ? p - 1 : p;   // compile-time after unrolling
+            const v4u v = load_slab(y, p);
+            sv[k][0] = v.x; sv[k][1] = v.y; sv[k][2] = v.z; sv[k][3] = v.w;
+        }
+    };
+
+    // the path's state under the band: nothing below the image's last row (the scan starts there, oracle S4), else the checkpoint row y1
+    uint32_t st[8], mm = 0;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) st[i] = 0;
+    if constexpr (RECOMP) load_census_row(y1 - 1);
+    if (RECOMP && y1 < g.h) {
+        const v4u v = load_slab(y1, kFusedUpPath);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {   // slab dword q = the low bytes of (st[2q], st[2q+1]) (agg_step's store)
+            st[2 * q] = perm(0u, v[q], 0x0c010c00u);
+            st[2 * q + 1] = perm(0u, v[q], 0x0c030c02u);
+        }
+        mm = path_min<LPP>(st);
+    }
+    load_slab_row(y1 - 1);
+    lds_barrier();   // s_rv and s_thr are set up; the first row's loads stay in flight
+
+    auto row = [&](int y, auto last_c) {
+        constexpr bool LAST = decltype(last_c)::value;   // the band's top row: nothing left to prefetch (every VMEM instruction of the body unconditional)
+        uint32_t *rvb = &s_rv[y & 1][0];
+        uint32_t sm[8];
+        if constexpr (RECOMP) {
+#pragma unroll
+            for (int i = 0; i < WN::NLD; ++i) wbuf[lslot[i]] = cw[i];
+            CensusRegs c;
+            c.fl = cfl;
+            win_read<LPP>(wbuf, rbase, c.r);
+            uint32_t xr[16];
+            agg_xor(c, xr);
+            if constexpr (!LAST) load_census_row(y - 1);
+            agg_step<LPP, false>(st, mm, xr, sel_lo, sel_hi, p1p1, p2p2, nullptr);
+        }
+        // S in natural adjacent pairs (as wta_fused_kernel): sm[q] = (S[d0+2q], S[d0+2q+1]), sm[4+q] = (S[d0+8+2q], S[d0+9+2q])
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            sm[q] = RECOMP ? perm(st[2 * q + 1], st[2 * q], 0x05040100u) : 0u;
+            sm[4 + q] = RECOMP ? perm(st[2 * q + 1], st[2 * q], 0x07060302u) : 0u;
+        }
+#pragma unroll
+        for (int k = 0; k < NS; ++k) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                sm[q] += sv[k][q] & 0x00ff00ffu;
+                sm[4 + q] += perm(0u, sv[k][q], 0x0c030c01u);
+            }
+        }
+        if constexpr (!LAST) load_slab_row(y - 1);
+        v4u *dst = reinterpret_cast<v4u *>(s_sum + xl * DP + d0);  // LDS tile in natural disparity order
+        dst[0] = v4u{sm[0], sm[1], sm[2], sm[3]};
+        dst[1] = v4u{sm[4], sm[5], sm[6], sm[7]};
+        if (valid) {   // columns past the image have no right view
+            uint32_t *rm = rvb + (xl + D - 1 - d0);
+#pragma unroll
+            for (int q = 0; q < 8; ++q) {
+                const int da = q < 4 ? 2 * q : 8 + 2 * (q - 4);   // local disparity of the low half of sm[q]
+                atomicMin(rm - da, (sm[q] << 16) | (uint32_t)(d0 + da));
+                atomicMin(rm - da - 1, (sm[q] & 0xffff0000u) | (uint32_t)(d0 + da + 1));
+            }
+        }
+        // packed argmin keys: S*16 + local disparity index
+        uint32_t key[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const u16x2 kk = __builtin_bit_cast(u16x2, sm[k]) * (u16x2){16, 16} + (u16x2){(uint16_t)(2 * k), (uint16_t)(2 * k + 1)};
+            key[k] = __builtin_bit_cast(uint32_t, kk);
+        }
+        uint32_t m = pk_min(pk_min(pk_min(key[0], key[1]), pk_min(key[2], key[3])), pk_min(pk_min(key[4], key[5]), pk_min(key[6], key[7])));
+        m = pk_min(m, __builtin_amdgcn_alignbit(m, m, 16)) & 0xffffu;
+        uint32_t pk = ((m >> 4) << 16) | (uint32_t)(d0 + (int)(m & 15u));
+        pk = group_allmin<LPP>(pk);
+        const uint32_t T = s_thr[pk >> 16];
+        const uint32_t tt = T * 0x10001u;
+        uint32_t acc = 0;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) acc = pk_add(acc, pk_sub_sat(tt, sm[k]));
+        const uint32_t tot = group_allsum<LPP>((acc & 0xffffu) + (acc >> 16));
+        if (gl == 0 && valid) {   // the sum row read here was written by lanes of this wave (LDS operations of one wave execute in order)
+            const int bd = (int)(pk & 0xffffu), bc = (int)(pk >> 16), Ti = (int)T;
+            const uint16_t *srow = s_sum + xl * DP;
+            const int l = bd > 0 ? srow[bd - 1] : 0x7fff, r = bd < D - 1 ? srow[bd + 1] : 0x7fff;
+            const int tot_nbr = max(Ti - bc, 0) + max(Ti - l, 0) + max(Ti - r, 0);
+            uint32_t out = kWtaInvalid;
+            if ((int)tot == tot_nbr) {
+                int subp = bd * 16;
+                if (bd > 0 && bd < D - 1) {
+                    const int num = l - r, den = l - 2 * bc + r;
+                    if (den != 0) subp += (num * 16 + den) / (2 * den);
+                }
+                out = (uint32_t)subp & 0xffffu;
+            }
+            a.wta_l[(size_t)frame * g.npx + (size_t)y * g.w + x] = (uint16_t)out;
+        }
+        lds_barrier();
+        // right view (oracle S6): the tile's minima of this row are complete in s_rv[y & 1]; the entry is reset for row y - 2 by the thread that read it
+        // (every thread passes the barrier of row y - 1 in between)
+        for (int pi = threadIdx.x; pi < kWtaTileX + D - 1; pi += NT) {
+            const int p = x0 - (D - 1) + pi;
+            const uint32_t best = rvb[pi];
+            rvb[pi] = 0xffffffffu;
+            if (p >= 0 && p < g.w && best != 0xffffffffu) atomicMin(&a.right_pk[(size_t)frame * g.npx + (size_t)y * g.w + p], best);
+        }
+    };
+    for (int y = y1 - 1; y > y0; --y) row(y, std::false_type{});
+    row(y0, std::true_type{});
+}
+
+bool wta_band_supported(const Geometry &g, int K, bool probe) { return g.D == 128 && g.P == kMaxPaths && (K == 4 || K == 8 || K == 16 || (probe && K == 1)); }
+
+void launch_wta_band(const uint32_t *cen_l, const uint32_t *cen_r, const SlabTable &slabs, uint16_t *wta_l, uint32_t *right_pk,
+                     const Geometry &g, const uint16_t *thr, int n_frames, int K, bool probe, hipStream_t s) {
+    dim3 grid((g.w + kWtaTileX - 1) / kWtaTileX, (g.h + K - 1) / K, n_frames), block(64 * (g.D / 16));
+    BandArgs a{cen_l, cen_r, slabs, wta_l, right_pk, g, thr};
+    if (probe) {
+        switch (K) {
+            case 1: hipLaunchKernelGGL((wta_band_kernel<8, 1, false>), grid, block, 0, s, a); break;
+            case 4: hipLaunchKernelGGL((wta_band_kernel<8, 4, false>), grid, block, 0, s, a); break;
+            case 8: hipLaunchKernelGGL((wta_band_kernel<8, 8, false>), grid, block, 0, s, a); break;
+            default: hipLaunchKernelGGL((wta_band_kernel<8, 16, false>), grid, block, 0, s, a); break;
+        }
+        return;
+    }
+    switch (K) {
+        case 4: hipLaunchKernelGGL((wta_band_kernel<8, 4>), grid, block, 0, s, a); break;
+        case 8: hipLaunchKernelGGL((wta_band_kernel<8, 8>), grid, block, 0, s, a); break;
+        default: hipLaunchKernelGGL((wta_band_kernel<8, 16>), grid, block, 0, s, a); break;
     }
 }
 

@@ -68,11 +68,14 @@ void cart_engine_destroy(cart_engine *engine);
 
 /* Launch plans of the SGM core.  Every plan produces the same bits; they differ in which path slabs exist in HBM.
  *   SLABS     all P path slabs are written by the aggregation launch and read by the WTA launch (2*P*D bytes / pixel);
- *   FUSED_UP  the "up" path is computed inside the WTA sweep and never stored (2*(P-1)*D bytes / pixel).
+ *   FUSED_UP  the "up" path is computed inside the WTA sweep and never stored (2*(P-1)*D bytes / pixel);
+ *   BAND_UP   the "up" path is stored on every K-th row only (checkpoints, in place in its slab) and recomputed in registers by a
+ *             WTA that works on tiles of 64 columns x K rows (2*(P-1 + 1/K)*D bytes / pixel).  D = 128 with 8 paths only: any
+ *             other engine answers SLABS.
  * AUTO picks per launch from the measured table in DESIGN.md section 4.  Options are plain integers so that the
  * boundary stays C; nothing in the engine reads the environment.
  */
-enum { CART_PLAN_AUTO = -1, CART_PLAN_SLABS = 0, CART_PLAN_FUSED_UP = 1 };
+enum { CART_PLAN_AUTO = -1, CART_PLAN_SLABS = 0, CART_PLAN_FUSED_UP = 1, CART_PLAN_BAND_UP = 2 };
 enum {
     CART_OPT_PLAN = 0,            /* CART_PLAN_*; default AUTO */
     CART_OPT_PLAN_MIN_FRAMES = 1, /* with a forced plan: launches of fewer frames take SLABS (default 1) */
@@ -83,8 +86,11 @@ enum {
      * variants by tests/test_gpu_parity.py::test_spec_variants.  These change results, by design; nothing else does. */
     CART_OPT_SPEC_S8_ZERO_INVALID = 3,      /* 1: the LR check also invalidates pixels whose integer disparity is 0 (older libSGM's `d <= 0`) */
     CART_OPT_SPEC_S7_REPLICATE_BORDER = 4,  /* 1: the 3x3 medians filter the one-pixel image border over a replicated border instead of passing it through */
-    CART_OPT_SPEC_S5_TOP2 = 5               /* 1: uniqueness tests the second-best (cost, d) only -- the top-2 wording of SURVEY.md 8a-4(4) -- instead of every
+    CART_OPT_SPEC_S5_TOP2 = 5,              /* 1: uniqueness tests the second-best (cost, d) only -- the top-2 wording of SURVEY.md 8a-4(4) -- instead of every
                                                disparity (the libSGM form, oracle S5); such an engine always takes plan SLABS */
+    CART_OPT_BAND_ROWS = 6,                 /* K of plan BAND_UP: 4, 8 or 16 rows per band (default: the measured winner); 1 with the probe */
+    CART_OPT_BAND_PROBE = 7                 /* measurement only, 1: plan BAND_UP stores and reads all P slabs and recomputes nothing -- the two-kernel WTA's
+                                               work in K-row tiles (the read-rate probe of DESIGN.md 8); describe_plan then reports P slabs */
 };
 int cart_engine_set_option(cart_engine *engine, int option, int value);
 int cart_engine_get_option(cart_engine *engine, int option, int *value);
@@ -92,8 +98,9 @@ int cart_engine_get_option(cart_engine *engine, int option, int *value);
  * path slabs that plan materialises (bench.py prices its roofline line from this instead of re-deriving it). */
 typedef struct {
     int frames_per_launch;
-    int plan;             /* CART_PLAN_SLABS | FUSED_UP */
-    int slabs_written;    /* u8 slabs of D bytes per pixel written (and read once) per frame */
+    int plan;             /* CART_PLAN_SLABS | FUSED_UP | BAND_UP */
+    int slabs_written;    /* u8 slabs of D bytes per pixel written (and read once) per frame.  BAND_UP reports P - 1: its checkpoint rows are
+                             1/K of one more slab, which this integer cannot say (bench.py's moved_bytes is 1.6 % low at K = 8) */
 } cart_launch_plan;
 int cart_engine_describe_plan(cart_engine *engine, int n_frames, cart_launch_plan *out);
 
