@@ -3,7 +3,13 @@ place in its slab) and wta_band_kernel recomputes the path inside tiles of 64 co
 plan "slabs" and of the CPU oracle on every output.
 
 The engine accepts images from 16 x 8 pixels up (cart_engine_create), so the band-edge heights below 8 and the widths below 16 cannot be run:
-for those the tests assert that the engine refuses the size, which is what a caller sees."""
+for those the tests assert that the engine refuses the size, which is what a caller sees.
+
+This file runs the plan at the default penalties and uniqueness ratio.  test_gpu_band_params.py beside it covers the rest: P1 / P2 / uniqueness /
+min_disparity over the accepted range (path costs up to 255 in a checkpoint byte), the checkpoint rows and the other seven slabs read back against
+the oracle and the rows the launch must not write, 16 distinct frames in one launch at full size, the 16384 x 8 and 16 x 2000 images, and the
+compute_disparity_multi / host threads / two-stream pipeline entry points; test_gpu_parity.py runs the plan wherever it loops over the launch
+plans at D = 128 with 8 paths (full-size scenes, KITTI frame sizes, the 4099-wide image, 8 distinct frames per launch, the S8 / S7 variants)."""
 import numpy as np
 import pytest
 

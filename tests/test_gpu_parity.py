@@ -36,6 +36,21 @@ def make_engine(w, h, D, P, md=4, radius=-1, iters=5, inflight=4, plan=None, pla
     return eng
 
 
+def forced_plans(eng, D, P, n, band_rows=(4, 16, 8)):
+    """Forces every launch plan the engine has for (D, P) in turn and yields its label: "slabs" and "fused_up" everywhere, and at D = 128 with
+    8 paths "band_up" once per K of band_rows (the default K = 8 last, so that it is what the engine is left with).  A forced band_up must be
+    what a call of n frames runs: plan_for would otherwise answer SLABS and the caller would compare SLABS with itself."""
+    for plan in ("slabs", "fused_up"):
+        eng.set_plan(plan)
+        yield plan
+    if (D, P) == (128, 8):
+        eng.set_plan("band_up")
+        for k in band_rows:
+            eng.set_band_rows(k)
+            assert eng.describe_plan(n)["plan"] == "band_up"
+            yield f"band_up K={k}"
+
+
 CASES = [
     # w, h, D, P, min_disp
     (160, 96, 64, 4, 4),
@@ -156,15 +171,17 @@ def test_edge_inputs(torch_cuda):
 def test_extreme_shapes(torch_cuda, w, h, D, P):
     """The smallest and the most lopsided images the engine accepts (16 x 8 is its minimum, 16384 its widest): one W-step scan
     per row group, 2000-step vertical scans on two lane groups, an image narrower than a sixteenth of its disparity range, and a
-    prime width -- single frame and a batch of three, every launch plan, through plane labelling and components."""
+    prime width -- single frame and a batch of three, every launch plan (forced_plans: at D = 128 with 8 paths also band_up with every K),
+    through plane labelling and components."""
     torch = torch_cuda
     rng = np.random.default_rng(w * 31 + h)
     base = rng.integers(0, 256, (h, w + 40)).astype(np.uint8)
     l, r = np.ascontiguousarray(base[:, 20:20 + w]), np.ascontiguousarray(base[:, 27:27 + w])   # a 7-pixel shift: real matches where the width allows
     exp = O.disparity_module(l, r, D, P, 4, radius=2, iterations=1)
     eng = make_engine(w, h, D, P, 4, radius=2, iters=1, inflight=3)
-    for plan in ("slabs", "fused_up"):
-        eng.set_plan(plan)
+    # (4099, 11, 128, 8): also band_up, every K.  The engine keeps the last forced plan (fused_up, or band_up K = 8 for that case): the single-frame
+    # call that feeds the plane stages below runs it.
+    for plan in forced_plans(eng, D, P, 3):
         got = eng.compute_disparity(dev(torch, np.stack([l, l, l])), dev(torch, np.stack([r, r, r]))).cpu().numpy()
         assert all((got[k] == exp).all() for k in range(3)), f"{plan}: {int((got[0] != exp).sum())} pixels differ"
         assert (eng.compute_disparity(dev(torch, l), dev(torch, r)).cpu().numpy() == exp).all(), plan
@@ -363,7 +380,7 @@ def test_full_size_scene_content_against_oracle(torch_cuda, scene):
     does not -- an exactly periodic striped facade (equal-cost candidates every 8 / 16 / 24 px), a saturated and a BLACK
     patch (gray == 0 is the LR check's mask, oracle S8), 1-px / 3-px poles, a large textureless wall, a right camera with its
     own gain, offset and noise -- whole frame through
-    classification, components and the component table, every launch plan, bit-exact.  (No KITTI data is available offline;
+    classification, components and the component table, every launch plan (slabs, fused_up, band_up with K = 16 and 8), bit-exact.  (No KITTI data is available offline;
     this is the nearest substitute.)"""
     torch = torch_cuda
     w, h, D, P = 1242, 375, 128, 8
@@ -382,8 +399,7 @@ def test_full_size_scene_content_against_oracle(torch_cuda, scene):
         assert 0.5 < inv[y0:y1, x0:x1].mean() < 1.0
     eng = make_engine(w, h, D, P, 4, radius=2, iters=1, inflight=4)
     L, R = dev(torch, np.stack([l, l])), dev(torch, np.stack([r, r]))
-    for plan in ("slabs", "fused_up"):
-        eng.set_plan(plan)
+    for plan in forced_plans(eng, D, P, 2, band_rows=(16, 8)):
         got = eng.compute_disparity(L, R).cpu().numpy()
         assert (got[0] == exp).all() and (got[1] == exp).all(), f"{plan}: {int((got[0] != exp).sum())} pixels differ"
     eng.set_plan("auto")
@@ -412,14 +428,14 @@ def test_full_size_scene_content_against_oracle(torch_cuda, scene):
 def test_native_kitti_frame_sizes(torch_cuda, w, h):
     """The other frame sizes KITTI sequences come in (odometry 00-02: 1241x376, 03: 1242x375, 04-10: 1226x370; raw drives
     1224x370): the reference resizes to its configured size, but an engine configured for the native size must be just as
-    exact -- D=128, 8 paths, every launch plan, a batch of two (the widths are odd or leave ragged tiles everywhere)."""
+    exact -- D=128, 8 paths, every launch plan (slabs, fused_up, band_up with K = 16 and 8), a batch of two (the widths are odd or leave ragged
+    tiles everywhere)."""
     torch = torch_cuda
     D, P = 128, 8
     l, r, _ = synth.make_pair(w, h, D, 4, seed=w * 7 + h, scene="pole")
     exp = O.disparity_module(l, r, D, P, 4, radius=2, iterations=1)
     eng = make_engine(w, h, D, P, 4, radius=2, iters=1, inflight=2)
-    for plan in ("slabs", "fused_up"):
-        eng.set_plan(plan)
+    for plan in forced_plans(eng, D, P, 2, band_rows=(16, 8)):
         got = eng.compute_disparity(dev(torch, np.stack([l, l])), dev(torch, np.stack([r, r]))).cpu().numpy()
         assert (got[0] == exp).all() and (got[1] == exp).all(), f"{plan}: {int((got[0] != exp).sum())} pixels differ"
     eng.close()
@@ -1092,10 +1108,12 @@ def test_spec_variants(torch_cuda, variants):
     """The three choices that are open upstream -- S8: the LR check also invalidates integer disparity 0; S7: medians over
     a replicated border; S5: uniqueness from the second-best cost only (the top-2 wording of SURVEY 8a-4(4)) -- as engine
     options (CART_OPT_SPEC_*), singly and together against the oracle's variants, on images that hit
-    them (ragged sizes, a border in every tile shape, min_disparity 0 so that disparity 0 wins often), with interpolation on top;
+    them (ragged sizes, a border in every tile shape, min_disparity 0 so that disparity 0 wins often), with interpolation on top; at D = 128 with
+    8 paths S8 / S7 also behind the banded WTA (forced band_up);
     and back to the default spec afterwards."""
     torch = torch_cuda
-    for (w, h, D, P, md, scene) in [(173, 67, 64, 8, 0, "road"), (330, 50, 128, 4, 4, "saturated"), (340, 60, 256, 8, 1, "wall"), (1242, 375, 128, 8, 4, "pole")]:
+    for (w, h, D, P, md, scene) in [(173, 67, 64, 8, 0, "road"), (330, 50, 128, 4, 4, "saturated"), (340, 60, 256, 8, 1, "wall"), (1242, 375, 128, 8, 4, "pole"),
+                                   (211, 53, 128, 8, 0, "stripes")]:   # D = 128 with 8 paths: also through the banded WTA (variants 1, 2, 3)
         l, r, _ = synth.make_pair(w, h, D, md, seed=77, scene=scene)
         base = O.disparity_module(l, r, D, P, md, radius=2, iterations=1)
         exp = O.disparity_module(l, r, D, P, md, radius=2, iterations=1, variants=variants)
@@ -1107,6 +1125,14 @@ def test_spec_variants(torch_cuda, variants):
             assert eng.describe_plan(2)["plan"] == "slabs"
         got = eng.compute_disparity(dev(torch, np.stack([l, l])), dev(torch, np.stack([r, r]))).cpu().numpy()
         assert (got[0] == exp).all() and (got[1] == exp).all(), f"{(w, h, D, P, md, scene)}: {int((got[0] != exp).sum())} pixels differ"
+        if (D, P) == (128, 8) and not variants & 4:   # S8 / S7 live behind the WTA: the banded WTA has to hand them the same maps
+            eng.set_plan("band_up")
+            for k in (4, 16, 8) if w * h < 100000 else (16, 8):
+                eng.set_band_rows(k)
+                assert eng.describe_plan(2)["plan"] == "band_up"
+                got = eng.compute_disparity(dev(torch, np.stack([l, l])), dev(torch, np.stack([r, r]))).cpu().numpy()
+                assert (got[0] == exp).all() and (got[1] == exp).all(), f"{(w, h, D, P, md, scene)} band_up K={k}: {int((got[0] != exp).sum())} pixels differ"
+            eng.set_plan("auto")
         eng.set_spec_variants()
         assert (eng.compute_disparity(dev(torch, l), dev(torch, r)).cpu().numpy() == base).all()
         eng.close()
@@ -1116,7 +1142,7 @@ def test_spec_variants(torch_cuda, variants):
 @pytest.mark.parametrize("w,h,D,P,n", [(173, 67, 64, 4, 16), (201, 45, 128, 8, 8), (330, 50, 256, 8, 16), (131, 90, 256, 4, 24)])
 def test_xcd_placed_launches_cover_every_frame(torch_cuda, w, h, D, P, n):
     """Launches whose frame count is a multiple of 8 decode their grid per XCD (frames x, x + 8, ... on XCD x; aggregation launch
-    and fused sweep, sgm_kernels.hip xcd_placement): n DISTINCT frames, every launch plan, EVERY frame against the oracle -- a
+    and fused sweep, sgm_kernels.hip xcd_placement): n DISTINCT frames, every launch plan (at D = 128 with 8 paths also band_up, every K), EVERY frame against the oracle -- a
     decode that skipped or doubled a (direction, frame, line group) could not hide behind repeated frames."""
     torch = torch_cuda
     ls, rs = synth.make_batch(n, w, h, D, 4, seed=5150 + D)
@@ -1124,8 +1150,7 @@ def test_xcd_placed_launches_cover_every_frame(torch_cuda, w, h, D, P, n):
     assert any((exp[0] != exp[k]).any() for k in range(1, n))
     eng = make_engine(w, h, D, P, 4, radius=2, iters=1, inflight=n)
     eng.set_chunk_frames(n)   # one launch sequence of n frames (24 > the default 16)
-    for plan in ("slabs", "fused_up"):
-        eng.set_plan(plan)
+    for plan in forced_plans(eng, D, P, n):   # (201, 45, 128, 8, 8): also band_up, every K
         assert eng.describe_plan(n)["frames_per_launch"] == n
         got = eng.compute_disparity(dev(torch, ls), dev(torch, rs)).cpu().numpy()
         for k in range(n):
