@@ -40,7 +40,7 @@ struct Slot {
     unsigned long long released_seq = 0;  // order of the last release (guarded by mu)
 };
 
-// Plan BAND_UP (sgm_kernels.hip, wta_band_kernel): rows per band, and the launch size from which CART_PLAN_AUTO takes the plan at D = 128 with
+// Plan BAND_UP (sgm_wta.hip, wta_band_kernel): rows per band, and the launch size from which CART_PLAN_AUTO takes the plan at D = 128 with
 // 8 paths.  Both from the A/B at 1242x375 in DESIGN.md 4.1 (profiles/band_up.txt).
 constexpr int kBandRowsDefault = 8;
 constexpr int kBandAutoMinFrames = 4;   // 2-frame launches stay on SLABS; 4, 6, 8, 12 and 16 frames measured

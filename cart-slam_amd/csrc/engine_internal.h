@@ -80,7 +80,7 @@ inline OutBatch strided_out(int16_t *ptr, size_t step, size_t frame_stride) {
     OutBatch b{}; b.ptr = ptr; b.step = step; b.frame_stride = frame_stride; return b;
 }
 
-// ---- launchers (sgm_kernels.hip) ----
+// ---- launchers (sgm_census.hip, sgm_aggregate.hip, sgm_wta.hip, sgm_post.hip) ----
 void launch_census(const ImageBatch &left, const ImageBatch &right, int channels, int n_frames,
                    uint8_t *gray_l, uint8_t *gray_r, uint32_t *cen_l, uint32_t *cen_r, uint32_t *right_pk,
                    const Geometry &g, hipStream_t s);
@@ -91,13 +91,14 @@ void launch_aggregate(const AggArgs &a, int n_frames, hipStream_t s);
 // thr = device table of the integer uniqueness threshold for every best cost 0..2047 (launch_uniq_table, built once per engine)
 void launch_wta(const SlabTable &slabs, uint16_t *wta_l, uint32_t *right_pk, const Geometry &g, const uint16_t *thr,
                 int n_frames, hipStream_t s, bool top2 = false);   // top2: the S5 variant (second-best only), two-kernel WTA only
-// WTA fused with the "up" direction (slab kFusedUpPath is never read: the aggregate launch may skip that direction)
-constexpr int kFusedUpPath = 1;
+// Slab index of the "up" direction (oracle order: down, up, right, left, diagonals).  The fused WTA computes that path itself and never reads its slab
+// (the aggregate launch may skip the direction); plan BAND_UP keeps only its checkpoint rows there.
+constexpr int kUpPath = 1;
 size_t wta_fused_partial_elems(const Geometry &g);  // u32 elements of the per-frame right-view partial buffer
 void launch_wta_fused(const uint32_t *cen_l, const uint32_t *cen_r, const SlabTable &slabs, uint16_t *wta_l, uint32_t *right_pk,
                       uint32_t *partial, const Geometry &g, const uint16_t *thr, int n_frames, hipStream_t s);
 // WTA over bands of K rows that recomputes the "up" path from the checkpoint rows a launch_aggregate with ckpt_rows = K left in slab
-// kFusedUpPath (plan BAND_UP: D = 128, 8 paths, K = 4, 8 or 16)
+// kUpPath (plan BAND_UP: D = 128, 8 paths, K = 4, 8 or 16)
 // probe: the read-rate probe -- all P slabs are read (the aggregation launch stored every row), nothing is recomputed; K = 1 allowed
 bool wta_band_supported(const Geometry &g, int K, bool probe);
 void launch_wta_band(const uint32_t *cen_l, const uint32_t *cen_r, const SlabTable &slabs, uint16_t *wta_l, uint32_t *right_pk,
@@ -106,7 +107,7 @@ void launch_uniq_table(float u, uint16_t *out_dev, hipStream_t s);   // test acc
 void uniq_table_host(float u, uint16_t *out);
 void launch_post(const uint16_t *wta_l, const uint32_t *right_pk, const uint8_t *gray_l, const OutBatch &out, const Geometry &g, int n_frames, hipStream_t s,
                  int spec = 0);
-// post stage + first Jacobi pass of the radius-2 interpolation in one launch (sgm_kernels.hip, post_interp_kernel)
+// post stage + first Jacobi pass of the radius-2 interpolation in one launch (sgm_post.hip, post_interp_kernel)
 bool post_interp_fusable(int radius, int min_disp16, int max_disp);
 void launch_post_interp(const uint16_t *wta_l, const uint32_t *right_pk, const uint8_t *gray_l, const OutBatch &out, const Geometry &g, int n_frames,
                         hipStream_t s, int spec, int min_disp16, int max_disp);   // spec: CART_OPT_SPEC_* bits (1 = S8 zero-disparity-invalid, 2 = S7 replicated border)

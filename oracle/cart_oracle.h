@@ -60,7 +60,7 @@
  *                 border row / column (pass-through, a replicated-border median, or untouched memory) cannot be
  *                 checked here.  A replicated-border median changes 66-100 output pixels on the committed goldens and
  *                 836-844 of 465 750 at 1242x375 (tests/spec_variants.py).  One place to change: the first `if` of
- *                 cart_oracle_median3x3_u16 (and left_median_at / right_median_at in sgm_kernels.hip).
+ *                 cart_oracle_median3x3_u16 (and left_median_at / right_median_at in sgm_post.hip).
  *  S8 LR check  left pixel -> 0xFFFF if gray_left==0, or already 0xFFFF, or
  *                 k = x-(dL>>4) in [0,W) and |R(k)-(dL>>4)| > 1.
  *                 NOTE -- probable point of departure [EXTERNAL-UNVERIFIED]: the check_consistency kernel of older libSGM
@@ -72,7 +72,7 @@
  *                 would invalidate 558 / 789 / 1187 / 592 more pixels on the four committed goldens and 2225-2686 of
  *                 465 750 on the 1242x375 scenes (tests/spec_variants.py).  One line to change in each place:
  *                 cart_oracle_lr_check_range (`gray_left[i] == 0 || org == CART_ORACLE_WTA_INVALID` -> add
- *                 `|| (org >> 4) == 0`) and post_kernel's `bool invalid =` line in sgm_kernels.hip.  tools/ref_pin produces the
+ *                 `|| (org >> 4) == 0`) and post_kernel's `bool invalid =` line in sgm_post.hip.  tools/ref_pin produces the
  *                 reference outputs that decide it; tests/test_ref_pin.py names this variant when they disagree.  Both forms exist:
  *                 CART_ORACLE_VARIANT_S8_ZERO_INVALID here, CART_OPT_SPEC_S8_ZERO_INVALID on the engine (likewise S7).
  *  S9 range     0xFFFF -> (min_disp-1)*16, else += min_disp*16; stored s16.

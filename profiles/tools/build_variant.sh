@@ -1,6 +1,7 @@
 #!/bin/bash
 # usage: build_variant.sh <name> <extra hipcc flags...>   ->  cart-slam_amd/build/ab/<name>/libcart_engine.so
 # A/B builds of the engine with development knobs (-D...); select one at run time with CART_ENGINE_LIB=<path> (cartslam/_lib.py).
+# DEAD since 8553023: it rebuilds csrc/sgm_kernels.hip, which no longer exists (split by stage into csrc/sgm_*.hip).  Kept for the record only.
 # Only sgm_kernels.hip is rebuilt, the other objects come from build/.
 set -e
 ROOT=$(cd "$(dirname "$0")/../.." && pwd); PKG=$ROOT/cart-slam_amd; name=$1; shift

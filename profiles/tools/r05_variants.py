@@ -1,4 +1,5 @@
 #!/usr/bin/env python3
+# Last tree this applies to: 8553023 (it patches csrc/sgm_kernels.hip by string; that file has since been split by stage into csrc/sgm_*.hip).
 """Round 5 A/B builds of the aggregation launch (does the number of direction x frame row fronts that are resident at a
 time -- the launch's instantaneous write window -- bind it?).  The product source is not touched: every variant is a patched COPY of
 cart-slam_amd/csrc/sgm_kernels.hip, compiled into cart-slam_amd/build/ab/<name>/libcart_engine.so (select with CART_ENGINE_LIB=<path>).

@@ -89,7 +89,7 @@ def test_sgm_stage_by_stage(torch_cuda, w, h, D, P, md):
 
 @pytest.mark.parametrize("w,h,D,P", [(173, 67, 128, 8), (333, 35, 64, 4), (211, 45, 64, 8), (97, 29, 256, 4), (1242, 375, 64, 4),
                                      # heights h with h % (2 x rows per pair) in {1, rows per pair + 1}: the last workgroup's pair(s) hold ONE valid row, every other
-                                     # lane group clones it -- two waves store the same bytes to the same cells (sgm_kernels.hip, split-scan row cloning)
+                                     # lane group clones it -- two waves store the same bytes to the same cells (sgm_aggregate.hip, split-scan row cloning)
                                      (173, 65, 128, 8), (333, 49, 64, 4), (97, 25, 256, 4)])
 def test_split_horizontal_scans_equal_plain_ones(torch_cuda, w, h, D, P):
     """The aggregation launch runs its horizontal scans as producer / consumer wave pairs when it would otherwise wait for their W-step
@@ -1142,7 +1142,7 @@ def test_spec_variants(torch_cuda, variants):
 @pytest.mark.parametrize("w,h,D,P,n", [(173, 67, 64, 4, 16), (201, 45, 128, 8, 8), (330, 50, 256, 8, 16), (131, 90, 256, 4, 24)])
 def test_xcd_placed_launches_cover_every_frame(torch_cuda, w, h, D, P, n):
     """Launches whose frame count is a multiple of 8 decode their grid per XCD (frames x, x + 8, ... on XCD x; aggregation launch
-    and fused sweep, sgm_kernels.hip xcd_placement): n DISTINCT frames, every launch plan (at D = 128 with 8 paths also band_up, every K), EVERY frame against the oracle -- a
+    and fused sweep, sgm_device.h xcd_placement): n DISTINCT frames, every launch plan (at D = 128 with 8 paths also band_up, every K), EVERY frame against the oracle -- a
     decode that skipped or doubled a (direction, frame, line group) could not hide behind repeated frames."""
     torch = torch_cuda
     ls, rs = synth.make_batch(n, w, h, D, 4, seed=5150 + D)
