@@ -35,7 +35,16 @@ class LaunchPlan(C.Structure):
 PLAN_AUTO, PLAN_SLABS, PLAN_FUSED_UP, PLAN_BAND_UP = -1, 0, 1, 2      # CART_PLAN_*
 OPT_PLAN, OPT_PLAN_MIN_FRAMES, OPT_CHUNK_FRAMES = 0, 1, 2           # CART_OPT_*
 OPT_BAND_ROWS, OPT_BAND_PROBE = 6, 7
+OPT_FLOW_GATHER = 8
 OPT_SPEC_S8_ZERO_INVALID, OPT_SPEC_S7_REPLICATE_BORDER, OPT_SPEC_S5_TOP2 = 3, 4, 5   # CART_OPT_SPEC_*: upstream variants of oracle S8 / S7 / S5
+
+
+class FlowParams(C.Structure):
+    # mirrors cart_flow_params (include/cart_engine.h, spec S21)
+    _fields_ = [(n, C.c_int) for n in ("levels", "radius", "refine_radius", "block", "median")]
+
+
+FLOW_MAX_LEVELS = 6
 
 
 class PlacementReport(C.Structure):
@@ -121,6 +130,10 @@ PROTOTYPES = {
     "cart_orb_detect": (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_sz), _i, _i, _i, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_sz), _vp, _vp]),
     "cart_orb_debug_level": (_i, [_vp, _i, _i, _vp, _sz, C.POINTER(C.c_int32), _vp]),
     "cart_optical_flow": (_i, [_vp, _vp, _sz, _vp, _sz, _i, _i, _i, _vp, _sz, _vp]),
+    "cart_flow_default_params": (None, [C.POINTER(FlowParams)]),
+    "cart_flow_pyramid_levels": (_i, [_i, _i, _i, C.POINTER(_i), C.POINTER(_i)]),
+    "cart_optical_flow_pyramid": (_i, [_vp, _vp, _sz, _vp, _sz, _i, C.POINTER(FlowParams), _vp, _sz, _vp]),
+    "cart_flow_debug_level": (_i, [_vp, _i, _i, _vp, _sz]),
     "cart_resize_linear": (_i, [_i, _vp, _sz, _i, _i, _i, _vp, _sz, _i, _i, _vp]),
     "cart_copy_narrow": (_i, [_vp, _vp, _vp, _sz, _i, _vp]),
     "cart_find_plane_params": (_i, [C.POINTER(C.c_int32), C.POINTER(PlaneParams)]),

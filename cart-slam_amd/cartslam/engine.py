@@ -43,6 +43,16 @@ def _geom(t, inner):
     return n, C.c_void_p(t.data_ptr()), step, fs
 
 
+def flow_pyramid_levels(w, h, levels):
+    """-> [(w_l, h_l)] of the levels spec S21 builds for a w x h frame when `levels` are asked for (cart_flow_pyramid_levels; host only)."""
+    lib = _lib.load()
+    lw, lh = (C.c_int * _lib.FLOW_MAX_LEVELS)(), (C.c_int * _lib.FLOW_MAX_LEVELS)()
+    n = lib.cart_flow_pyramid_levels(int(w), int(h), int(levels), lw, lh)
+    if n < 1:
+        raise EngineError("cart_flow_pyramid_levels: " + lib.cart_last_error(None).decode())
+    return [(lw[k], lh[k]) for k in range(n)]
+
+
 class Engine:
     """One engine = one (width, height, D, paths, ...) configuration on one GPU.
     num_disparities=0, paths=0 gives a geometry-only engine for the post-SGM entry points."""
@@ -318,6 +328,37 @@ class Engine:
         self._check(self._lib.cart_optical_flow(self._h, cp, cs, pp, ps, ch, int(radius), int(block), op, os_, _stream_ptr()),
                     "cart_optical_flow")
         return out
+
+    def optical_flow_pyramid(self, cur, prev, levels=4, radius=4, refine_radius=2, block=2, median=True):
+        """Coarse-to-fine form (spec S21): same images and output as optical_flow, reach radius * 2^(L-1) + refine_radius * (2^(L-1) - 1)."""
+        import torch
+        ch = 3 if cur.dim() == 3 else 1
+        _, cp, cs, _ = _geom(cur, 2 if ch == 3 else 1)
+        _, pp, ps, _ = _geom(prev, 2 if ch == 3 else 1)
+        if tuple(cur.shape[:2]) != (self.height, self.width) or cur.shape != prev.shape:
+            raise EngineError("image shape does not match the engine")
+        fp = _lib.FlowParams(int(levels), int(radius), int(refine_radius), int(block), 1 if median else 0)
+        out = torch.empty((self.height, self.width, 2), dtype=torch.int16, device=cur.device)
+        _, op, os_, _ = _geom(out, 2)
+        self._check(self._lib.cart_optical_flow_pyramid(self._h, cp, cs, pp, ps, ch, C.byref(fp), op, os_, _stream_ptr()),
+                    "cart_optical_flow_pyramid")
+        return out
+
+    def flow_debug_level(self, level, what):
+        """Level `level` of the calling thread's last optical_flow_pyramid call as a numpy array: what = 0 image of cur, 1 of prev
+        (uint8 [h_l, w_l]), 2 flow in whole pixels (int16 [h_l, w_l, 2], after the median when it is on).  Synchronises the device."""
+        sizes = flow_pyramid_levels(self.width, self.height, _lib.FLOW_MAX_LEVELS)
+        if not 0 <= level < len(sizes):
+            raise EngineError("flow_debug_level: that level is not built for this image size")
+        w, h = sizes[level]
+        out = np.empty((h, w, 2), np.int16) if what == 2 else np.empty((h, w), np.uint8)
+        self._check(self._lib.cart_flow_debug_level(self._h, int(level), int(what), out.ctypes.data_as(C.c_void_p), out.nbytes), "cart_flow_debug_level")
+        return out
+
+    def set_flow_gather(self, on):
+        """Tests and measurements: the refinement kernel of optical_flow_pyramid gathers the previous features from global memory in
+        every tile instead of staging them in LDS where they fit (same bits)."""
+        self._check(self._lib.cart_engine_set_option(self._h, _lib.OPT_FLOW_GATHER, 1 if on else 0), "cart_engine_set_option")
 
     # ---- depth module (reference src/modules/depth.cpp:9-25) ----
     def reproject_depth(self, disp, Q):

@@ -93,7 +93,7 @@ int ensure_ws_locked(cart_engine *e, void **ws, size_t bytes_per_slot, bool zero
     const size_t bytes = e->slots.size() * bytes_per_slot;
     void *p = nullptr;
     HIP_TRY(hipMalloc(&p, bytes));
-    if (zero && (hipMemset(p, 0, bytes) != hipSuccess || hipDeviceSynchronize() != hipSuccess)) { (void)hipFree(p); return fail("hipMemset of the component-table workspace failed"); }
+    if (zero && (hipMemset(p, 0, bytes) != hipSuccess || hipDeviceSynchronize() != hipSuccess)) { (void)hipFree(p); return fail("hipMemset of a zeroed workspace failed"); }
     e->bufs.push_back(p);
     *ws = p;
     return 0;
@@ -411,6 +411,10 @@ int cart_engine_set_option(cart_engine *e, int option, int value) {
             if (value != 0 && value != 1) return fail("the band probe is 0 or 1");
             e->opt_band_probe = value;
             return 0;
+        case CART_OPT_FLOW_GATHER:
+            if (value != 0 && value != 1) return fail("the flow gather option is 0 or 1");
+            e->opt_flow_gather = value;
+            return 0;
         case CART_OPT_SPEC_S8_ZERO_INVALID:
         case CART_OPT_SPEC_S7_REPLICATE_BORDER:
         case CART_OPT_SPEC_S5_TOP2: {
@@ -432,6 +436,7 @@ int cart_engine_get_option(cart_engine *e, int option, int *value) {
         case CART_OPT_CHUNK_FRAMES: *value = e->chunk_frames; return 0;
         case CART_OPT_BAND_ROWS: *value = e->opt_band_rows; return 0;
         case CART_OPT_BAND_PROBE: *value = e->opt_band_probe; return 0;
+        case CART_OPT_FLOW_GATHER: *value = e->opt_flow_gather; return 0;
         case CART_OPT_SPEC_S8_ZERO_INVALID: *value = (e->opt_spec & 1) ? 1 : 0; return 0;
         case CART_OPT_SPEC_S7_REPLICATE_BORDER: *value = (e->opt_spec & 2) ? 1 : 0; return 0;
         case CART_OPT_SPEC_S5_TOP2: *value = (e->opt_spec & 4) ? 1 : 0; return 0;

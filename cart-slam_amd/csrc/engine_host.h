@@ -86,6 +86,7 @@ struct cart_engine {
     // allocated by the first call that needs them (ensure_ws)
     uint32_t *rv_partial = nullptr; // [max_inflight][wta_fused_partial_elems]: fused batches
     uint8_t *flow_ws = nullptr;     // [max_inflight][flow_ws_bytes]: gray x2, census x2, scratch (cart_optical_flow)
+    uint8_t *flow_pyr_ws = nullptr; // [max_inflight][FlowPyrLayout::bytes]: level images, census planes and level flows (cart_optical_flow_pyramid)
     int32_t *ccl_stats_ws = nullptr; // component-table workspace: [max_inflight][npx][kCclStatInts] scratch + [max_inflight][h][tile columns]
     unsigned *sp_votes = nullptr;   // [max_inflight][kSpMaxLabels*3] (cart_superpixel_plane_classify)
     std::vector<void *> bufs;       // every device allocation above, freed by cart_engine_destroy
@@ -97,6 +98,7 @@ struct cart_engine {
     int auto_band_min_frames = 1 << 30;  // CART_OPT_PLAN = auto: launches of at least this many frames take BAND_UP (D = 128, 8 paths)
     int opt_band_rows = cart_amd::kBandRowsDefault, opt_band_probe = 0;   // CART_OPT_BAND_ROWS / CART_OPT_BAND_PROBE
     int opt_plan_min_frames = 1;         // with a forced plan: launches of fewer frames still take CART_PLAN_SLABS
+    int opt_flow_gather = 0;             // CART_OPT_FLOW_GATHER
     int opt_spec = 0;                    // CART_OPT_SPEC_* bits: upstream variants of S8 / S7 (default: the oracle's spec)
     std::mutex mu;
     std::condition_variable cv;
@@ -132,7 +134,7 @@ class SlotLease {
 };
 
 // The workspaces a first call allocates: *ws = [max_inflight][bytes_per_slot], recorded in e->bufs; returns at once when *ws is
-// set.  `zero` clears the new buffer and waits for that (the component-table scratch).  The caller of the _locked form holds e->mu.
+// set.  `zero` clears the new buffer and waits for that (the component-table scratch, the flow pyramid's census padding).  The caller of the _locked form holds e->mu.
 int ensure_ws_locked(cart_engine *e, void **ws, size_t bytes_per_slot, bool zero);
 template <typename T>
 int ensure_ws(cart_engine *e, T **ws, size_t bytes_per_slot, bool zero = false) {

@@ -224,7 +224,13 @@ int launch_pf_fit(const PfFitArgs &a, hipStream_t s);   // returns the number of
 
 // ---- optical flow (flow_kernels.hip) ----
 void launch_block_flow(const uint32_t *cen_cur, const uint32_t *cen_prev, const Geometry &g, int radius, int block, int16_t *flow,
-                       size_t flow_step, hipStream_t s);
+                       size_t flow_step, hipStream_t s, int scale = 32);   // flow = scale * (u, v): 32 = S10.5, 1 = whole pixels
+// ---- coarse-to-fine flow (flow_pyramid_kernels.hip); level flows are tight s16 [h][w][2] in whole pixels ----
+void launch_flow_downsample(const uint8_t *src_c, const uint8_t *src_p, int sw, int sh, uint8_t *dst_c, uint8_t *dst_p, hipStream_t s);
+// g = the level's geometry; coarse = flow of the next coarser level (coarse_w wide); out32 non-null: also the S10.5 image of the caller
+void launch_flow_refine(const uint32_t *cen_cur, const uint32_t *cen_prev, const Geometry &g, const int16_t *coarse, int coarse_w, int refine_radius,
+                        int block, bool force_gather, int16_t *flow, int16_t *out32, size_t out32_step, hipStream_t s);
+void launch_flow_median(const int16_t *in, int w, int h, bool filter, int16_t *out, int16_t *out32, size_t out32_step, hipStream_t s);
 
 void launch_resize_linear(const uint8_t *src, size_t sstep, int sw, int sh, int channels, uint8_t *dst, size_t dstep, int dw, int dh, hipStream_t s);
 // ---- ORB features (orb_kernels.hip) ----

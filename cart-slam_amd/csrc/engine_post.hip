@@ -347,6 +347,138 @@ int cart_optical_flow(cart_engine *e, const uint8_t *cur, size_t cur_step, const
     return 0;
 }
 
+// ---- coarse-to-fine optical flow (spec S21) ----
+namespace {
+constexpr int kFlowMaxLevels = 6, kFlowMinW = 24, kFlowMinH = 16;
+
+int flow_level_sizes(int w, int h, int levels, int *lw, int *lh) {
+    int n = 1, cw = w, ch = h;
+    if (lw) lw[0] = w;
+    if (lh) lh[0] = h;
+    while (n < levels) {
+        const int nw = (cw + 1) >> 1, nh = (ch + 1) >> 1;
+        if (nw < kFlowMinW || nh < kFlowMinH) break;
+        cw = nw; ch = nh;
+        if (lw) lw[n] = cw;
+        if (lh) lh[n] = ch;
+        ++n;
+    }
+    return n;
+}
+
+// One slot of the pyramid workspace, laid out for the most levels a call may ask for (every region 256-byte aligned).
+struct FlowPyrLayout {
+    int n;                          // levels of the kFlowMaxLevels plan
+    Geometry g[kFlowMaxLevels];     // w, h, npx, cpitch, cpadl, census_elems of a level: what launch_census and the flow kernels read
+    size_t gray_c[kFlowMaxLevels], gray_p[kFlowMaxLevels], cen_c[kFlowMaxLevels], cen_p[kFlowMaxLevels];
+    size_t raw[kFlowMaxLevels], flow[kFlowMaxLevels];   // winners before the median / the level's flow, s16 [h][w][2]
+    size_t sink, scratch;           // launch_census also writes a gray copy (levels >= 1: of its own input) and resets a right-view plane
+    size_t bytes;
+
+    explicit FlowPyrLayout(const Geometry &eg) {
+        int lw[kFlowMaxLevels], lh[kFlowMaxLevels];
+        n = flow_level_sizes(eg.w, eg.h, kFlowMaxLevels, lw, lh);
+        size_t off = 0;
+        auto take = [&off](size_t b) { const size_t at = off; off += (b + 255) & ~(size_t)255; return at; };
+        for (int l = 0; l < n; ++l) {
+            Geometry &q = g[l];
+            q = Geometry{};
+            q.w = lw[l]; q.h = lh[l];
+            q.cpadl = 16;                                  // census rows: 16 zero features left, at least 16 right
+            q.cpitch = ((q.cpadl + q.w + 16 + 15) / 16) * 16;
+            q.npx = (size_t)q.w * q.h;
+            q.census_elems = (size_t)q.h * q.cpitch;
+            gray_c[l] = take(q.npx); gray_p[l] = take(q.npx);
+            cen_c[l] = take(q.census_elems * 4); cen_p[l] = take(q.census_elems * 4);
+            raw[l] = take(q.npx * 4); flow[l] = take(q.npx * 4);
+        }
+        sink = take(2 * g[n > 1 ? 1 : 0].npx);
+        scratch = take(g[0].npx * 4);
+        bytes = off;
+    }
+};
+
+struct FlowPyrLast { const cart_engine *e = nullptr; int slot = 0, levels = 0; };
+thread_local FlowPyrLast g_flow_last;   // cart_flow_debug_level
+}  // namespace
+
+void cart_flow_default_params(cart_flow_params *p) {
+    if (p) *p = cart_flow_params{4, 4, 2, 2, 1};
+}
+
+int cart_flow_pyramid_levels(int width, int height, int levels, int *level_w, int *level_h) {
+    if (width < 1 || height < 1 || levels < 1 || levels > kFlowMaxLevels) return fail("bad size, or levels not in [1, 6]");
+    return flow_level_sizes(width, height, levels, level_w, level_h);
+}
+
+int cart_optical_flow_pyramid(cart_engine *e, const uint8_t *cur, size_t cur_step, const uint8_t *prev, size_t prev_step, int channels,
+                              const cart_flow_params *fp, int16_t *flow, size_t flow_step, void *stream_) {
+    if (!e) return fail("engine is NULL");
+    if (!cur || !prev || !flow || !fp) return fail("NULL pointer");
+    if (channels != 1 && channels != 3) return fail("channels must be 1 (gray) or 3 (BGR)");
+    if (fp->levels < 1 || fp->levels > kFlowMaxLevels) return fail("levels must be in [1, 6]");
+    if (fp->radius < 1 || fp->radius > 16) return fail("radius must be in [1, 16]");
+    if (fp->refine_radius < 1 || fp->refine_radius > 4) return fail("refine_radius must be in [1, 4]");
+    if (fp->block < 1 || fp->block > 3) return fail("block must be in [1, 3]");
+    if (fp->median != 0 && fp->median != 1) return fail("median must be 0 or 1");
+    const Geometry &g = e->g;
+    if (cur_step < (size_t)g.w * channels || prev_step < (size_t)g.w * channels) return fail("input step smaller than a row");
+    if (flow_step < (size_t)g.w * 4 || (flow_step & 3) || (reinterpret_cast<uintptr_t>(flow) & 3)) return fail("bad step");
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    HIP_TRY(hipSetDevice(e->params.device_id));
+    const FlowPyrLayout L(g);
+    const int n = std::min(fp->levels, L.n);   // = flow_level_sizes(w, h, levels): the plans share their first levels
+    // zeroed once: nothing ever writes the padding left and right of a census row
+    if (ensure_ws(e, &e->flow_pyr_ws, L.bytes, true)) return -1;
+    bool gather;
+    { std::lock_guard<std::mutex> lk(e->mu); gather = e->opt_flow_gather != 0; }
+    SlotLease l;
+    if (l.begin(e, 1, stream)) return -1;
+    g_flow_last = FlowPyrLast{e, l.s0, n};
+    uint8_t *ws = e->flow_pyr_ws + (size_t)l.s0 * L.bytes;
+    auto u32 = [ws](size_t off) { return reinterpret_cast<uint32_t *>(ws + off); };
+    auto s16 = [ws](size_t off) { return reinterpret_cast<int16_t *>(ws + off); };
+    launch_census(strided_images(cur, cur_step, 0), strided_images(prev, prev_step, 0), channels, 1, ws + L.gray_c[0], ws + L.gray_p[0], u32(L.cen_c[0]),
+                  u32(L.cen_p[0]), u32(L.scratch), L.g[0], stream);
+    for (int k = 1; k < n; ++k) {
+        const Geometry &q = L.g[k];
+        launch_flow_downsample(ws + L.gray_c[k - 1], ws + L.gray_p[k - 1], L.g[k - 1].w, L.g[k - 1].h, ws + L.gray_c[k], ws + L.gray_p[k], stream);
+        launch_census(strided_images(ws + L.gray_c[k], (size_t)q.w, 0), strided_images(ws + L.gray_p[k], (size_t)q.w, 0), 1, 1, ws + L.sink,
+                      ws + L.sink + q.npx, u32(L.cen_c[k]), u32(L.cen_p[k]), u32(L.scratch), q, stream);
+    }
+    // Coarsest level first.  A level's search writes its winners to raw[k] and the median makes flow[k] of them; without the median the
+    // search writes flow[k] itself.  Whatever makes flow[0] also writes the caller's S10.5 image -- the S15 kernel cannot write both,
+    // so a single level without the median takes the median kernel as a plain copy.
+    for (int k = n - 1; k >= 0; --k) {
+        const Geometry &q = L.g[k];
+        const bool coarsest = k == n - 1, second = fp->median || (coarsest && k == 0);
+        int16_t *win = s16(second ? L.raw[k] : L.flow[k]);
+        int16_t *out32 = k == 0 ? flow : nullptr;
+        if (coarsest) launch_block_flow(u32(L.cen_c[k]), u32(L.cen_p[k]), q, fp->radius, fp->block, win, (size_t)q.w * 4, stream, 1);
+        else launch_flow_refine(u32(L.cen_c[k]), u32(L.cen_p[k]), q, s16(L.flow[k + 1]), L.g[k + 1].w, fp->refine_radius, fp->block, gather, win,
+                                second ? nullptr : out32, flow_step, stream);
+        if (second) launch_flow_median(win, q.w, q.h, fp->median != 0, s16(L.flow[k]), out32, flow_step, stream);
+    }
+    hipError_t err = hipGetLastError();
+    if (err != hipSuccess) return fail(std::string("kernel launch failed: ") + hipGetErrorString(err));
+    return 0;
+}
+
+int cart_flow_debug_level(cart_engine *e, int level, int what, void *host_dst, size_t bytes) {
+    if (!e || !host_dst) return fail("bad arguments");
+    if (what < 0 || what > 2) return fail("what must be 0 (cur image), 1 (prev image) or 2 (flow)");
+    if (g_flow_last.e != e || !e->flow_pyr_ws) return fail("this thread has made no cart_optical_flow_pyramid call on this engine");
+    if (level < 0 || level >= g_flow_last.levels) return fail("that call did not build this level");
+    const FlowPyrLayout L(e->g);
+    const size_t want = L.g[level].npx * (what == 2 ? 4 : 1);
+    if (bytes != want) return fail("bytes must be the size of the level");
+    HIP_TRY(hipSetDevice(e->params.device_id));
+    HIP_TRY(hipDeviceSynchronize());
+    const size_t off = what == 0 ? L.gray_c[level] : what == 1 ? L.gray_p[level] : L.flow[level];
+    HIP_TRY(hipMemcpy(host_dst, e->flow_pyr_ws + (size_t)g_flow_last.slot * L.bytes + off, want, hipMemcpyDeviceToHost));
+    return 0;
+}
+
 int cart_resize_linear(int device_id, const uint8_t *src, size_t src_step, int sw, int sh, int channels, uint8_t *dst, size_t dst_step, int dw,
                        int dh, void *stream_) {
     if (!src || !dst) return fail("NULL image pointer");

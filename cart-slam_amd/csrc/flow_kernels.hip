@@ -26,7 +26,7 @@ __device__ __forceinline__ unsigned wave_shift(unsigned v) {
 
 template <int B>
 __global__ __launch_bounds__(256) void block_flow_kernel(const uint32_t *cen_cur, const uint32_t *cen_prev, int cpitch, int cpadl,
-                                                         int w, int h, int radius, int16_t *flow, size_t flow_step) {
+                                                         int w, int h, int radius, int scale, int16_t *flow, size_t flow_step) {
     extern __shared__ uint32_t s_prev[];   // [FT_ROWS + 2B + 2R][64 + 2R]: tile position (ty, tx) = image (y0-B-R+ty, x0-B-R+tx)
     constexpr int WIN = 2 * B + 1, OUT_W = 64 - 2 * B;
     const int R = radius;
@@ -77,20 +77,20 @@ __global__ __launch_bounds__(256) void block_flow_kernel(const uint32_t *cen_cur
             }
         if (lane >= B && lane < 64 - B && xc < w) {
             int16_t *row = reinterpret_cast<int16_t *>(reinterpret_cast<uint8_t *>(flow) + (size_t)y * flow_step);
-            *reinterpret_cast<short2 *>(row + 2 * xc) = make_short2((short)(bu * 32), (short)(bv * 32));
+            *reinterpret_cast<short2 *>(row + 2 * xc) = make_short2((short)(bu * scale), (short)(bv * scale));   // scale 32: S10.5
         }
     }
 }
 
 void launch_block_flow(const uint32_t *cen_cur, const uint32_t *cen_prev, const Geometry &g, int radius, int block, int16_t *flow,
-                       size_t flow_step, hipStream_t s) {
+                       size_t flow_step, hipStream_t s, int scale) {
     const int out_w = 64 - 2 * block;
     dim3 grid((g.w + out_w - 1) / out_w, (g.h + FT_ROWS - 1) / FT_ROWS), threads(256);
     const size_t lds = (size_t)(64 + 2 * radius) * (FT_ROWS + 2 * block + 2 * radius) * sizeof(uint32_t);
     switch (block) {
-        case 1: hipLaunchKernelGGL(block_flow_kernel<1>, grid, threads, lds, s, cen_cur, cen_prev, g.cpitch, g.cpadl, g.w, g.h, radius, flow, flow_step); break;
-        case 2: hipLaunchKernelGGL(block_flow_kernel<2>, grid, threads, lds, s, cen_cur, cen_prev, g.cpitch, g.cpadl, g.w, g.h, radius, flow, flow_step); break;
-        default: hipLaunchKernelGGL(block_flow_kernel<3>, grid, threads, lds, s, cen_cur, cen_prev, g.cpitch, g.cpadl, g.w, g.h, radius, flow, flow_step); break;
+        case 1: hipLaunchKernelGGL(block_flow_kernel<1>, grid, threads, lds, s, cen_cur, cen_prev, g.cpitch, g.cpadl, g.w, g.h, radius, scale, flow, flow_step); break;
+        case 2: hipLaunchKernelGGL(block_flow_kernel<2>, grid, threads, lds, s, cen_cur, cen_prev, g.cpitch, g.cpadl, g.w, g.h, radius, scale, flow, flow_step); break;
+        default: hipLaunchKernelGGL(block_flow_kernel<3>, grid, threads, lds, s, cen_cur, cen_prev, g.cpitch, g.cpadl, g.w, g.h, radius, scale, flow, flow_step); break;
     }
 }
 

@@ -107,8 +107,10 @@ void applyModuleConfig(const Value &modulesConfig, std::shared_ptr<System> syste
                                                                           (unsigned)get(moduleConfig, "temporal_smoothing_distance", CARTSLAM_PLANE_TEMPORAL_DISTANCE_DEFAULT));
         } else if (moduleType == "optflow_file") {  // extension: replays flow fields from <sequence>/flow/%06d.bin
             system->addModule<OpticalFlowFileModule>();
-        } else if (moduleType == "optflow") {  // cartconfig.cpp:183-185; search_radius / block_radius are extensions
-            system->addModule<ImageOpticalFlowModule>(dataSource->getImageSize(), get(moduleConfig, "search_radius", 8), get(moduleConfig, "block_radius", 2));
+        } else if (moduleType == "optflow") {  // cartconfig.cpp:183-185; every key is an extension.  pyramid_levels > 1: coarse-to-fine (spec S21)
+            const int pyramidLevels = get(moduleConfig, "pyramid_levels", 1);
+            system->addModule<ImageOpticalFlowModule>(dataSource->getImageSize(), get(moduleConfig, "search_radius", 8), get(moduleConfig, "block_radius", 2),
+                                                      pyramidLevels, get(moduleConfig, "refine_radius", 2), get(moduleConfig, "median", pyramidLevels > 1));
         } else if (moduleType == "planefit") {  // extension key "seed" (default 0): the reference seeds from std::random_device
             system->addModule<SuperPixelPlaneFitModule>((uint64_t)get(moduleConfig, "seed", 0));
         } else if (moduleType == "planecluster") {

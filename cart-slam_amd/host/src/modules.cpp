@@ -591,10 +591,13 @@ void SuperPixelDisparityPlaneSegmentationModule::updatePlaneParameters(System &s
 }
 
 // ---------------------------------------------------------------- optical flow (optflow.cpp:52-140)
-ImageOpticalFlowModule::ImageOpticalFlowModule(const Size imageRes, int searchRadius, int blockRadius)
-    : SyncWrapperSystemModule("ImageOpticalFlow"), searchRadius(searchRadius), blockRadius(blockRadius) {
+ImageOpticalFlowModule::ImageOpticalFlowModule(const Size imageRes, int searchRadius, int blockRadius, int pyramidLevels, int refineRadius, bool median)
+    : SyncWrapperSystemModule("ImageOpticalFlow"), searchRadius(searchRadius), blockRadius(blockRadius), pyramidLevels(pyramidLevels),
+      refineRadius(refineRadius), median(median) {
     if (searchRadius < 1 || searchRadius > 16) throw std::invalid_argument("search_radius must be in [1, 16]");
     if (blockRadius < 1 || blockRadius > 3) throw std::invalid_argument("block_radius must be in [1, 3]");
+    if (pyramidLevels < 1 || pyramidLevels > 6) throw std::invalid_argument("pyramid_levels must be in [1, 6]");
+    if (refineRadius < 1 || refineRadius > 4) throw std::invalid_argument("refine_radius must be in [1, 4]");
     this->providesData.push_back(CARTSLAM_KEY_OPTFLOW);
     engine = std::make_shared<EngineHandle>(imageRes, paramsFor(imageRes, 0, 0, -1, 0, 0, 10, 120, 12));
 }
@@ -608,9 +611,16 @@ system_data_t ImageOpticalFlowModule::runInternal(System &, SystemRunData &data)
         throw std::runtime_error("ImageOpticalFlowModule requires CV_8UC1 or CV_8UC3 images");
     auto flow = std::make_shared<image_t>(referenceCurrent.rows, referenceCurrent.cols, CV_16SC2);
     ScopedStream stream;
-    if (cart_optical_flow(engine->get(), referenceCurrent.ptr<uint8_t>(), referenceCurrent.step, referencePrevious.ptr<uint8_t>(), referencePrevious.step,
-                          referenceCurrent.type() == CV_8UC3 ? 3 : 1, searchRadius, blockRadius, flow->ptr<int16_t>(), flow->step, stream.s) != 0)
+    const int channels = referenceCurrent.type() == CV_8UC3 ? 3 : 1;
+    if (pyramidLevels > 1) {
+        const cart_flow_params params{pyramidLevels, searchRadius, refineRadius, blockRadius, median ? 1 : 0};
+        if (cart_optical_flow_pyramid(engine->get(), referenceCurrent.ptr<uint8_t>(), referenceCurrent.step, referencePrevious.ptr<uint8_t>(),
+                                      referencePrevious.step, channels, &params, flow->ptr<int16_t>(), flow->step, stream.s) != 0)
+            engine->fail("cart_optical_flow_pyramid");
+    } else if (cart_optical_flow(engine->get(), referenceCurrent.ptr<uint8_t>(), referenceCurrent.step, referencePrevious.ptr<uint8_t>(),
+                                 referencePrevious.step, channels, searchRadius, blockRadius, flow->ptr<int16_t>(), flow->step, stream.s) != 0) {
         engine->fail("cart_optical_flow");
+    }
     stream.wait();
     return MODULE_RETURN(CARTSLAM_KEY_OPTFLOW, flow);
 }

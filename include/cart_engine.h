@@ -89,8 +89,10 @@ enum {
     CART_OPT_SPEC_S5_TOP2 = 5,              /* 1: uniqueness tests the second-best (cost, d) only -- the top-2 wording of SURVEY.md 8a-4(4) -- instead of every
                                                disparity (the libSGM form, oracle S5); such an engine always takes plan SLABS */
     CART_OPT_BAND_ROWS = 6,                 /* K of plan BAND_UP: 4, 8 or 16 rows per band (default: the measured winner); 1 with the probe */
-    CART_OPT_BAND_PROBE = 7                 /* measurement only, 1: plan BAND_UP stores and reads all P slabs and recomputes nothing -- the two-kernel WTA's
+    CART_OPT_BAND_PROBE = 7,                /* measurement only, 1: plan BAND_UP stores and reads all P slabs and recomputes nothing -- the two-kernel WTA's
                                                work in K-row tiles (the read-rate probe of DESIGN.md 8); describe_plan then reports P slabs */
+    CART_OPT_FLOW_GATHER = 8                /* tests and measurements, 1: the refinement kernel of cart_optical_flow_pyramid never stages the previous
+                                               features in LDS and gathers them from global memory in every tile (same bits; default 0: per tile) */
 };
 int cart_engine_set_option(cart_engine *engine, int option, int value);
 int cart_engine_get_option(cart_engine *engine, int option, int *value);
@@ -452,6 +454,29 @@ int cart_orb_debug_level(cart_orb *orb, int image, int level, uint8_t *dst, size
  * radius = search range in pixels (1..16), block = half window (1..3 -> 3x3, 5x5, 7x7). */
 int cart_optical_flow(cart_engine *engine, const uint8_t *cur, size_t cur_step, const uint8_t *prev, size_t prev_step,
                       int channels, int radius, int block, int16_t *flow, size_t flow_step, void *stream);
+
+/* Coarse-to-fine form of the same stand-in (spec S21): a 2x2-mean pyramid of both frames, S2 census per level, S15 at
+ * the coarsest level (radius, block), then per finer level a search of (2 refine_radius + 1)^2 candidates around twice the coarser
+ * level's flow, optionally a 3x3 median of each flow component per level.  Integer only; reach radius * 2^(L-1) + refine_radius *
+ * (2^(L-1) - 1) pixels, no sub-pixel step (the consumers floor flow >> 5).  levels = 1, median = 0 is cart_optical_flow bit for bit. */
+typedef struct cart_flow_params {
+    int levels;         /* 1..6 requested; a level is built only while it is at least 24 x 16 */
+    int radius;         /* 1..16, full search at the coarsest level */
+    int refine_radius;  /* 1..4 */
+    int block;          /* 1..3 */
+    int median;         /* 0 | 1 */
+} cart_flow_params;
+void cart_flow_default_params(cart_flow_params *p); /* 4, 4, 2, 2, 1 */
+/* HOST only: sizes of the levels S21 builds for a width x height frame (level_w / level_h: `levels` entries, may be NULL).
+ * Returns levels_used <= levels, or -1 on bad arguments. */
+int cart_flow_pyramid_levels(int width, int height, int levels, int *level_w, int *level_h);
+/* Arguments as cart_optical_flow.  One workspace slot per call, nothing allocated after an engine's first call, asynchronous on `stream`. */
+int cart_optical_flow_pyramid(cart_engine *engine, const uint8_t *cur, size_t cur_step, const uint8_t *prev, size_t prev_step,
+                              int channels, const cart_flow_params *params, int16_t *flow, size_t flow_step, void *stream);
+/* Test access to the calling thread's last cart_optical_flow_pyramid call (synchronises the device): what = 0 level image of cur,
+ * 1 of prev (u8 [h_l][w_l]), 2 level flow (s16 [h_l][w_l][2], whole pixels, after the median when it is on).  host_dst is a HOST
+ * buffer of exactly `bytes` = the level's size.  Fails for a level that call did not build. */
+int cart_flow_debug_level(cart_engine *engine, int level, int what, void *host_dst, size_t bytes);
 
 /* replaces: cv::cuda::resize(src, dst, size, 0, 0, cv::INTER_LINEAR) as KITTIDataSource::getNextInternal applies it when the
  * configured image size differs from the files' (src/sources/kitti.cpp:169-172); oracle S16.  8-bit, channels = 1 | 3,
