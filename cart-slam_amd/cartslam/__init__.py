@@ -4,5 +4,5 @@ Only device-memory/stream plumbing, the synthetic scene generator and the frame-
 live here; all arithmetic is in the HIP library (cart-slam_amd/csrc).  Nothing here imports oracle/.
 """
 from . import _lib, synth  # noqa: F401
-from ._lib import EngineParams, Keypoint, PlaneParams, SuperpixelParams  # noqa: F401
-from .engine import INVALID, DevicePlaneSchedule, Engine, EngineError, OrbFeatures, PlaneFit, Superpixels, find_peaks, find_plane_params, orb_levels, plane_cluster  # noqa: F401
+from ._lib import EngineParams, Keypoint, Match, MatchParams, PlaneParams, SuperpixelParams  # noqa: F401
+from .engine import INVALID, MATCH_DTYPE, DevicePlaneSchedule, Engine, EngineError, OrbFeatures, OrbMatcher, PlaneFit, Superpixels, find_peaks, find_plane_params, orb_levels, plane_cluster  # noqa: F401

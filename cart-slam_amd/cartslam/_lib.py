@@ -66,6 +66,17 @@ class Keypoint(C.Structure):
     _fields_ = [(n, C.c_float) for n in ("x", "y", "size", "angle", "response")] + [("octave", C.c_int32), ("class_id", C.c_int32)]
 
 
+class Match(C.Structure):
+    # mirrors cart_match (include/cart_engine.h, spec S22)
+    _fields_ = [(n, C.c_int32) for n in ("query", "train", "distance", "second")]
+
+
+class MatchParams(C.Structure):
+    # mirrors cart_match_params (include/cart_engine.h, spec S22); the defaults are cart_match_default_params'
+    _fields_ = [("use_gate", C.c_int32)] + [(n, C.c_float) for n in ("dx_min", "dx_max", "dy_min", "dy_max")] + \
+               [(n, C.c_int32) for n in ("max_octave_diff", "max_distance", "ratio", "cross_check")]
+
+
 PLACE_MODES = {0: "unknown", 1: "fast", 2: "mixed", 3: "uniform"}                                       # CART_PLACE_MODE_*
 PLACE_STOPS = {0: "nothing to do", 1: "fast set found", 2: "uniform", 3: "tries", 4: "time", 5: "memory"}   # CART_PLACE_STOP_*
 
@@ -129,6 +140,10 @@ PROTOTYPES = {
     "cart_orb_levels": (_i, [_i, _i, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
     "cart_orb_detect": (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_sz), _i, _i, _i, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_sz), _vp, _vp]),
     "cart_orb_debug_level": (_i, [_vp, _i, _i, _vp, _sz, C.POINTER(C.c_int32), _vp]),
+    "cart_match_default_params": (None, [C.POINTER(MatchParams)]),
+    "cart_matcher_create": (_i, [_vp, _i, C.POINTER(_vp)]),
+    "cart_matcher_destroy": (None, [_vp]),
+    "cart_matcher_match": (_i, [_vp, C.POINTER(MatchParams), _vp, _sz, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp]),
     "cart_optical_flow": (_i, [_vp, _vp, _sz, _vp, _sz, _i, _i, _i, _vp, _sz, _vp]),
     "cart_flow_default_params": (None, [C.POINTER(FlowParams)]),
     "cart_flow_pyramid_levels": (_i, [_i, _i, _i, C.POINTER(_i), C.POINTER(_i)]),

@@ -9,7 +9,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import EngineParams, PlaneParams, SuperpixelParams
+from ._lib import EngineParams, MatchParams, PlaneParams, SuperpixelParams
 
 INVALID = -32768  # CARTSLAM_DISPARITY_INVALID, reference include/modules/disparity.hpp:17
 
@@ -702,6 +702,82 @@ class OrbFeatures(_DeviceObject):
         self._check(self._lib.cart_orb_debug_level(self._h, int(image), int(level), C.c_void_p(dst.data_ptr()), w, C.byref(n), _stream_ptr()),
                     "cart_orb_debug_level")
         return dst, n.value
+
+
+MATCH_DTYPE = np.dtype([("query", "<i4"), ("train", "<i4"), ("distance", "<i4"), ("second", "<i4")])   # cart_match
+
+
+def match_params(**fields):
+    """cart_match_default_params (spec S22) with the given fields replaced."""
+    p = MatchParams()
+    _lib.load().cart_match_default_params(C.byref(p))
+    for k, v in fields.items():
+        if k not in dict(MatchParams._fields_):
+            raise ValueError(f"cart_match_params has no field {k}")
+        setattr(p, k, v)
+    return p
+
+
+class OrbMatcher(_DeviceObject):
+    """Brute-force matching of two sets of ORB descriptors (cart_matcher_* in the C ABI, spec S22 in DESIGN.md 7.4): best and
+    second-best Hamming distance per query under an optional position / octave gate, distance, ratio and cross-check tests."""
+    _name = "matcher"
+
+    def __init__(self, engine, max_features=_lib.ORB_DEFAULT_FEATURES):
+        self.max_features = int(max_features)
+        super().__init__(engine, self.max_features)
+
+    def _side(self, side):
+        """(keypoints, descriptors, count) -> device (keypoints or None, descriptors, int32 count [1], rows available); host arrays are uploaded."""
+        import torch
+        kp, de, cnt = side
+        if not isinstance(de, torch.Tensor):
+            de = torch.from_numpy(np.ascontiguousarray(de, dtype=np.uint8)).cuda()
+        if de.dtype != torch.uint8 or not de.is_cuda or de.dim() != 2 or de.shape[1] != _lib.ORB_DESCRIPTOR_BYTES or (de.shape[0] > 1 and de.stride(1) != 1):
+            raise EngineError("descriptors must be a uint8 CUDA tensor [n, 32] with unit column stride")
+        rows = int(de.shape[0])
+        if rows == 0:   # an empty tensor has no address: one unread row
+            de = torch.zeros((1, _lib.ORB_DESCRIPTOR_BYTES), dtype=torch.uint8, device=de.device)
+            kp = None if kp is None else torch.zeros((1, 7), dtype=torch.float32, device=de.device)
+        elif kp is not None:
+            if not isinstance(kp, torch.Tensor):
+                kp = torch.from_numpy(np.ascontiguousarray(kp).view(np.float32).reshape(-1, 7)).cuda()
+            if kp.dtype != torch.float32 or not kp.is_cuda or not kp.is_contiguous() or kp.dim() != 2 or kp.shape[1] != 7 or kp.shape[0] < rows:
+                raise EngineError("keypoints must be a contiguous float32 CUDA tensor [>= n, 7] (the cart_keypoint records)")
+        if cnt is None:
+            cnt = rows
+        if not isinstance(cnt, torch.Tensor):
+            if int(cnt) > rows:
+                raise EngineError("count exceeds the descriptor rows")
+            return kp, de, torch.tensor([int(cnt)], dtype=torch.int32, device=de.device)
+        if cnt.dtype != torch.int32 or not cnt.is_cuda or cnt.numel() != 1:
+            raise EngineError("count must be one int32 on the device")
+        if rows < self.max_features or (kp is not None and kp.shape[0] < self.max_features):
+            raise EngineError("with a device count the descriptor and keypoint tensors must hold max_features rows")
+        return kp, de, cnt
+
+    def match(self, query, train, params=None, want_forward=False):
+        """query / train = (keypoints, descriptors, count): keypoints float32 device [n, 7] (OrbFeatures.detect(raw=True)) or a
+        KEYPOINT_DTYPE array or None (gate off), descriptors uint8 [n, 32] (rows may be pitched), count = a device int32 (no host
+        round trip), an int or None (= n).  -> matches as a MATCH_DTYPE array (host), and with want_forward the int32 [nq, 4]
+        forward table (j1, d1, d2, i1(j1))."""
+        import torch
+        p = params if params is not None else match_params()
+        qk, qd, qc = self._side(query)
+        tk, td, tc = self._side(train)
+        dev = qd.device
+        matches = torch.empty((self.max_features, 4), dtype=torch.int32, device=dev)
+        n = torch.zeros(1, dtype=torch.int32, device=dev)
+        fwd = torch.empty((self.max_features, 4), dtype=torch.int32, device=dev) if want_forward else None
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None   # noqa: E731
+        step = lambda d: d.stride(0) if d.shape[0] > 1 else _lib.ORB_DESCRIPTOR_BYTES   # noqa: E731
+        self._check(self._lib.cart_matcher_match(self._h, C.byref(p), ptr(qd), step(qd), ptr(qk), ptr(qc), ptr(td), step(td), ptr(tk), ptr(tc),
+                                                 ptr(matches), ptr(n), ptr(fwd), _stream_ptr()), "cart_matcher_match")
+        both = torch.cat([n, qc.reshape(1)]).cpu().tolist()
+        out = matches[:both[0]].cpu().numpy().view(MATCH_DTYPE).reshape(-1)
+        if want_forward:
+            return out, fwd[:min(max(both[1], 0), self.max_features)].cpu().numpy()
+        return out
 
 
 def plane_cluster(planes, offsets, neighbours):

@@ -262,6 +262,22 @@ void launch_orb_pyramid_level(const OrbPlan &p, int level, const OrbOut &o, uint
 void launch_orb_detect(const OrbPlan &p, const uint8_t *pyr, OrbCand *cand, int32_t *cand_cnt, hipStream_t s);
 void launch_orb_select(const OrbPlan &p, const OrbCand *cand, const int32_t *cand_cnt, OrbCand *sel, int4 *kpi, int32_t *counts, hipStream_t s);
 void launch_orb_describe(const OrbPlan &p, const uint8_t *pyr, const int4 *kpi, const char4 *pattern, const OrbOut &o, hipStream_t s);
+// ---- ORB descriptor matching (match_kernels.hip) ----
+constexpr int kMatchRows = 128;     // rows (one lane each) of a match_pairs workgroup
+constexpr int kMatchTile = 128;     // columns staged in LDS at a time; a chunk is a whole number of tiles
+constexpr int kMatchMaxChunks = 64; // column chunks of the largest matcher: bounds the partial tables
+struct MatchArgs {
+    cart_match_params p;
+    const uint8_t *q_desc; size_t q_step; const cart_keypoint *q_kp; const int32_t *q_count;
+    const uint8_t *t_desc; size_t t_step; const cart_keypoint *t_kp; const int32_t *t_count;
+    int cap, chunk_len;   // max_features; columns per chunk
+    int2 *fwd_part;       // [chunks][cap] (best key, second distance) of every query and train chunk
+    int32_t *bwd_part;    // [chunks][cap] best key of every train row and query chunk
+    int4 *fwd;            // [cap] (j1, d1, d2, -1)
+    int32_t *bwd;         // [cap] i1(j)
+    cart_match *matches; int32_t *match_count; int32_t *forward;
+};
+void launch_match(const MatchArgs &a, hipStream_t s);
 void launch_narrow_copy(const void *src, void *dst, size_t bytes, int blocks, hipStream_t s);
 int kernel_count();
 

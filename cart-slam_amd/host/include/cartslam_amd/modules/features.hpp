@@ -20,9 +20,24 @@ static_assert(sizeof(KeyPoint) == 28, "cv::KeyPoint layout");
 class ImageFeatures {
    public:
     ImageFeatures(std::vector<KeyPoint> keypoints, image_t descriptors) : keypoints(std::move(keypoints)), descriptors(descriptors) {}
+    ImageFeatures(std::vector<KeyPoint> keypoints, image_t descriptors, image_t records, size_t countOffset, size_t keypointOffset, int capacity)
+        : keypoints(std::move(keypoints)), descriptors(descriptors), records(records), countOffset(countOffset), keypointOffset(keypointOffset),
+          capacity(capacity) {}
 
     std::vector<KeyPoint> keypoints;
     image_t descriptors;   // CV_8UC1, keypoints.size() rows of 32 bytes (device)
+
+    // What cart_orb_detect wrote for this image, still on the device and owned by the frame (empty when made from host data):
+    // the keypoint count and `capacity` keypoint records, for consumers that stay on the device (modules/matches.hpp).
+    bool onDevice() const { return !records.empty(); }
+    const int32_t *deviceCount() const { return reinterpret_cast<const int32_t *>(records.ptr<uint8_t>() + countOffset); }
+    const KeyPoint *deviceKeypoints() const { return reinterpret_cast<const KeyPoint *>(records.ptr<uint8_t>() + keypointOffset); }
+    int deviceCapacity() const { return capacity; }   // rows the descriptor image and the keypoint records hold
+
+   private:
+    image_t records;   // one row of bytes shared by both images of the frame: counts [2] int32, padding, keypoints [2][capacity]
+    size_t countOffset = 0, keypointOffset = 0;
+    int capacity = 0;
 };
 
 // Per-thread cart_orb workspaces of one module (the frames of a run may overlap).

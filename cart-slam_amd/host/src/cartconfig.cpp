@@ -14,6 +14,7 @@
 #include "cartslam_amd/modules/depth.hpp"
 #include "cartslam_amd/modules/disparity.hpp"
 #include "cartslam_amd/modules/features.hpp"
+#include "cartslam_amd/modules/matches.hpp"
 #include "cartslam_amd/modules/planefit.hpp"
 #include "cartslam_amd/modules/planeseg.hpp"
 #include "cartslam_amd/modules/superpixels.hpp"
@@ -122,6 +123,17 @@ void applyModuleConfig(const Value &modulesConfig, std::shared_ptr<System> syste
             const std::string featureType = get<std::string>(moduleConfig, "feature_type", "orb");
             if (featureType != "orb") throw std::runtime_error("Unknown feature type.");
             system->addModule<ImageFeatureDetectorModule>(get(moduleConfig, "nfeatures", CARTSLAM_OPTION_KEYPOINTS));
+        } else if (moduleType == "orb_matches") {  // extension (spec S22): stereo and temporal matches of the orb_features module's output
+            FeatureMatcherOptions o;
+            o.stereo = get(moduleConfig, "stereo", o.stereo);
+            o.temporal = get(moduleConfig, "temporal", o.temporal);
+            o.maxDistance = get(moduleConfig, "max_distance", o.maxDistance);
+            o.ratio = get(moduleConfig, "ratio", o.ratio);
+            o.crossCheck = get(moduleConfig, "cross_check", o.crossCheck);
+            o.maxDisparity = (float)get(moduleConfig, "max_disparity", (double)o.maxDisparity);
+            o.maxDy = (float)get(moduleConfig, "max_dy", (double)o.maxDy);
+            o.searchRadius = (float)get(moduleConfig, "search_radius", (double)o.searchRadius);
+            system->addModule<FeatureMatcherModule>(o);
         } else if (endsWith(moduleType, "_visualization")) {
             std::cerr << "[cartconfig] skipping GUI module type " << moduleType << " (out of scope)\n";
         } else {

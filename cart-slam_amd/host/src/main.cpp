@@ -17,6 +17,7 @@
 #include "cartslam_amd/cartconfig.hpp"
 #include "cartslam_amd/modules/depth.hpp"
 #include "cartslam_amd/modules/features.hpp"
+#include "cartslam_amd/modules/matches.hpp"
 #include "cartslam_amd/timing.hpp"
 #include "cartslam_amd/modules/planefit.hpp"
 #include "cartslam_amd/modules/planeseg.hpp"
@@ -88,6 +89,14 @@ int main(int argc, char **argv) {
                         if (!d.empty()) side.second->descriptors.download(d.data(), CART_ORB_DESCRIPTOR_BYTES);
                         std::ofstream o(base + "_descriptors.bin", std::ios::binary);
                         o.write(reinterpret_cast<const char *>(d.data()), (std::streamsize)d.size());
+                    }
+                }
+                if (run->hasData(CARTSLAM_KEY_FEATURE_MATCHES)) {   // 16-byte cart_match records; an empty list gives an empty file
+                    auto fm = run->getData<cart::FeatureMatches>(CARTSLAM_KEY_FEATURE_MATCHES);
+                    const std::pair<const char *, const std::vector<cart::FeatureMatch> *> lists[] = {{"stereo", &fm->stereo}, {"temporal", &fm->temporal}};
+                    for (const auto &list : lists) {
+                        std::ofstream o(dump + "/" + std::to_string(id) + "_" + CARTSLAM_KEY_FEATURE_MATCHES + "_" + list.first + ".bin", std::ios::binary);
+                        o.write(reinterpret_cast<const char *>(list.second->data()), (std::streamsize)(list.second->size() * sizeof(cart::FeatureMatch)));
                     }
                 }
                 if (run->hasData(CARTSLAM_KEY_PLANES_EQ_LABEL_PLANES)) {   // f64 [max_label + 1][4]

@@ -447,6 +447,45 @@ int cart_orb_detect(cart_orb *orb, int n_images, const uint8_t *const *images, c
  * not read; synchronises `stream`).  Fails for a level that call did not build. */
 int cart_orb_debug_level(cart_orb *orb, int image, int level, uint8_t *dst, size_t dst_step, int32_t *n_candidates, void *stream);
 
+/* ---- ORB descriptor matching: stereo and temporal correspondences (spec S22) --------------------------------
+ * An extension: the reference's feature module only draws its keypoints.  Brute-force Hamming matching of two sets of 256-bit
+ * descriptors (what cart_orb_detect writes), integer and deterministic:
+ *   d(i, j) = popcount(Q_i xor T_j).  With use_gate, a pair (i, j) is admissible iff dx_min <= q.x - t.x <= dx_max, dy_min <=
+ *   q.y - t.y <= dy_max (one float32 subtraction each, bounds inclusive, NaN fails) and max_octave_diff < 0 or
+ *   |q.octave - t.octave| <= max_octave_diff (int32 arithmetic); without it every pair is.
+ *   Forward: (d1, j1) of the minimum d * 65536 + j over the admissible j of query i (ties go to the lowest train index), d2 = the
+ *   minimum d over admissible j != j1 (may equal d1), -1 without one; j1 = d1 = d2 = -1 without any admissible j.
+ *   Backward: i1(j) = the i of the minimum d * 65536 + i over the admissible i of train j.
+ *   Query i is accepted iff j1 >= 0, d1 <= max_distance, (ratio == 0 or d2 < 0 or 100 d1 < ratio d2) and (cross_check == 0 or
+ *   i1(j1) == i). */
+typedef struct cart_match {
+    int32_t query, train, distance, second;   /* i, j1, d1, d2 */
+} cart_match;
+typedef struct cart_match_params {
+    int32_t use_gate;                         /* 0 | 1 */
+    float dx_min, dx_max, dy_min, dy_max;     /* inclusive bounds on q - t */
+    int32_t max_octave_diff;                  /* < 0: no octave test */
+    int32_t max_distance;                     /* 0..256 */
+    int32_t ratio;                            /* 0..100, 0 = off */
+    int32_t cross_check;                      /* 0 | 1 */
+} cart_match_params;
+void cart_match_default_params(cart_match_params *p); /* gate off, octave test off, 64, 80, 1 */
+
+typedef struct cart_matcher cart_matcher;
+/* Workspaces for sets of up to max_features (1..65536) descriptors each; nothing is allocated per call. */
+int cart_matcher_create(cart_engine *engine, int max_features, cart_matcher **out);
+/* Keeps the device it was created on, so it may be destroyed after its engine. */
+void cart_matcher_destroy(cart_matcher *matcher);
+/* Query set q, train set t: descriptor rows of 32 bytes q_step / t_step (>= 32) bytes apart, cart_keypoint records (4-byte
+ * aligned; may be NULL when use_gate is 0) and the set sizes as DEVICE int32 (what cart_orb_detect writes; clamped to [0,
+ * max_features]; rows at or beyond a size are never read).  Device outputs: matches [max_features] = the accepted queries in
+ * ascending query order, match_count = their number, forward (may be NULL) = int32 [max_features][4], of which the first
+ * q_count rows are written: (j1, d1, d2, i1(j1)), entry 3 = -1 when cross_check is 0 or j1 < 0.  No host synchronisation. */
+int cart_matcher_match(cart_matcher *matcher, const cart_match_params *params, const uint8_t *q_desc, size_t q_step,
+                       const cart_keypoint *q_kp, const int32_t *q_count, const uint8_t *t_desc, size_t t_step,
+                       const cart_keypoint *t_kp, const int32_t *t_count, cart_match *matches, int32_t *match_count,
+                       int32_t *forward, void *stream);
+
 /* Stand-in for ImageOpticalFlowModule's device work (src/modules/optflow.cpp:96-140: cvtColor x2 +
  * cv::cuda::NvidiaOpticalFlow_2_0::calc(current, previous), NVIDIA fixed-function hardware): dense census block
  * matching (oracle S15).  cur / prev = the reference images of frame id and id-1 (1-channel gray or 3-channel BGR),
