@@ -77,6 +77,30 @@ class MatchParams(C.Structure):
                [(n, C.c_int32) for n in ("max_octave_diff", "max_distance", "ratio", "cross_check")]
 
 
+class EgoCamera(C.Structure):
+    # mirrors cart_ego_camera (include/cart_engine.h, spec S23)
+    _fields_ = [(n, C.c_double) for n in ("fx", "fy", "cx", "cy", "baseline")]
+
+
+class EgoParams(C.Structure):
+    # mirrors cart_ego_params (include/cart_engine.h, spec S23); the defaults are cart_ego_default_params'
+    _fields_ = [("min_disparity", C.c_double), ("inlier_threshold", C.c_double), ("hypotheses", C.c_int32), ("refine_iterations", C.c_int32)]
+
+
+class EgoResult(C.Structure):
+    # mirrors cart_ego_result (include/cart_engine.h, spec S23)
+    _fields_ = [("R", C.c_double * 9), ("t", C.c_double * 3), ("rms", C.c_double)] + \
+               [(n, C.c_int32) for n in ("status", "n_correspondences", "n_inliers", "best_hypothesis")]
+
+
+class EgoHypothesis(C.Structure):
+    # mirrors cart_ego_hypothesis (include/cart_engine.h, spec S23)
+    _fields_ = [("qerr", C.c_uint64), ("count", C.c_int32), ("skipped", C.c_int32)]
+
+
+EGO_MAX_HYPOTHESES, EGO_MAX_REFINE = 1024, 16   # CART_EGO_MAX_*
+
+
 PLACE_MODES = {0: "unknown", 1: "fast", 2: "mixed", 3: "uniform"}                                       # CART_PLACE_MODE_*
 PLACE_STOPS = {0: "nothing to do", 1: "fast set found", 2: "uniform", 3: "tries", 4: "time", 5: "memory"}   # CART_PLACE_STOP_*
 
@@ -144,6 +168,12 @@ PROTOTYPES = {
     "cart_matcher_create": (_i, [_vp, _i, C.POINTER(_vp)]),
     "cart_matcher_destroy": (None, [_vp]),
     "cart_matcher_match": (_i, [_vp, C.POINTER(MatchParams), _vp, _sz, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "cart_ego_default_params": (None, [C.POINTER(EgoParams)]),
+    "cart_ego_create": (_i, [_vp, _i, C.POINTER(_vp)]),
+    "cart_ego_destroy": (None, [_vp]),
+    "cart_ego_triangulate": (_i, [_vp, C.POINTER(EgoCamera), C.POINTER(EgoParams), _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "cart_ego_estimate": (_i, [_vp, C.POINTER(EgoCamera), C.POINTER(EgoParams), _vp, _vp, _vp, _vp, _vp, C.c_uint64, C.c_uint64, _vp, _vp, _vp]),
+    "cart_ego_debug_hypotheses": (_i, [_vp, C.POINTER(EgoHypothesis), _i, C.POINTER(_i), _vp]),
     "cart_optical_flow": (_i, [_vp, _vp, _sz, _vp, _sz, _i, _i, _i, _vp, _sz, _vp]),
     "cart_flow_default_params": (None, [C.POINTER(FlowParams)]),
     "cart_flow_pyramid_levels": (_i, [_i, _i, _i, C.POINTER(_i), C.POINTER(_i)]),

@@ -9,7 +9,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import EngineParams, MatchParams, PlaneParams, SuperpixelParams
+from ._lib import EgoCamera, EgoParams, EngineParams, MatchParams, PlaneParams, SuperpixelParams
 
 INVALID = -32768  # CARTSLAM_DISPARITY_INVALID, reference include/modules/disparity.hpp:17
 
@@ -778,6 +778,110 @@ class OrbMatcher(_DeviceObject):
         if want_forward:
             return out, fwd[:min(max(both[1], 0), self.max_features)].cpu().numpy()
         return out
+
+
+EGO_RESULT_DTYPE = np.dtype([("R", "<f8", 9), ("t", "<f8", 3), ("rms", "<f8"), ("status", "<i4"), ("n_correspondences", "<i4"),
+                             ("n_inliers", "<i4"), ("best_hypothesis", "<i4")])   # cart_ego_result
+EGO_HYPOTHESIS_DTYPE = np.dtype([("qerr", "<u8"), ("count", "<i4"), ("skipped", "<i4")])   # cart_ego_hypothesis
+
+
+def ego_params(**fields):
+    """cart_ego_default_params (spec S23) with the given fields replaced."""
+    p = EgoParams()
+    _lib.load().cart_ego_default_params(C.byref(p))
+    for k, v in fields.items():
+        if k not in dict(EgoParams._fields_):
+            raise ValueError(f"cart_ego_params has no field {k}")
+        setattr(p, k, v)
+    return p
+
+
+class EgoMotion(_DeviceObject):
+    """Stereo visual odometry from ORB matches (cart_ego_* in the C ABI, spec S23 in DESIGN.md 7.5): landmarks from the stereo
+    matches of a frame, then the relative pose p_cur = R p_prev + t from the temporal matches between two frames' landmarks."""
+    _name = "ego"
+
+    def __init__(self, engine, camera, max_features=_lib.ORB_DEFAULT_FEATURES):
+        """camera = EgoCamera or (fx, fy, cx, cy, baseline)."""
+        self.max_features = int(max_features)
+        self.camera = camera if isinstance(camera, EgoCamera) else EgoCamera(*[float(v) for v in camera])
+        super().__init__(engine, self.max_features)
+
+    def _rows(self, a, dtype, width, what):
+        """A host array or device tensor of records -> (device tensor [max_features, width] of torch `dtype`, rows given)."""
+        import torch
+        if isinstance(a, torch.Tensor):
+            if a.dtype != dtype or not a.is_cuda or not a.is_contiguous() or a.dim() != 2 or a.shape[1] != width or a.shape[0] < self.max_features:
+                raise EngineError(f"{what} on the device must be a contiguous [>= max_features, {width}] tensor of {dtype}")
+            return a, int(a.shape[0])
+        np_dtype = {torch.float32: np.float32, torch.int32: np.int32, torch.float64: np.float64}[dtype]
+        host = np.ascontiguousarray(a)
+        host = host.view(np_dtype).reshape(-1, width) if host.dtype.fields else np.asarray(host, np_dtype).reshape(-1, width)
+        if len(host) > self.max_features:
+            raise EngineError(f"{what}: more than max_features rows")
+        full = np.zeros((self.max_features, width), np_dtype)
+        full[:len(host)] = host
+        return torch.from_numpy(full).cuda(), len(host)
+
+    def _count(self, cnt, rows, given_on_device):
+        import torch
+        if isinstance(cnt, torch.Tensor):
+            if cnt.dtype != torch.int32 or not cnt.is_cuda or cnt.numel() != 1:
+                raise EngineError("a count must be one int32 on the device")
+            return cnt
+        if cnt is None:
+            if given_on_device:
+                raise EngineError("a device list needs its count")
+            cnt = rows
+        return torch.tensor([int(cnt)], dtype=torch.int32, device="cuda")
+
+    def triangulate(self, kp_left, kp_right, stereo_matches, left_count=None, stereo_count=None, params=None, raw=False):
+        """Keypoints as KEYPOINT_DTYPE arrays or float32 device [max_features, 7] records, matches as a MATCH_DTYPE array or an
+        int32 device [max_features, 4] tensor, counts as ints, device int32 or None (= the rows of a host array).
+        -> landmarks float64 [left_count, 4] (host), or with raw=True the device tensor [max_features, 4] with no host round trip."""
+        import torch
+        p = params if params is not None else ego_params()
+        kl, nl = self._rows(kp_left, torch.float32, 7, "keypoints")
+        kr, _ = self._rows(kp_right, torch.float32, 7, "keypoints")
+        sm, ns = self._rows(stereo_matches, torch.int32, 4, "matches")
+        lc = self._count(left_count, nl, isinstance(kp_left, torch.Tensor))
+        sc = self._count(stereo_count, ns, isinstance(stereo_matches, torch.Tensor))
+        lm = torch.empty((self.max_features, 4), dtype=torch.float64, device=kl.device)
+        ptr = lambda t: C.c_void_p(t.data_ptr())   # noqa: E731
+        self._check(self._lib.cart_ego_triangulate(self._h, C.byref(self.camera), C.byref(p), ptr(kl), ptr(kr), ptr(lc), ptr(sm), ptr(sc), ptr(lm),
+                                                   _stream_ptr()), "cart_ego_triangulate")
+        if raw:
+            return lm
+        return lm[:min(max(int(lc.item()), 0), self.max_features)].cpu().numpy()
+
+    def estimate(self, cur_landmarks, cur_kp_left, prev_landmarks, temporal_matches, temporal_count=None, seed=0, frame_id=0, params=None,
+                 want_mask=False, raw=False):
+        """Landmarks as float64 [n, 4] arrays or the device tensors of triangulate(raw=True), the current frame's left keypoints and
+        the temporal matches as in triangulate.  -> the result as an EGO_RESULT_DTYPE array of one record (host), with want_mask also
+        the int32 inlier mask [max_features]; raw=True returns the device tensors (result as 120 bytes) with no host round trip."""
+        import torch
+        p = params if params is not None else ego_params()
+        cl, _ = self._rows(cur_landmarks, torch.float64, 4, "landmarks")
+        pl, _ = self._rows(prev_landmarks, torch.float64, 4, "landmarks")
+        kl, _ = self._rows(cur_kp_left, torch.float32, 7, "keypoints")
+        tm, nt = self._rows(temporal_matches, torch.int32, 4, "matches")
+        tc = self._count(temporal_count, nt, isinstance(temporal_matches, torch.Tensor))
+        res = torch.zeros(EGO_RESULT_DTYPE.itemsize // 8, dtype=torch.float64, device=cl.device)
+        mask = torch.empty(self.max_features, dtype=torch.int32, device=cl.device) if want_mask else None
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None   # noqa: E731
+        self._check(self._lib.cart_ego_estimate(self._h, C.byref(self.camera), C.byref(p), ptr(cl), ptr(kl), ptr(pl), ptr(tm), ptr(tc),
+                                                C.c_uint64(int(seed)), C.c_uint64(int(frame_id)), ptr(res), ptr(mask), _stream_ptr()), "cart_ego_estimate")
+        if raw:
+            return (res, mask) if want_mask else res
+        out = res.cpu().numpy().view(EGO_RESULT_DTYPE).reshape(-1)
+        return (out, mask.cpu().numpy()) if want_mask else out
+
+    def debug_hypotheses(self):
+        """The (qerr, count, skipped) table of the last estimate call -> EGO_HYPOTHESIS_DTYPE array [hypotheses] (synchronises)."""
+        buf = (_lib.EgoHypothesis * _lib.EGO_MAX_HYPOTHESES)()
+        n = C.c_int(0)
+        self._check(self._lib.cart_ego_debug_hypotheses(self._h, buf, _lib.EGO_MAX_HYPOTHESES, C.byref(n), _stream_ptr()), "cart_ego_debug_hypotheses")
+        return np.frombuffer(buf, EGO_HYPOTHESIS_DTYPE, n.value).copy()
 
 
 def plane_cluster(planes, offsets, neighbours):

@@ -278,6 +278,33 @@ struct MatchArgs {
     cart_match *matches; int32_t *match_count; int32_t *forward;
 };
 void launch_match(const MatchArgs &a, hipStream_t s);
+// ---- stereo visual odometry (ego_kernels.hip) ----
+constexpr int kEgoHypLanes = 64;    // hypotheses (one lane each) of an ego_score workgroup
+constexpr int kEgoTile = 256;       // correspondences of one ego_score workgroup, staged in LDS
+constexpr int kEgoLanes = 256;      // threads of the refinement workgroup = virtual lanes of the S23 sums
+constexpr int kEgoCorrRows = 8;     // SoA rows of the correspondence list: a.xyz, b.xyz, u, v
+struct EgoHyp { double R[9], t[3]; };   // pose of one hypothesis
+struct EgoArgs {
+    cart_ego_camera cam;
+    cart_ego_params p;
+    int cap;                           // max_features
+    // triangulation
+    const cart_keypoint *kpL, *kpR; const int32_t *left_count;
+    const cart_match *stereo; const int32_t *stereo_count;
+    double *landmarks;                 // [cap][4]
+    // estimation
+    const double *cur, *prev; const cart_keypoint *cur_kp;
+    const cart_match *temporal; const int32_t *temporal_count;
+    uint64_t seed, frame;
+    double *corr;                      // [kEgoCorrRows][cap]
+    int32_t *corr_k;                   // [cap] temporal match index of every correspondence
+    int32_t *n;                        // number of correspondences
+    EgoHyp *hyp;                       // [CART_EGO_MAX_HYPOTHESES]
+    cart_ego_hypothesis *table;        // [CART_EGO_MAX_HYPOTHESES]
+    cart_ego_result *result; int32_t *mask;
+};
+void launch_ego_triangulate(const EgoArgs &a, hipStream_t s);
+void launch_ego_estimate(const EgoArgs &a, hipStream_t s);
 void launch_narrow_copy(const void *src, void *dst, size_t bytes, int blocks, hipStream_t s);
 int kernel_count();
 

@@ -18,6 +18,16 @@ static_assert(sizeof(FeatureMatch) == 16, "cart_match layout");
 struct FeatureMatches {
     std::vector<FeatureMatch> stereo;     // query = left, train = right of the frame
     std::vector<FeatureMatch> temporal;   // query = left of the frame, train = left of the previous frame; empty for frame 1
+
+    // What cart_matcher_match wrote, still on the device and owned by the frame (empty when made from host data), for consumers
+    // that stay on the device (modules/egomotion.hpp): list 0 = stereo, 1 = temporal; a list that was not matched has count 0.
+    bool onDevice() const { return !records.empty(); }
+    const int32_t *deviceCount(int list) const { return records.ptr<int32_t>() + list; }
+    const FeatureMatch *deviceMatches(int list) const { return reinterpret_cast<const FeatureMatch *>(records.ptr<uint8_t>() + 16) + (size_t)list * capacity; }
+    int deviceCapacity() const { return capacity; }   // records each list holds
+
+    image_t records;   // one row of bytes: counts [2] int32, 8 B padding, matches [2][capacity]
+    int capacity = 0;
 };
 
 struct FeatureMatcherOptions {

@@ -13,6 +13,7 @@
 #include "cartslam_amd/json.hpp"
 #include "cartslam_amd/modules/depth.hpp"
 #include "cartslam_amd/modules/disparity.hpp"
+#include "cartslam_amd/modules/egomotion.hpp"
 #include "cartslam_amd/modules/features.hpp"
 #include "cartslam_amd/modules/matches.hpp"
 #include "cartslam_amd/modules/planefit.hpp"
@@ -134,6 +135,20 @@ void applyModuleConfig(const Value &modulesConfig, std::shared_ptr<System> syste
             o.maxDy = (float)get(moduleConfig, "max_dy", (double)o.maxDy);
             o.searchRadius = (float)get(moduleConfig, "search_radius", (double)o.searchRadius);
             system->addModule<FeatureMatcherModule>(o);
+        } else if (moduleType == "ego_motion") {  // extension (spec S23): frame-to-frame pose from the orb_matches module's output
+            EgoMotionOptions o;
+            const CameraIntrinsics K = dataSource->getCameraIntrinsics();   // Q as the source builds it: an uncalibrated source has fx = 0
+            o.fx = get(moduleConfig, "fx", (double)K.Q[11]);
+            o.fy = get(moduleConfig, "fy", (double)K.Q[11]);
+            o.cx = get(moduleConfig, "cx", -(double)K.Q[3]);
+            o.cy = get(moduleConfig, "cy", -(double)K.Q[7]);
+            o.baseline = get(moduleConfig, "baseline", K.Q[14] != 0 ? std::fabs(1.0 / (double)K.Q[14]) : 0.0);
+            o.minDisparity = get(moduleConfig, "min_disparity", o.minDisparity);
+            o.inlierThreshold = get(moduleConfig, "inlier_threshold", o.inlierThreshold);
+            o.hypotheses = get(moduleConfig, "hypotheses", o.hypotheses);
+            o.refineIterations = get(moduleConfig, "refine_iterations", o.refineIterations);
+            o.seed = (uint64_t)get(moduleConfig, "seed", 0);
+            system->addModule<EgoMotionModule>(o);
         } else if (endsWith(moduleType, "_visualization")) {
             std::cerr << "[cartconfig] skipping GUI module type " << moduleType << " (out of scope)\n";
         } else {

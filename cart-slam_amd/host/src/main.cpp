@@ -16,6 +16,7 @@
 
 #include "cartslam_amd/cartconfig.hpp"
 #include "cartslam_amd/modules/depth.hpp"
+#include "cartslam_amd/modules/egomotion.hpp"
 #include "cartslam_amd/modules/features.hpp"
 #include "cartslam_amd/modules/matches.hpp"
 #include "cartslam_amd/timing.hpp"
@@ -98,6 +99,12 @@ int main(int argc, char **argv) {
                         std::ofstream o(dump + "/" + std::to_string(id) + "_" + CARTSLAM_KEY_FEATURE_MATCHES + "_" + list.first + ".bin", std::ios::binary);
                         o.write(reinterpret_cast<const char *>(list.second->data()), (std::streamsize)(list.second->size() * sizeof(cart::FeatureMatch)));
                     }
+                }
+                if (run->hasData(CARTSLAM_KEY_EGO_MOTION)) {   // the 120-byte cart_ego_result, then the pose as 12 doubles
+                    auto ego = run->getData<cart::EgoMotion>(CARTSLAM_KEY_EGO_MOTION);
+                    std::ofstream o(dump + "/" + std::to_string(id) + "_" + CARTSLAM_KEY_EGO_MOTION + ".bin", std::ios::binary);
+                    o.write(reinterpret_cast<const char *>(&ego->result), sizeof(ego->result));
+                    o.write(reinterpret_cast<const char *>(ego->pose), sizeof(ego->pose));
                 }
                 if (run->hasData(CARTSLAM_KEY_PLANES_EQ_LABEL_PLANES)) {   // f64 [max_label + 1][4]
                     auto lp = run->getData<std::vector<cart::Vec4d>>(CARTSLAM_KEY_PLANES_EQ_LABEL_PLANES);

@@ -486,6 +486,62 @@ int cart_matcher_match(cart_matcher *matcher, const cart_match_params *params, c
                        const cart_keypoint *t_kp, const int32_t *t_count, cart_match *matches, int32_t *match_count,
                        int32_t *forward, void *stream);
 
+/* ---- Stereo visual odometry: frame-to-frame ego-motion from the ORB matches (spec S23) ------------------------
+ * An extension: the reference estimates no pose.  The stereo matches of a frame are triangulated into landmarks, the temporal
+ * matches whose two ends have landmarks become 3-D / 3-D correspondences, seeded three-point (triad) hypotheses are scored by
+ * their left-image reprojection inliers, and the best is refined by Gauss-Newton.  fp64 with + - * / sqrt only, integer scores,
+ * every sum in a fixed order: deterministic, restated in tests/np_ego.py.  Pose convention: p_cur = R p_prev + t. */
+typedef struct cart_ego_camera {
+    double fx, fy, cx, cy, baseline;          /* fx, fy, baseline > 0 */
+} cart_ego_camera;
+typedef struct cart_ego_params {
+    double min_disparity;                     /* a landmark needs left.x - right.x >= this (> 0) */
+    double inlier_threshold;                  /* pixels (> 0) */
+    int32_t hypotheses;                       /* 1..1024 */
+    int32_t refine_iterations;                /* 0..16 */
+} cart_ego_params;
+void cart_ego_default_params(cart_ego_params *p); /* extension: 1.0, 2.0, 256, 4 */
+#define CART_EGO_MAX_HYPOTHESES 1024
+#define CART_EGO_MAX_REFINE 16
+typedef struct cart_ego_result {
+    double R[9], t[3];                        /* row-major rotation and translation; the identity when status is 0 */
+    double rms;                               /* sqrt(mean squared reprojection error) of the final inliers, pixels */
+    int32_t status;                           /* 1 = a pose was found */
+    int32_t n_correspondences, n_inliers;
+    int32_t best_hypothesis;                  /* -1 when status is 0 */
+} cart_ego_result;
+typedef struct cart_ego_hypothesis {
+    uint64_t qerr;                            /* sum over the inliers of floor(e2 / thr^2 * 2^24) */
+    int32_t count, skipped;                   /* inliers; 1 = degenerate sample, not scored */
+} cart_ego_hypothesis;
+
+typedef struct cart_ego cart_ego;
+/* Extension.  Workspaces for lists of up to max_features (1..65536) keypoints / matches; nothing is allocated per call. */
+int cart_ego_create(cart_engine *engine, int max_features, cart_ego **out);
+/* Extension.  Keeps the device it was created on, so it may be destroyed after its engine. */
+void cart_ego_destroy(cart_ego *ego);
+/* Extension.  Landmarks of one frame: kpL / kpR = the cart_keypoint records of the left and right image, left_count = the number of
+ * left keypoints, stereo_matches / stereo_count = a match list with query = left, train = right and distinct queries (what
+ * cart_matcher_match writes); all device memory, the counts DEVICE int32 clamped to [0, max_features].  landmarks = device double
+ * [max_features][4] (8-byte aligned): (X, Y, Z, 1.0) for a left index with an accepted match, four zeros for every other
+ * index below left_count; rows from left_count on are not written.  A match with an index outside [0, left_count) x
+ * [0, max_features) is ignored.  No host synchronisation. */
+int cart_ego_triangulate(cart_ego *ego, const cart_ego_camera *camera, const cart_ego_params *params, const cart_keypoint *kpL,
+                         const cart_keypoint *kpR, const int32_t *left_count, const cart_match *stereo_matches,
+                         const int32_t *stereo_count, double *landmarks, void *stream);
+/* Extension.  Relative pose between two frames: cur_landmarks / cur_kpL of the current frame, prev_landmarks of the previous one
+ * (each what cart_ego_triangulate wrote), temporal_matches / temporal_count = matches with query = current left, train =
+ * previous left (device; the count a DEVICE int32, clamped to [0, max_features]).  Device outputs: result (8-byte aligned) and
+ * inlier_mask (may be NULL) = int32 [max_features], entry k = 1 iff temporal match k is a final inlier (all max_features entries
+ * are written).  The draws of hypothesis h come from the S17 stream (seed, 3, frame_id, h, 0).  No host synchronisation. */
+int cart_ego_estimate(cart_ego *ego, const cart_ego_camera *camera, const cart_ego_params *params, const double *cur_landmarks,
+                      const cart_keypoint *cur_kpL, const double *prev_landmarks, const cart_match *temporal_matches,
+                      const int32_t *temporal_count, uint64_t seed, uint64_t frame_id, cart_ego_result *result,
+                      int32_t *inlier_mask, void *stream);
+/* Extension.  Test / diagnostic access to the last cart_ego_estimate call: the per-hypothesis table into host_dst (HOST, `capacity`
+ * records; the first *n_hypotheses = that call's params.hypotheses are written).  Synchronises `stream`. */
+int cart_ego_debug_hypotheses(cart_ego *ego, cart_ego_hypothesis *host_dst, int capacity, int *n_hypotheses, void *stream);
+
 /* Stand-in for ImageOpticalFlowModule's device work (src/modules/optflow.cpp:96-140: cvtColor x2 +
  * cv::cuda::NvidiaOpticalFlow_2_0::calc(current, previous), NVIDIA fixed-function hardware): dense census block
  * matching (oracle S15).  cur / prev = the reference images of frame id and id-1 (1-channel gray or 3-channel BGR),
