@@ -101,6 +101,16 @@ class EgoHypothesis(C.Structure):
 EGO_MAX_HYPOTHESES, EGO_MAX_REFINE = 1024, 16   # CART_EGO_MAX_*
 
 
+class PlaneMapParams(C.Structure):
+    # mirrors cart_plane_map_params (include/cart_engine.h, spec S24); the defaults are cart_plane_map_default_params'
+    _fields_ = [(n, C.c_double) for n in ("cell_size", "min_disparity", "max_depth", "max_lateral", "height_quantum")]
+
+
+class PlaneMapCell(C.Structure):
+    # mirrors cart_plane_map_cell (include/cart_engine.h, spec S24)
+    _fields_ = [("horizontal", C.c_uint32), ("vertical", C.c_uint32), ("y_min", C.c_int32), ("y_max", C.c_int32)]
+
+
 PLACE_MODES = {0: "unknown", 1: "fast", 2: "mixed", 3: "uniform"}                                       # CART_PLACE_MODE_*
 PLACE_STOPS = {0: "nothing to do", 1: "fast set found", 2: "uniform", 3: "tries", 4: "time", 5: "memory"}   # CART_PLACE_STOP_*
 
@@ -174,6 +184,14 @@ PROTOTYPES = {
     "cart_ego_triangulate": (_i, [_vp, C.POINTER(EgoCamera), C.POINTER(EgoParams), _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "cart_ego_estimate": (_i, [_vp, C.POINTER(EgoCamera), C.POINTER(EgoParams), _vp, _vp, _vp, _vp, _vp, C.c_uint64, C.c_uint64, _vp, _vp, _vp]),
     "cart_ego_debug_hypotheses": (_i, [_vp, C.POINTER(EgoHypothesis), _i, C.POINTER(_i), _vp]),
+    "cart_plane_map_default_params": (None, [C.POINTER(PlaneMapParams)]),
+    "cart_plane_map_create": (_i, [_vp, _i, _i, C.POINTER(PlaneMapParams), C.POINTER(_vp)]),
+    "cart_plane_map_destroy": (None, [_vp]),
+    "cart_plane_map_clear": (_i, [_vp]),
+    "cart_plane_map_update": (_i, [_vp, C.POINTER(EgoCamera), C.POINTER(C.c_double), _vp, _sz, _vp, _sz, _i, _i, _vp]),
+    "cart_plane_map_window": (_i, [_vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(_i)]),
+    "cart_plane_map_read": (_i, [_vp, _vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _vp]),
+    "cart_plane_map_classify": (_i, [_vp, _i, _i, _vp, _sz, _vp]),
     "cart_optical_flow": (_i, [_vp, _vp, _sz, _vp, _sz, _i, _i, _i, _vp, _sz, _vp]),
     "cart_flow_default_params": (None, [C.POINTER(FlowParams)]),
     "cart_flow_pyramid_levels": (_i, [_i, _i, _i, C.POINTER(_i), C.POINTER(_i)]),

@@ -9,7 +9,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import EgoCamera, EgoParams, EngineParams, MatchParams, PlaneParams, SuperpixelParams
+from ._lib import EgoCamera, EgoParams, EngineParams, MatchParams, PlaneMapParams, PlaneParams, SuperpixelParams
 
 INVALID = -32768  # CARTSLAM_DISPARITY_INVALID, reference include/modules/disparity.hpp:17
 
@@ -882,6 +882,76 @@ class EgoMotion(_DeviceObject):
         n = C.c_int(0)
         self._check(self._lib.cart_ego_debug_hypotheses(self._h, buf, _lib.EGO_MAX_HYPOTHESES, C.byref(n), _stream_ptr()), "cart_ego_debug_hypotheses")
         return np.frombuffer(buf, EGO_HYPOTHESIS_DTYPE, n.value).copy()
+
+
+PLANE_MAP_CELL_DTYPE = np.dtype([("horizontal", "<u4"), ("vertical", "<u4"), ("y_min", "<i4"), ("y_max", "<i4")])   # cart_plane_map_cell
+
+
+def plane_map_params(**fields):
+    """cart_plane_map_default_params (spec S24) with the given fields replaced."""
+    p = PlaneMapParams()
+    _lib.load().cart_plane_map_default_params(C.byref(p))
+    for k, v in fields.items():
+        if k not in dict(PlaneMapParams._fields_):
+            raise ValueError(f"cart_plane_map_params has no field {k}")
+        setattr(p, k, v)
+    return p
+
+
+class PlaneMap(_DeviceObject):
+    """World-frame bird's-eye plane map (cart_plane_map_* in the C ABI, spec S24 in DESIGN.md 7.6): a rolling grid of cells_x x
+    cells_z cells that every frame's disparity + plane labels vote into through the frame's camera-to-world pose.  Stateful:
+    updates must come in frame order."""
+    _name = "plane_map"
+
+    def __init__(self, engine, camera, cells_x, cells_z, params=None):
+        """camera = EgoCamera or (fx, fy, cx, cy, baseline); params = PlaneMapParams (default: plane_map_params())."""
+        self.camera = camera if isinstance(camera, EgoCamera) else EgoCamera(*[float(v) for v in camera])
+        self.cells_x, self.cells_z = int(cells_x), int(cells_z)
+        self.params = params if params is not None else plane_map_params()
+        super().__init__(engine, self.cells_x, self.cells_z, C.byref(self.params))
+
+    def update(self, disp, planes, pose, raw=False):
+        """One frame: disp int16 [h, w] (x16), planes uint8 [h, w], pose = 12 numbers (3 x 4 camera-to-world, KITTI row order, host).
+        raw=True takes the two device tensors as they are (rows may be pitched) with no conversion or upload.  -> (ox, oz)."""
+        import torch
+        if not raw:
+            disp = torch.as_tensor(np.ascontiguousarray(disp.cpu() if isinstance(disp, torch.Tensor) else disp), dtype=torch.int16).cuda()
+            planes = torch.as_tensor(np.ascontiguousarray(planes.cpu() if isinstance(planes, torch.Tensor) else planes), dtype=torch.uint8).cuda()
+        if not isinstance(disp, torch.Tensor) or not isinstance(planes, torch.Tensor) or disp.dtype != torch.int16 or planes.dtype != torch.uint8:
+            raise EngineError("disp must be an int16 and planes a uint8 device tensor")
+        if disp.dim() != 2 or planes.shape != disp.shape:
+            raise EngineError("disp and planes must be [h, w] images of one size")
+        _, dp, ds, _ = _geom(disp, 1)
+        _, pp, ps, _ = _geom(planes, 1)
+        host_pose = (C.c_double * 12)(*[float(v) for v in np.asarray(pose, np.float64).reshape(-1)])
+        self._check(self._lib.cart_plane_map_update(self._h, C.byref(self.camera), host_pose, dp, ds, pp, ps, int(disp.shape[1]), int(disp.shape[0]),
+                                                    _stream_ptr()), "cart_plane_map_update")
+        return self.window()[:2]
+
+    def window(self):
+        """-> (ox, oz, valid): the window origin in absolute cells; valid is False after create / clear (host getter)."""
+        ox, oz, valid = C.c_int64(0), C.c_int64(0), C.c_int(0)
+        self._check(self._lib.cart_plane_map_window(self._h, C.byref(ox), C.byref(oz), C.byref(valid)), "cart_plane_map_window")
+        return ox.value, oz.value, bool(valid.value)
+
+    def read(self):
+        """-> (cells PLANE_MAP_CELL_DTYPE [cells_z, cells_x] in window order, (ox, oz)); synchronises."""
+        cells = np.empty((self.cells_z, self.cells_x), PLANE_MAP_CELL_DTYPE)
+        ox, oz = C.c_int64(0), C.c_int64(0)
+        self._check(self._lib.cart_plane_map_read(self._h, C.c_void_p(cells.ctypes.data), C.byref(ox), C.byref(oz), _stream_ptr()), "cart_plane_map_read")
+        return cells, (ox.value, oz.value)
+
+    def classify(self, min_votes=3, obstacle_percent=50, raw=False):
+        """-> uint8 [cells_z, cells_x] in window order: 0 free, 1 obstacle, 2 unknown (host array; raw=True: the device tensor)."""
+        import torch
+        out = torch.empty((self.cells_z, self.cells_x), dtype=torch.uint8, device="cuda")
+        self._check(self._lib.cart_plane_map_classify(self._h, int(min_votes), int(obstacle_percent), C.c_void_p(out.data_ptr()), self.cells_x,
+                                                      _stream_ptr()), "cart_plane_map_classify")
+        return out if raw else out.cpu().numpy()
+
+    def clear(self):
+        self._check(self._lib.cart_plane_map_clear(self._h), "cart_plane_map_clear")
 
 
 def plane_cluster(planes, offsets, neighbours):

@@ -168,3 +168,19 @@ def make_batch(n, w, h, D, min_disp=4, seed=DEFAULT_SEED, channels=1, first_fram
         l, r, _ = make_pair(w, h, D, min_disp, seed, first_frame + f, channels, scene)
         ls.append(l); rs.append(r)
     return np.stack(ls), np.stack(rs)
+
+
+def road_corridor(w, h, fx, fy, cx, cy, baseline, camera_height=1.65, half_width=4.0):
+    """Labelled disparity of a street corridor (the input of the plane map, spec S24): a ground plane camera_height under the
+    camera (label 0), a wall on each side at X = -half_width and +half_width (label 1; the nearer surface wins) and sky above the
+    horizon (invalid disparity, label 2).  -> (disparity int16 x16 [h, w], labels uint8 [h, w])."""
+    y, x = np.mgrid[0:h, 0:w].astype(np.float64)
+    with np.errstate(divide="ignore"):
+        d_ground = np.where(y > cy, baseline * fy * (y - cy) / (fy * camera_height), 0.0) * fx / fy
+        d_wall = baseline * fx * np.abs(x - cx) / (fx * half_width)
+    d = np.maximum(d_ground, d_wall)
+    labels = np.where(d_wall >= d_ground, 1, 0).astype(np.uint8)
+    disp = np.clip(np.round(d * 16.0), 0, 32767).astype(np.int16)
+    sky = (y <= cy) & (d < 3.0)          # the walls end 1/3 of the way to the horizon's vanishing point
+    disp[sky], labels[sky] = -32768, 2
+    return disp, labels

@@ -305,6 +305,29 @@ struct EgoArgs {
 };
 void launch_ego_triangulate(const EgoArgs &a, hipStream_t s);
 void launch_ego_estimate(const EgoArgs &a, hipStream_t s);
+// ---- world-frame plane map (planemap_kernels.hip) ----
+// The grid is stored toroidally: window cell (rx, rz) = absolute cell (ox + rx, oz + rz) lives at column (rx + mx) mod nx, row
+// (rz + mz) mod nz with mx = ox mod nx, mz = oz mod nz, so a window move copies nothing.
+constexpr int kMapStrip = 8;        // image rows one lane of the vote kernel walks
+struct PlaneMapGrid {
+    cart_plane_map_cell *cells;        // [nz][nx], toroidal
+    int nx, nz, mx, mz;
+};
+struct PlaneMapVoteArgs {
+    PlaneMapGrid grid;
+    cart_ego_camera cam;
+    cart_plane_map_params p;
+    double pose[12];
+    double ox, oz;                     // window origin in absolute cells (integers, exact in a double)
+    const int16_t *disp; size_t disp_step;
+    const uint8_t *planes; size_t planes_step;
+    int w, h;
+};
+// empties the window rectangle [rx0, rx0 + rw) x [rz0, rz0 + rh)
+void launch_plane_map_clear(const PlaneMapGrid &grid, int rx0, int rw, int rz0, int rh, hipStream_t s);
+void launch_plane_map_vote(const PlaneMapVoteArgs &a, hipStream_t s);
+// empty != 0: the map has no window, every class is UNKNOWN
+void launch_plane_map_classify(const PlaneMapGrid &grid, int empty, unsigned min_votes, unsigned percent, uint8_t *out, size_t out_step, hipStream_t s);
 void launch_narrow_copy(const void *src, void *dst, size_t bytes, int blocks, hipStream_t s);
 int kernel_count();
 

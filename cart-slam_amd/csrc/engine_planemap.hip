@@ -1,0 +1,164 @@
+// engine_planemap.hip -- C ABI of the world-frame bird's-eye plane map (include/cart_engine.h): argument checks, the
+// window arithmetic (host, int64) and the cart_plane_map device object.
+
+#include "engine_host.h"
+
+using namespace cart_amd;
+
+extern "C" {
+
+struct cart_plane_map : DeviceObject {
+    using DeviceObject::DeviceObject;
+    int nx = 0, nz = 0;
+    cart_plane_map_params p{};
+    cart_plane_map_cell *cells = nullptr;   // [nz][nx], toroidal (engine_internal.h, PlaneMapGrid)
+    bool valid = false;                     // a window exists (guarded by mu)
+    int64_t ox = 0, oz = 0;                 // its origin in absolute cells
+};
+
+void cart_plane_map_default_params(cart_plane_map_params *p) {
+    if (!p) return;
+    *p = cart_plane_map_params{0.25, 1.0, 20.0, 10.0, 0.05};
+}
+
+static int64_t floor_div(int64_t a, int64_t b) { return a / b - ((a % b != 0) && ((a < 0) != (b < 0))); }
+static int floor_mod(int64_t a, int n) { return (int)(((a % n) + n) % n); }
+
+static PlaneMapGrid grid_of(const cart_plane_map *m) { return PlaneMapGrid{m->cells, m->nx, m->nz, floor_mod(m->ox, m->nx), floor_mod(m->oz, m->nz)}; }
+
+int cart_plane_map_create(cart_engine *e, int cells_x, int cells_z, const cart_plane_map_params *p, cart_plane_map **out) {
+    if (cells_x < 32 || cells_x > 4096 || cells_x % 16) return fail("cells_x must be a multiple of 16 in [32, 4096]");
+    if (cells_z < 32 || cells_z > 4096 || cells_z % 16) return fail("cells_z must be a multiple of 16 in [32, 4096]");
+    if (!p) return fail("params is NULL");
+    if (!(p->cell_size >= 0.01) || !std::isfinite(p->cell_size)) return fail("cell_size must be a number >= 0.01");
+    if (!(p->min_disparity > 0) || !std::isfinite(p->min_disparity)) return fail("min_disparity must be a positive number");
+    if (!(p->max_depth > 0) || !std::isfinite(p->max_depth)) return fail("max_depth must be a positive number");
+    if (!(p->max_lateral > 0) || !std::isfinite(p->max_lateral)) return fail("max_lateral must be a positive number");
+    if (!(p->height_quantum >= 0.001) || !std::isfinite(p->height_quantum)) return fail("height_quantum must be a number >= 0.001");
+    if (!e || !out) return fail("bad arguments");
+    HIP_TRY(hipSetDevice(e->params.device_id));
+    cart_plane_map *m = new (std::nothrow) cart_plane_map(e);
+    if (!m) return fail("out of host memory");
+    m->nx = cells_x; m->nz = cells_z; m->p = *p;
+    if (m->alloc(&m->cells, (size_t)cells_x * cells_z * sizeof(cart_plane_map_cell)) || m->create_event()) {
+        destroy_object(m);
+        return fail("allocating the plane map failed");
+    }
+    *out = m;
+    return 0;
+}
+
+void cart_plane_map_destroy(cart_plane_map *m) { destroy_object(m); }
+
+int cart_plane_map_clear(cart_plane_map *m) {
+    if (!m) return fail("map is NULL");
+    std::lock_guard<std::mutex> lk(m->mu);
+    m->valid = false;   // the next update empties the grid on its stream
+    return 0;
+}
+
+static int check_camera(const cart_ego_camera *cam) {   // as cart_ego_*'s
+    if (!cam) return fail("camera is NULL");
+    if (!(cam->fx > 0) || !std::isfinite(cam->fx)) return fail("fx must be a positive number");
+    if (!(cam->fy > 0) || !std::isfinite(cam->fy)) return fail("fy must be a positive number");
+    if (!std::isfinite(cam->cx)) return fail("cx must be finite");
+    if (!std::isfinite(cam->cy)) return fail("cy must be finite");
+    if (!(cam->baseline > 0) || !std::isfinite(cam->baseline)) return fail("baseline must be a positive number");
+    return 0;
+}
+
+int cart_plane_map_update(cart_plane_map *m, const cart_ego_camera *cam, const double *pose, const int16_t *disp, size_t disp_step, const uint8_t *planes,
+                          size_t planes_step, int w, int h, void *stream_) {
+    if (check_camera(cam)) return -1;
+    if (!pose) return fail("pose is NULL");
+    for (int k = 0; k < 12; ++k) {
+        const double bound = k % 4 == 3 ? 1e6 : 2.0;
+        if (!std::isfinite(pose[k]) || std::fabs(pose[k]) > bound)
+            return fail("pose[" + std::to_string(k) + "] must be finite and within " + (k % 4 == 3 ? "1e6 (translation)" : "2 (rotation)"));
+    }
+    if (w < 1 || w > 16384) return fail("width must be in [1, 16384]");
+    if (h < 1 || h > 16384) return fail("height must be in [1, 16384]");
+    if (!m) return fail("map is NULL");
+    if (!disp || !planes) return fail("NULL pointer");
+    if ((reinterpret_cast<uintptr_t>(disp) & 1) || (disp_step & 1)) return fail("disparity and its step must be 2-byte aligned");
+    if (disp_step < (size_t)w * sizeof(int16_t)) return fail("disparity_step is below the row size");
+    if (planes_step < (size_t)w) return fail("planes_step is below the row size");
+
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    ObjectCall call(*m, stream);
+    if (call.begin()) return -1;
+    // the window (S24): |t| <= 1e6 and cell_size >= 0.01 keep every value below 2^27
+    const int64_t cx = (int64_t)std::floor(pose[3] / m->p.cell_size), cz = (int64_t)std::floor(pose[11] / m->p.cell_size);
+    const int64_t ox = 16 * floor_div(cx - m->nx / 2, 16), oz = 16 * floor_div(cz - m->nz / 2, 16);
+    const int64_t dx = ox - m->ox, dz = oz - m->oz;
+    const bool all = !m->valid || std::llabs(dx) >= m->nx || std::llabs(dz) >= m->nz;
+    m->ox = ox; m->oz = oz; m->valid = true;
+    const PlaneMapGrid grid = grid_of(m);
+    if (all) {
+        launch_plane_map_clear(grid, 0, m->nx, 0, m->nz, stream);
+    } else {   // the strips that entered: |dx| columns on the side the window moved to, |dz| rows likewise
+        if (dx) launch_plane_map_clear(grid, dx > 0 ? m->nx - (int)dx : 0, (int)std::llabs(dx), 0, m->nz, stream);
+        if (dz) launch_plane_map_clear(grid, 0, m->nx, dz > 0 ? m->nz - (int)dz : 0, (int)std::llabs(dz), stream);
+    }
+    PlaneMapVoteArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.grid = grid; a.cam = *cam; a.p = m->p;
+    std::memcpy(a.pose, pose, sizeof(a.pose));
+    a.ox = (double)ox; a.oz = (double)oz;
+    a.disp = disp; a.disp_step = disp_step; a.planes = planes; a.planes_step = planes_step; a.w = w; a.h = h;
+    launch_plane_map_vote(a, stream);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int cart_plane_map_window(cart_plane_map *m, int64_t *origin_x, int64_t *origin_z, int *valid) {
+    if (!m) return fail("map is NULL");
+    if (!origin_x || !origin_z || !valid) return fail("NULL pointer");
+    std::lock_guard<std::mutex> lk(m->mu);
+    *origin_x = m->valid ? m->ox : 0;
+    *origin_z = m->valid ? m->oz : 0;
+    *valid = m->valid ? 1 : 0;
+    return 0;
+}
+
+int cart_plane_map_read(cart_plane_map *m, cart_plane_map_cell *host_cells, int64_t *origin_x, int64_t *origin_z, void *stream_) {
+    if (!m) return fail("map is NULL");
+    if (!host_cells || !origin_x || !origin_z) return fail("NULL pointer");
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    ObjectCall call(*m, stream);
+    if (call.begin()) return -1;
+    const size_t n = (size_t)m->nx * m->nz;
+    if (!m->valid) {
+        std::fill(host_cells, host_cells + n, cart_plane_map_cell{0, 0, INT32_MAX, INT32_MIN});
+        *origin_x = *origin_z = 0;
+        return 0;
+    }
+    std::vector<cart_plane_map_cell> stored(n);
+    HIP_TRY(hipMemcpyAsync(stored.data(), m->cells, n * sizeof(cart_plane_map_cell), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    const PlaneMapGrid g = grid_of(m);   // toroidal storage -> window order: two pieces per row
+    for (int rz = 0; rz < g.nz; ++rz) {
+        const cart_plane_map_cell *row = stored.data() + (size_t)((rz + g.mz) % g.nz) * g.nx;
+        cart_plane_map_cell *dst = host_cells + (size_t)rz * g.nx;
+        std::copy(row + g.mx, row + g.nx, dst);
+        std::copy(row, row + g.mx, dst + (g.nx - g.mx));
+    }
+    *origin_x = m->ox; *origin_z = m->oz;
+    return 0;
+}
+
+int cart_plane_map_classify(cart_plane_map *m, int min_votes, int obstacle_percent, uint8_t *classes, size_t classes_step, void *stream_) {
+    if (!m) return fail("map is NULL");
+    if (min_votes < 1) return fail("min_votes must be at least 1");
+    if (obstacle_percent < 1 || obstacle_percent > 100) return fail("obstacle_percent must be in [1, 100]");
+    if (!classes) return fail("classes is NULL");
+    if (classes_step < (size_t)m->nx) return fail("classes_step is below the row size");
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    ObjectCall call(*m, stream);
+    if (call.begin()) return -1;
+    launch_plane_map_classify(grid_of(m), m->valid ? 0 : 1, (unsigned)min_votes, (unsigned)obstacle_percent, classes, classes_step, stream);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+}  // extern "C"

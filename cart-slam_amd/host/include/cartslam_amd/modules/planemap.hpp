@@ -1,0 +1,49 @@
+// modules/planemap.hpp -- an extension module (the reference only paints one frame's vertical pixels into a picture,
+// planeseg_vis.cu:58-107): the world-frame bird's-eye plane map through cart_plane_map_* (include/cart_engine.h), spec DESIGN.md S24.
+// Every frame's "disparity" + "planes" vote into one rolling grid through the frame's camera-to-world pose, which comes from the
+// "ego_motion" module or from a KITTI pose file.  Factory type "plane_map".
+#pragma once
+#include <array>
+#include <mutex>
+#include <string>
+#include <vector>
+
+#include "../cartslam.hpp"
+#include "cart_engine.h"
+
+#define CARTSLAM_KEY_PLANE_MAP "plane_map"
+
+namespace cart {
+struct PlaneMap {
+    int64_t originX = 0, originZ = 0;   // the window's first cell in absolute cells
+    int cellsX = 0, cellsZ = 0;
+    double cellSize = 0;
+    image_t classes;                    // device u8 [cellsZ][cellsX] in window order: 0 free, 1 obstacle, 2 unknown
+    std::vector<cart_plane_map_cell> cells;   // the cells in window order; filled only when CARTSLAM_PLANE_MAP_SNAPSHOT is set (--dump)
+};
+
+// The grid and vote defaults are build-owned choices that no data set has tuned; 20 and 10 are the reference's gates.
+struct PlaneMapOptions {
+    double fx = 0, fy = 0, cx = 0, cy = 0, baseline = 0;   // the factory fills them from the data source's Q
+    int cellsX = 512, cellsZ = 512;
+    double cellSize = 0.25, minDisparity = 1.0, maxDepth = 20.0, maxLateral = 10.0, heightQuantum = 0.05;   // cart_plane_map_default_params
+    int minVotes = 3, obstaclePercent = 50;
+    std::string poseFile;   // KITTI poses/NN.txt: 12 numbers per line, line id - 1 belongs to frame id; empty = the "ego_motion" module's pose
+};
+
+class PlaneMapModule : public SyncWrapperSystemModule {
+   public:
+    explicit PlaneMapModule(const PlaneMapOptions &options);   // throws std::invalid_argument naming the key that is out of range
+    ~PlaneMapModule();
+    system_data_t runInternal(System &system, SystemRunData &data) override;
+
+   private:
+    const PlaneMapOptions options;
+    const bool snapshot;
+    std::vector<std::array<double, 12>> poses;   // of the pose file
+    std::vector<bool> poseGiven;
+    std::mutex mutex;                            // the frames arrive one at a time (the -1 dependency); this guards the lazy creation
+    cart_plane_map *map = nullptr;
+    void *stream = nullptr;                      // hipStream_t
+};
+}  // namespace cart

@@ -21,6 +21,7 @@
 #include "cartslam_amd/modules/matches.hpp"
 #include "cartslam_amd/timing.hpp"
 #include "cartslam_amd/modules/planefit.hpp"
+#include "cartslam_amd/modules/planemap.hpp"
 #include "cartslam_amd/modules/planeseg.hpp"
 
 int main(int argc, char **argv) {
@@ -33,7 +34,7 @@ int main(int argc, char **argv) {
     bool sequential = false;
     for (int i = 3; i + 1 < argc; i += 2) {
         if (!std::strcmp(argv[i], "--frames")) maxFrames = std::atoi(argv[i + 1]);
-        else if (!std::strcmp(argv[i], "--dump")) dump = argv[i + 1];
+        else if (!std::strcmp(argv[i], "--dump")) { dump = argv[i + 1]; setenv("CARTSLAM_PLANE_MAP_SNAPSHOT", "1", 1); }  // plane_map keeps every frame's cells
         else if (!std::strcmp(argv[i], "--sequential")) sequential = std::atoi(argv[i + 1]) != 0;
         else if (!std::strcmp(argv[i], "--inflight")) setenv("CARTSLAM_CONCURRENT_RUN_LIMIT", argv[i + 1], 1);  // frames in flight (reference: 12)
         else if (!std::strcmp(argv[i], "--timing")) cart::timing::Sink::instance().open(argv[i + 1]);
@@ -105,6 +106,18 @@ int main(int argc, char **argv) {
                     std::ofstream o(dump + "/" + std::to_string(id) + "_" + CARTSLAM_KEY_EGO_MOTION + ".bin", std::ios::binary);
                     o.write(reinterpret_cast<const char *>(&ego->result), sizeof(ego->result));
                     o.write(reinterpret_cast<const char *>(ego->pose), sizeof(ego->pose));
+                }
+                if (run->hasData(CARTSLAM_KEY_PLANE_MAP)) {   // int64 ox, oz; int32 Nx, Nz; double cell_size; the 16-byte cells; the u8 classes
+                    auto pm = run->getData<cart::PlaneMap>(CARTSLAM_KEY_PLANE_MAP);
+                    std::ofstream o(dump + "/" + std::to_string(id) + "_" + CARTSLAM_KEY_PLANE_MAP + ".bin", std::ios::binary);
+                    const int64_t origin[2] = {pm->originX, pm->originZ};
+                    const int32_t shape[2] = {pm->cellsX, pm->cellsZ};
+                    o.write(reinterpret_cast<const char *>(origin), sizeof(origin));
+                    o.write(reinterpret_cast<const char *>(shape), sizeof(shape));
+                    o.write(reinterpret_cast<const char *>(&pm->cellSize), sizeof(pm->cellSize));
+                    o.write(reinterpret_cast<const char *>(pm->cells.data()), (std::streamsize)(pm->cells.size() * sizeof(cart_plane_map_cell)));
+                    const auto classes = pm->classes.downloadTight();
+                    o.write(reinterpret_cast<const char *>(classes.data()), (std::streamsize)classes.size());
                 }
                 if (run->hasData(CARTSLAM_KEY_PLANES_EQ_LABEL_PLANES)) {   // f64 [max_label + 1][4]
                     auto lp = run->getData<std::vector<cart::Vec4d>>(CARTSLAM_KEY_PLANES_EQ_LABEL_PLANES);

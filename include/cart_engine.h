@@ -542,6 +542,60 @@ int cart_ego_estimate(cart_ego *ego, const cart_ego_camera *camera, const cart_e
  * records; the first *n_hypotheses = that call's params.hypotheses are written).  Synchronises `stream`. */
 int cart_ego_debug_hypotheses(cart_ego *ego, cart_ego_hypothesis *host_dst, int capacity, int *n_hypotheses, void *stream);
 
+/* ---- World-frame bird's-eye plane map (spec S24) -----------------------------------------------------------------
+ * An extension: the headless, race-free, accumulated form of the reference's paintBEVPlanes (planeseg_vis.cu:58-107).  A rolling
+ * grid of cells_x x cells_z cells in the world's X-Z plane; every frame's disparity + plane labels vote into it through the frame's
+ * camera-to-world pose.  fp64 with + - * / floor only and integer atomics: independent of execution order, restated in
+ * tests/np_planemap.py.
+ *   Window: c = floor(t / cell_size) per axis (t_x = pose[3], t_z = pose[11]), origin o = 16 floor_div(c - N / 2, 16) in absolute
+ *   cells.  The first update after create / clear starts an empty window; afterwards the cells of the new window that the old one
+ *   did not hold are empty before the frame's votes, and cells that leave are forgotten.
+ *   Vote of pixel (x, y), disparity s, label l, in this order: l in {0, 1}; s != -32768; d = s / 16.0 >= min_disparity;
+ *   Z = (fx baseline) / d <= max_depth; X = ((x - cx) Z) / fx in [-max_lateral, max_lateral]; Y = ((y - cy) Z) / fy;
+ *   p_w[r] = ((P[4r] X + P[4r+1] Y) + P[4r+2] Z) + P[4r+3]; gx = floor(Xw / cell_size), gz = floor(Zw / cell_size); inside the
+ *   window (compared as doubles) the cell's `horizontal` (l = 0) or `vertical` (l = 1) count grows by one, and for l = 1
+ *   y_min / y_max take q = (int32) clamp(floor(Yw / height_quantum), -2^30, 2^30).  Votes outside the window are dropped.
+ *   At the defaults the depth gate also removes the invalid marker of a range-fixed disparity, (min_disp - 1) * 16: with
+ *   min_disp = 4 that is d = 3, Z = fx baseline / 3 > 20 m for any fx baseline > 60 (KITTI: 386).  When max_depth is raised,
+ *   set min_disparity to the disparity module's own minimum. */
+typedef struct cart_plane_map_cell {
+    uint32_t horizontal, vertical;            /* votes */
+    int32_t y_min, y_max;                     /* quantised world Y extent of the vertical votes */
+} cart_plane_map_cell;                        /* the empty cell is (0, 0, INT32_MAX, INT32_MIN) */
+typedef struct cart_plane_map_params {
+    double cell_size;                         /* metres, >= 0.01 */
+    double min_disparity;                     /* pixels, > 0 */
+    double max_depth;                         /* metres, > 0; the reference's 20 */
+    double max_lateral;                       /* metres, > 0; the reference's 10 */
+    double height_quantum;                    /* metres, >= 0.001 */
+} cart_plane_map_params;
+void cart_plane_map_default_params(cart_plane_map_params *p); /* extension: 0.25, 1.0, 20.0, 10.0, 0.05 */
+
+typedef struct cart_plane_map cart_plane_map;
+/* Extension.  cells_x, cells_z: multiples of 16 in 32..4096.  The parameters are fixed for the object's life.  Stateful like
+ * cart_superpixels: calls on one object must be issued in frame order.  cells_x, cells_z and params are checked before the engine,
+ * so a configuration can be validated without a device. */
+int cart_plane_map_create(cart_engine *engine, int cells_x, int cells_z, const cart_plane_map_params *params, cart_plane_map **out);
+/* Extension.  Keeps the device it was created on, so it may be destroyed after its engine. */
+void cart_plane_map_destroy(cart_plane_map *map);
+/* Extension.  Empties the grid: the next update starts a new window.  No device work. */
+int cart_plane_map_clear(cart_plane_map *map);
+/* Extension.  One frame: pose = HOST double [12], the 3 x 4 camera-to-world matrix in KITTI row order (all finite, |R entries| <= 2,
+ * |t entries| <= 1e6); disparity = device int16 x16 (2-byte aligned, step a multiple of 2), planes = device u8 labels, both
+ * width x height (1..16384 each), steps in bytes.  Moves the window, clears what entered it, votes.  The camera, the pose and the
+ * sizes are checked before the map and the images.  No host synchronisation. */
+int cart_plane_map_update(cart_plane_map *map, const cart_ego_camera *camera, const double *pose, const int16_t *disparity,
+                          size_t disparity_step, const uint8_t *planes, size_t planes_step, int width, int height, void *stream);
+/* Extension.  HOST getter: the window origin in absolute cells and whether a window exists (0 after create / clear). */
+int cart_plane_map_window(cart_plane_map *map, int64_t *origin_x, int64_t *origin_z, int *valid);
+/* Extension.  Test / dump access: synchronises `stream` and copies the cells in window order (row gz - oz, column gx - ox) into
+ * host_cells (HOST, cells_z * cells_x records); without a window every cell is empty and the origin is (0, 0). */
+int cart_plane_map_read(cart_plane_map *map, cart_plane_map_cell *host_cells, int64_t *origin_x, int64_t *origin_z, void *stream);
+/* Extension.  Classes of the window into classes (device u8 [cells_z][cells_x], classes_step bytes per row), with the Plane enum's
+ * values: n = horizontal + vertical (uint64); n < min_votes (>= 1) -> 2 (UNKNOWN), else vertical * 100 >= obstacle_percent
+ * (1..100) * n -> 1 (VERTICAL = obstacle), else 0 (HORIZONTAL = free).  No host synchronisation. */
+int cart_plane_map_classify(cart_plane_map *map, int min_votes, int obstacle_percent, uint8_t *classes, size_t classes_step, void *stream);
+
 /* Stand-in for ImageOpticalFlowModule's device work (src/modules/optflow.cpp:96-140: cvtColor x2 +
  * cv::cuda::NvidiaOpticalFlow_2_0::calc(current, previous), NVIDIA fixed-function hardware): dense census block
  * matching (oracle S15).  cur / prev = the reference images of frame id and id-1 (1-channel gray or 3-channel BGR),
