@@ -111,6 +111,11 @@ class PlaneMapCell(C.Structure):
     _fields_ = [("horizontal", C.c_uint32), ("vertical", C.c_uint32), ("y_min", C.c_int32), ("y_max", C.c_int32)]
 
 
+class MotionParams(C.Structure):
+    # mirrors cart_motion_params (include/cart_engine.h, spec S25); the defaults are cart_motion_default_params'
+    _fields_ = [(n, C.c_double) for n in ("min_disparity", "flow_threshold", "disparity_threshold")] + [(n, C.c_int32) for n in ("radius", "support_percent")]
+
+
 PLACE_MODES = {0: "unknown", 1: "fast", 2: "mixed", 3: "uniform"}                                       # CART_PLACE_MODE_*
 PLACE_STOPS = {0: "nothing to do", 1: "fast set found", 2: "uniform", 3: "tries", 4: "time", 5: "memory"}   # CART_PLACE_STOP_*
 
@@ -192,6 +197,9 @@ PROTOTYPES = {
     "cart_plane_map_window": (_i, [_vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(_i)]),
     "cart_plane_map_read": (_i, [_vp, _vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _vp]),
     "cart_plane_map_classify": (_i, [_vp, _i, _i, _vp, _sz, _vp]),
+    "cart_motion_default_params": (None, [C.POINTER(MotionParams)]),
+    "cart_motion_segment": (_i, [_vp, C.POINTER(EgoCamera), C.POINTER(C.c_double), C.POINTER(MotionParams), _vp, _sz, _vp, _sz, _vp, _sz, _i, _i,
+                                 _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp]),
     "cart_optical_flow": (_i, [_vp, _vp, _sz, _vp, _sz, _i, _i, _i, _vp, _sz, _vp]),
     "cart_flow_default_params": (None, [C.POINTER(FlowParams)]),
     "cart_flow_pyramid_levels": (_i, [_i, _i, _i, C.POINTER(_i), C.POINTER(_i)]),

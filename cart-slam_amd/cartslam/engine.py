@@ -4,12 +4,13 @@ torch is used only for device memory and streams; every op below is one C-ABI ca
 current torch stream.  Tensors are [n, h, w(, c)] or [h, w(, c)] CUDA tensors with a contiguous
 innermost row; row and frame pitches are taken from the strides (like cv::cuda::GpuMat::step).
 """
+import collections
 import ctypes as C
 
 import numpy as np
 
 from . import _lib
-from ._lib import EgoCamera, EgoParams, EngineParams, MatchParams, PlaneMapParams, PlaneParams, SuperpixelParams
+from ._lib import EgoCamera, EgoParams, EngineParams, MatchParams, MotionParams, PlaneMapParams, PlaneParams, SuperpixelParams
 
 INVALID = -32768  # CARTSLAM_DISPARITY_INVALID, reference include/modules/disparity.hpp:17
 
@@ -952,6 +953,58 @@ class PlaneMap(_DeviceObject):
 
     def clear(self):
         self._check(self._lib.cart_plane_map_clear(self._h), "cart_plane_map_clear")
+
+
+def motion_params(**fields):
+    """cart_motion_default_params (spec S25) with the given fields replaced."""
+    p = MotionParams()
+    _lib.load().cart_motion_default_params(C.byref(p))
+    for k, v in fields.items():
+        if k not in dict(MotionParams._fields_):
+            raise ValueError(f"cart_motion_params has no field {k}")
+        setattr(p, k, v)
+    return p
+
+
+MotionSegmentation = collections.namedtuple("MotionSegmentation", "residual raw labels planes_static")
+
+
+def motion_segment(engine, camera, rel, disp_cur, disp_prev, flow, params=None, planes=None, residual=True, raw=False):
+    """Motion segmentation of one frame (cart_motion_segment, spec S25 in DESIGN.md 7.7): camera = EgoCamera or (fx, fy, cx, cy, baseline),
+    rel = 12 numbers, the 3 x 4 (R | t) with p_cur = R p_prev + t (host); disp_cur / disp_prev int16 [h, w] (x16), flow int16 [h, w, 2]
+    (S10.5), planes uint8 [h, w] or None.  raw=True takes device tensors as they are (rows may be pitched) and returns device tensors;
+    otherwise host arrays go up and numpy arrays come back.  -> MotionSegmentation(residual int16 [h, w, 4] or None when residual is
+    false, raw uint8 [h, w], labels uint8 [h, w], planes_static uint8 [h, w] or None when planes is)."""
+    import torch
+    cam = camera if isinstance(camera, EgoCamera) else EgoCamera(*[float(v) for v in camera])
+    p = params if params is not None else motion_params()
+
+    def dev(a, dtype):
+        if raw or a is None:
+            return a
+        return torch.as_tensor(np.ascontiguousarray(a.cpu() if isinstance(a, torch.Tensor) else a), dtype=dtype).cuda()
+    dc, dp, fl, pl = dev(disp_cur, torch.int16), dev(disp_prev, torch.int16), dev(flow, torch.int16), dev(planes, torch.uint8)
+    for t, dtype, dims, what in ((dc, torch.int16, 2, "disp_cur"), (dp, torch.int16, 2, "disp_prev"), (fl, torch.int16, 3, "flow"), (pl, torch.uint8, 2, "planes")):
+        if t is None and what == "planes":
+            continue
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.dim() != dims or tuple(t.shape[:2]) != tuple(dc.shape[:2]) or (dims == 3 and t.shape[2] != 2):
+            raise EngineError(f"{what} must be a device tensor of {dtype} and of the frame's size")
+    h, w = int(dc.shape[0]), int(dc.shape[1])
+    res = torch.empty((h, w, 4), dtype=torch.int16, device=dc.device) if residual else None
+    rawl = torch.empty((h, w), dtype=torch.uint8, device=dc.device)
+    labels = torch.empty((h, w), dtype=torch.uint8, device=dc.device)
+    static = torch.empty((h, w), dtype=torch.uint8, device=dc.device) if pl is not None else None
+    args = []
+    for t, inner in ((dc, 1), (dp, 1), (fl, 2)):
+        args += list(_geom(t, inner)[1:3])
+    args += [w, h]
+    for t, inner in ((res, 2), (rawl, 1), (labels, 1), (pl, 1), (static, 1)):
+        args += list(_geom(t, inner)[1:3]) if t is not None else [None, 0]
+    host_rel = (C.c_double * 12)(*[float(v) for v in np.asarray(rel, np.float64).reshape(-1)])
+    if _lib.load().cart_motion_segment(engine._h, C.byref(cam), host_rel, C.byref(p), *args, _stream_ptr()) != 0:
+        raise EngineError("cart_motion_segment: " + _lib.load().cart_last_error(None).decode())
+    out = MotionSegmentation(res, rawl, labels, static)
+    return out if raw else MotionSegmentation(*[t.cpu().numpy() if t is not None else None for t in out])
 
 
 def plane_cluster(planes, offsets, neighbours):

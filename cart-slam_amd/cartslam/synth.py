@@ -184,3 +184,31 @@ def road_corridor(w, h, fx, fy, cx, cy, baseline, camera_height=1.65, half_width
     sky = (y <= cy) & (d < 3.0)          # the walls end 1/3 of the way to the horizon's vanishing point
     disp[sky], labels[sky] = -32768, 2
     return disp, labels
+
+
+def road_corridor_motion(w, h, fx, fy, cx, cy, baseline, step=0.5, seed=5):
+    """One frame of input for the motion segmentation (spec S25): road_corridor seen again after a forward step of `step` metres, the
+    flow and the previous disparity from the geometry (rounded), a car-sized block painted in that keeps its image position and its
+    disparity (24) although the camera moved, 2 % holes in the previous disparity and a band of rows whose flow is 200 pixels off.
+    -> (rel [12] with p_cur = R p_prev + t, disp_cur, disp_prev, flow int16 [h, w, 2] S10.5, labels, block as a pair of slices)."""
+    dc, planes = road_corridor(w, h, fx, fy, cx, cy, baseline)
+    rel = [1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 1.0, -float(step)]
+    y, x = np.mgrid[0:h, 0:w].astype(np.float64)
+    valid = dc != -32768
+    with np.errstate(divide="ignore", invalid="ignore"):
+        Z = np.where(valid, fx * baseline / (dc / 16.0), 1.0)
+        Zp = Z + step                                                        # p_prev = p_cur - t
+        xp = cx + (x - cx) * Z / Zp
+        yp = cy + (y - cy) * Z / Zp
+    fl = np.zeros((h, w, 2), np.int16)
+    fl[..., 0] = np.round((x - xp) * 32.0)
+    fl[..., 1] = np.round((y - yp) * 32.0)
+    dp = np.full((h, w), -32768, np.int16)
+    xi, yi = (x - (fl[..., 0] >> 5)).astype(np.int64), (y - (fl[..., 1] >> 5)).astype(np.int64)
+    ok = valid & (xi >= 0) & (xi < w) & (yi >= 0) & (yi < h)
+    dp[yi[ok], xi[ok]] = np.round(fx * baseline / Zp[ok] * 16.0)
+    block = (slice(2 * h // 3, 2 * h // 3 + h // 5), slice(2 * w // 5, 2 * w // 5 + w // 9))
+    dc[block], dp[block], fl[block], planes[block] = 24 * 16, 24 * 16, 0, 1
+    dp[np.random.default_rng(seed).random((h, w)) < 0.02] = -32768           # holes in the previous disparity (gate 3)
+    fl[h - 35:h - 25, :, 0] += 200 * 32                                      # a band of wrong flow: its left 200 columns leave the image (gate 2)
+    return rel, dc, dp, fl, planes, block

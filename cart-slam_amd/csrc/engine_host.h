@@ -22,6 +22,7 @@ extern thread_local std::string g_last_error;   // cart_last_error
 extern thread_local int g_last_slot;            // first slot of this thread's most recent compute lease (cart_debug_read)
 
 int fail(const std::string &msg);   // sets g_last_error, returns -1
+int check_camera(const cart_ego_camera *cam);   // fx, fy, baseline > 0 and all finite, else fail() naming the field (engine_planemap.hip)
 
 #define HIP_TRY(expr)                                                                               \
     do {                                                                                            \

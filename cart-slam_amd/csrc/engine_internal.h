@@ -328,6 +328,25 @@ void launch_plane_map_clear(const PlaneMapGrid &grid, int rx0, int rw, int rz0, 
 void launch_plane_map_vote(const PlaneMapVoteArgs &a, hipStream_t s);
 // empty != 0: the map has no window, every class is UNKNOWN
 void launch_plane_map_classify(const PlaneMapGrid &grid, int empty, unsigned min_votes, unsigned percent, uint8_t *out, size_t out_step, hipStream_t s);
+// ---- motion segmentation (motion_kernels.hip) ----
+constexpr int kMotionStrip = 2;     // image rows one lane of the residual kernel handles
+constexpr int kMotionTileW = 64, kMotionTileH = 16, kMotionMaxRadius = 4;   // the filter's tile and the largest halo
+struct MotionArgs {
+    cart_ego_camera cam;
+    cart_motion_params p;
+    double rel[12];
+    const int16_t *disp_cur; size_t disp_cur_step;
+    const int16_t *disp_prev; size_t disp_prev_step;
+    const int16_t *flow; size_t flow_step;
+    int16_t *residual; size_t residual_step;     // may be NULL
+    uint8_t *raw; size_t raw_step;
+    uint8_t *labels; size_t labels_step;
+    const uint8_t *planes; size_t planes_step;   // may be NULL, then planes_static is
+    uint8_t *planes_static; size_t planes_static_step;
+    int w, h;
+};
+void launch_motion_residual(const MotionArgs &a, hipStream_t s);
+void launch_motion_filter(const MotionArgs &a, hipStream_t s);
 void launch_narrow_copy(const void *src, void *dst, size_t bytes, int blocks, hipStream_t s);
 int kernel_count();
 

@@ -5,6 +5,18 @@
 
 using namespace cart_amd;
 
+namespace cart_amd {
+int check_camera(const cart_ego_camera *cam) {   // as cart_ego_*'s; shared with engine_motion.hip (engine_host.h)
+    if (!cam) return fail("camera is NULL");
+    if (!(cam->fx > 0) || !std::isfinite(cam->fx)) return fail("fx must be a positive number");
+    if (!(cam->fy > 0) || !std::isfinite(cam->fy)) return fail("fy must be a positive number");
+    if (!std::isfinite(cam->cx)) return fail("cx must be finite");
+    if (!std::isfinite(cam->cy)) return fail("cy must be finite");
+    if (!(cam->baseline > 0) || !std::isfinite(cam->baseline)) return fail("baseline must be a positive number");
+    return 0;
+}
+}  // namespace cart_amd
+
 extern "C" {
 
 struct cart_plane_map : DeviceObject {
@@ -54,16 +66,6 @@ int cart_plane_map_clear(cart_plane_map *m) {
     if (!m) return fail("map is NULL");
     std::lock_guard<std::mutex> lk(m->mu);
     m->valid = false;   // the next update empties the grid on its stream
-    return 0;
-}
-
-static int check_camera(const cart_ego_camera *cam) {   // as cart_ego_*'s
-    if (!cam) return fail("camera is NULL");
-    if (!(cam->fx > 0) || !std::isfinite(cam->fx)) return fail("fx must be a positive number");
-    if (!(cam->fy > 0) || !std::isfinite(cam->fy)) return fail("fy must be a positive number");
-    if (!std::isfinite(cam->cx)) return fail("cx must be finite");
-    if (!std::isfinite(cam->cy)) return fail("cy must be finite");
-    if (!(cam->baseline > 0) || !std::isfinite(cam->baseline)) return fail("baseline must be a positive number");
     return 0;
 }
 

@@ -16,6 +16,7 @@
 #include "cartslam_amd/modules/egomotion.hpp"
 #include "cartslam_amd/modules/features.hpp"
 #include "cartslam_amd/modules/matches.hpp"
+#include "cartslam_amd/modules/motionseg.hpp"
 #include "cartslam_amd/modules/planefit.hpp"
 #include "cartslam_amd/modules/planemap.hpp"
 #include "cartslam_amd/modules/planeseg.hpp"
@@ -168,7 +169,24 @@ void applyModuleConfig(const Value &modulesConfig, std::shared_ptr<System> syste
             o.minVotes = get(moduleConfig, "min_votes", o.minVotes);
             o.obstaclePercent = get(moduleConfig, "obstacle_percent", o.obstaclePercent);
             o.poseFile = get<std::string>(moduleConfig, "pose_file", "");   // absent: the pose of the ego_motion module
+            o.planesKey = get<std::string>(moduleConfig, "planes_key", o.planesKey);   // "planes_static": the static world only (motion_seg)
             system->addModule<PlaneMapModule>(o);
+        } else if (moduleType == "motion_seg") {  // extension (spec S25): which pixels moved on their own, from disparity, optflow and ego_motion
+            MotionSegOptions o;
+            const CameraIntrinsics K = dataSource->getCameraIntrinsics();   // as for ego_motion
+            o.fx = get(moduleConfig, "fx", (double)K.Q[11]);
+            o.fy = get(moduleConfig, "fy", (double)K.Q[11]);
+            o.cx = get(moduleConfig, "cx", -(double)K.Q[3]);
+            o.cy = get(moduleConfig, "cy", -(double)K.Q[7]);
+            o.baseline = get(moduleConfig, "baseline", K.Q[14] != 0 ? std::fabs(1.0 / (double)K.Q[14]) : 0.0);
+            o.minDisparity = get(moduleConfig, "min_disparity", o.minDisparity);
+            o.flowThreshold = get(moduleConfig, "flow_threshold", o.flowThreshold);
+            o.disparityThreshold = get(moduleConfig, "disparity_threshold", o.disparityThreshold);
+            o.radius = get(moduleConfig, "radius", o.radius);
+            o.supportPercent = get(moduleConfig, "support_percent", o.supportPercent);
+            o.planes = get(moduleConfig, "planes", o.planes);
+            o.components = get(moduleConfig, "components", o.components);
+            system->addModule<MotionSegModule>(o);
         } else if (endsWith(moduleType, "_visualization")) {
             std::cerr << "[cartconfig] skipping GUI module type " << moduleType << " (out of scope)\n";
         } else {

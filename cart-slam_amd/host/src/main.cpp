@@ -19,6 +19,7 @@
 #include "cartslam_amd/modules/egomotion.hpp"
 #include "cartslam_amd/modules/features.hpp"
 #include "cartslam_amd/modules/matches.hpp"
+#include "cartslam_amd/modules/motionseg.hpp"
 #include "cartslam_amd/timing.hpp"
 #include "cartslam_amd/modules/planefit.hpp"
 #include "cartslam_amd/modules/planemap.hpp"
@@ -63,7 +64,8 @@ int main(int argc, char **argv) {
         if (!dump.empty()) {
             const char *keys[] = {CARTSLAM_KEY_DISPARITY, CARTSLAM_KEY_DISPARITY_DERIVATIVE, CARTSLAM_KEY_DISPARITY_DERIVATIVE_HISTOGRAM, CARTSLAM_KEY_PLANES,
                                   CARTSLAM_KEY_PLANE_COMPONENTS, CARTSLAM_KEY_DEPTH, CARTSLAM_KEY_PLANES_UNSMOOTHED, CARTSLAM_KEY_SUPERPIXELS, CARTSLAM_KEY_OPTFLOW,
-                                  CARTSLAM_KEY_PLANE_COMPONENT_TABLE, CARTSLAM_KEY_PLANE_COMPONENT_COUNT};
+                                  CARTSLAM_KEY_PLANE_COMPONENT_TABLE, CARTSLAM_KEY_PLANE_COMPONENT_COUNT, CARTSLAM_KEY_PLANES_STATIC, CARTSLAM_KEY_MOTION_COMPONENTS,
+                                  CARTSLAM_KEY_MOTION_COMPONENT_TABLE, CARTSLAM_KEY_MOTION_COMPONENT_COUNT};
             for (int id = 1; id <= frames; ++id) {
                 std::shared_ptr<cart::SystemRunData> run;
                 try { run = system->getRunById((uint32_t)id); } catch (const std::exception &) { continue; }  // evicted (retention ring)
@@ -118,6 +120,16 @@ int main(int argc, char **argv) {
                     o.write(reinterpret_cast<const char *>(pm->cells.data()), (std::streamsize)(pm->cells.size() * sizeof(cart_plane_map_cell)));
                     const auto classes = pm->classes.downloadTight();
                     o.write(reinterpret_cast<const char *>(classes.data()), (std::streamsize)classes.size());
+                }
+                if (run->hasData(CARTSLAM_KEY_MOTION)) {   // int32 width, height; the filtered labels, the raw labels, the residual records
+                    auto labels = run->getData<cart::image_t>(CARTSLAM_KEY_MOTION);
+                    std::ofstream o(dump + "/" + std::to_string(id) + "_" + CARTSLAM_KEY_MOTION + ".bin", std::ios::binary);
+                    const int32_t shape[2] = {labels->cols, labels->rows};
+                    o.write(reinterpret_cast<const char *>(shape), sizeof(shape));
+                    for (const char *k : {CARTSLAM_KEY_MOTION, CARTSLAM_KEY_MOTION_UNSMOOTHED, CARTSLAM_KEY_MOTION_RESIDUAL}) {
+                        const auto bytes = run->getData<cart::image_t>(k)->downloadTight();
+                        o.write(reinterpret_cast<const char *>(bytes.data()), (std::streamsize)bytes.size());
+                    }
                 }
                 if (run->hasData(CARTSLAM_KEY_PLANES_EQ_LABEL_PLANES)) {   // f64 [max_label + 1][4]
                     auto lp = run->getData<std::vector<cart::Vec4d>>(CARTSLAM_KEY_PLANES_EQ_LABEL_PLANES);

@@ -53,7 +53,8 @@ PlaneMapModule::PlaneMapModule(const PlaneMapOptions &options)
         }
     }
     this->requiresData.push_back(module_dependency_t(CARTSLAM_KEY_DISPARITY));
-    this->requiresData.push_back(module_dependency_t(CARTSLAM_KEY_PLANES));
+    if (options.planesKey.empty()) throw std::invalid_argument("planes_key must name a blackboard image");
+    this->requiresData.push_back(module_dependency_t(options.planesKey));
     if (options.poseFile.empty()) this->requiresData.push_back(module_dependency_t(CARTSLAM_KEY_EGO_MOTION));
     this->requiresData.push_back(module_dependency_t(CARTSLAM_KEY_PLANE_MAP, -1));   // one frame at a time, in order
     this->providesData.push_back(CARTSLAM_KEY_PLANE_MAP);
@@ -66,10 +67,10 @@ PlaneMapModule::~PlaneMapModule() {
 
 system_data_t PlaneMapModule::runInternal(System &, SystemRunData &data) {
     auto disparity = data.getData<image_t>(CARTSLAM_KEY_DISPARITY);
-    auto planes = data.getData<image_t>(CARTSLAM_KEY_PLANES);
+    auto planes = data.getData<image_t>(options.planesKey);
     if (disparity->empty() || disparity->type() != CV_16SC1) throw std::runtime_error("Disparity must be of type CV_16SC1");
-    if (planes->empty() || planes->type() != CV_8UC1 || planes->rows != disparity->rows || planes->cols != disparity->cols)
-        throw std::runtime_error("PlaneMapModule: planes must be a CV_8UC1 image of the disparity's size");
+    if (!planes || planes->empty() || planes->type() != CV_8UC1 || planes->rows != disparity->rows || planes->cols != disparity->cols)
+        throw std::runtime_error("PlaneMapModule: " + options.planesKey + " must be a CV_8UC1 image of the disparity's size");
     double pose[12];
     if (options.poseFile.empty()) {   // a frame whose ego_motion.status is 0 carries the kept pose
         std::memcpy(pose, data.getData<EgoMotion>(CARTSLAM_KEY_EGO_MOTION)->pose, sizeof(pose));

@@ -596,6 +596,45 @@ int cart_plane_map_read(cart_plane_map *map, cart_plane_map_cell *host_cells, in
  * (1..100) * n -> 1 (VERTICAL = obstacle), else 0 (HORIZONTAL = free).  No host synchronisation. */
 int cart_plane_map_classify(cart_plane_map *map, int min_votes, int obstacle_percent, uint8_t *classes, size_t classes_step, void *stream);
 
+/* ---- Motion segmentation from flow, disparity and ego-motion (spec S25) ------------------------------------------
+ * An extension: the reference has no such stage.  A pixel moves on its own if the point seen there in frame t-1 (through the flow and
+ * the previous disparity), carried through the relative pose and projected back, does not land where the image and the disparity of
+ * frame t see it.  fp64 with + - * / floor only, every sum in the written order, no atomics: restated in tests/np_motion.py.
+ *   Raw label of pixel (x, y); the first failing gate makes it 2 (UNKNOWN):
+ *     1. s_c = disp_cur[y][x] != -32768 and d_c = s_c / 16.0 >= min_disparity;
+ *     2. xp = x - (flow.x >> 5), yp = y - (flow.y >> 5) (arithmetic shifts of the S10.5 components) lie inside the image;
+ *     3. s_p = disp_prev[yp][xp] passes the gate of step 1, giving d_p;
+ *     4. Zp = (fx baseline) / d_p, Xp = ((xp - cx) Zp) / fx, Yp = ((yp - cy) Zp) / fy,
+ *        q[r] = ((rel[4r] Xp + rel[4r+1] Yp) + rel[4r+2] Zp) + rel[4r+3], and q.z > 0.
+ *   Then eu = ((fx q.x) / q.z + cx) - x, ev = ((fy q.y) / q.z + cy) - y, ed = (fx baseline) / q.z - d_c, and the label is 1 (MOVING)
+ *   iff eu eu + ev ev > flow_threshold^2 or ed ed > disparity_threshold^2, else 0 (STATIC).  The three values are the Plane enum's, so
+ *   cart_plane_ccl_table works on a motion label image unchanged.
+ *   Residual record (int16 x 4): (Q(eu), Q(ev), Q(ed), raw label) with Q(e) = clamp(floor(16 e + 0.5), -32767, 32767) and Q(NaN) = -32767 (reachable only where a camera's fx baseline overflows); an UNKNOWN
+ *   pixel holds (-32768, -32768, -32768, 2).
+ *   Filtered label: raw 2 stays 2; else with n_m / n_s the raw 1 / raw 0 pixels of the (2 radius + 1)^2 window clipped to the image,
+ *   the pixel itself included, 1 iff n_m 100 >= support_percent (n_m + n_s), else 0.  radius = 0: filtered = raw.
+ *   Static planes: planes_static = (filtered == 1) ? 2 : planes. */
+typedef struct cart_motion_params {
+    double min_disparity;                     /* pixels, > 0 */
+    double flow_threshold;                    /* pixels, > 0 */
+    double disparity_threshold;               /* pixels, > 0 */
+    int32_t radius;                           /* 0..4 */
+    int32_t support_percent;                  /* 1..100 */
+} cart_motion_params;
+void cart_motion_default_params(cart_motion_params *p); /* extension: 1.0, 2.0, 1.0, 2, 50 (build-owned, untuned) */
+/* Extension.  One frame, stateless: every buffer is the caller's device memory, width x height (1..16384 each), steps in bytes.
+ * rel = HOST double [12], the 3 x 4 (R | t) in row order with p_cur = R p_prev + t (cart_ego_result's R and t as a KITTI pose row; all
+ * finite, |R entries| <= 2, |t entries| <= 1e6).  disp_cur / disp_prev = int16 x16 (2-byte aligned), flow = int16 x 2 in S10.5 of the
+ * current frame against the previous one (4-byte aligned), residual = int16 x 4 (8-byte aligned; may be NULL), raw / labels = u8;
+ * planes (may be NULL) / planes_static (NULL iff planes is) = u8.  Steps are multiples of the alignment.  No output (residual, raw,
+ * labels, planes_static) may overlap another output or an input: each such pair is refused by name.  Checked in this order, all before any device call: params, camera, rel, sizes, engine, then
+ * pointers, alignment and steps; a refused call touches no output.  Asynchronous on `stream`, no host synchronisation. */
+int cart_motion_segment(cart_engine *engine, const cart_ego_camera *camera, const double *rel, const cart_motion_params *params,
+                        const int16_t *disp_cur, size_t disp_cur_step, const int16_t *disp_prev, size_t disp_prev_step,
+                        const int16_t *flow, size_t flow_step, int width, int height, int16_t *residual, size_t residual_step,
+                        uint8_t *raw, size_t raw_step, uint8_t *labels, size_t labels_step, const uint8_t *planes, size_t planes_step,
+                        uint8_t *planes_static, size_t planes_static_step, void *stream);
+
 /* Stand-in for ImageOpticalFlowModule's device work (src/modules/optflow.cpp:96-140: cvtColor x2 +
  * cv::cuda::NvidiaOpticalFlow_2_0::calc(current, previous), NVIDIA fixed-function hardware): dense census block
  * matching (oracle S15).  cur / prev = the reference images of frame id and id-1 (1-channel gray or 3-channel BGR),
