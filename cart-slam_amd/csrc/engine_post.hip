@@ -8,6 +8,9 @@
 using namespace cart_amd;
 
 namespace {
+// Kernels that access a pair or a word as one 4-byte value need the base on a 4-byte boundary as well as the steps.
+bool misaligned4(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3) != 0; }
+
 // The strided and the _multi form of a plane stage share one body.  Frame f of an image argument is base + f * frame stride
 // bytes or, with pointer tables (base NULL, frame stride 0), the table's f-th entry; a launch takes at most kLaunchFrames of those.
 template <typename T>
@@ -73,6 +76,7 @@ int cart_interpolate(cart_engine *e, int n_frames, int16_t *disp, size_t step, s
                      int iterations, int min_disp16, int max_disp, void *stream_) {
     if (!e) return fail("engine is NULL");
     if (!disp) return fail("NULL image pointer");
+    if (n_frames <= 0) return fail("n_frames must be positive");
     if (radius <= 0 || iterations <= 0) return 0;
     if (radius > 8) return fail("radius must be <= 8");
     const Geometry &g = e->g;
@@ -108,6 +112,7 @@ int cart_disparity_derivative(cart_engine *e, int n_frames, const int16_t *disp,
     const Geometry &g = e->g;
     if (disp_step < (size_t)g.w * 2 || out_step < (size_t)g.w * 4 || (out_step & 3) || (out_frame_stride & 3) || (disp_step & 1) || (disp_frame_stride & 1))
         return fail("bad step (derivative rows must be 4-byte aligned)");
+    if (misaligned4(out)) return fail("out must be 4-byte aligned");
     HIP_TRY(hipSetDevice(e->params.device_id));
     launch_dir_derivative(disp, disp_step, disp_frame_stride, out, out_step, out_frame_stride, hist512, g.w, g.h, n_frames,
                           static_cast<hipStream_t>(stream_));
@@ -143,8 +148,10 @@ int cart_plane_ccl(cart_engine *e, int n_frames, const uint8_t *planes, size_t p
                    int32_t *ids, size_t ids_step, size_t ids_frame_stride, int32_t *n_components, void *stream_) {
     if (!e) return fail("engine is NULL");
     if (!planes || !ids) return fail("NULL pointer");
+    if (n_frames <= 0) return fail("n_frames must be positive");
     const Geometry &g = e->g;
     if (planes_step < (size_t)g.w || ids_step < (size_t)g.w * 4 || (ids_step & 3) || (ids_frame_stride & 3)) return fail("bad step");
+    if (misaligned4(ids)) return fail("ids must be 4-byte aligned");
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     HIP_TRY(hipSetDevice(e->params.device_id));
     SlotLease l;
@@ -174,8 +181,10 @@ int cart_plane_ccl_stats(cart_engine *e, int n_frames, const uint8_t *planes, si
     if (!e) return fail("engine is NULL");
     if (!planes || !ids || !table) return fail("NULL pointer");
     if (max_components < 1) return fail("max_components must be positive");
+    if (n_frames <= 0) return fail("n_frames must be positive");
     const Geometry &g = e->g;
     if (planes_step < (size_t)g.w || ids_step < (size_t)g.w * 4 || (ids_step & 3) || (ids_frame_stride & 3)) return fail("bad step");
+    if (misaligned4(ids)) return fail("ids must be 4-byte aligned");
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     HIP_TRY(hipSetDevice(e->params.device_id));
     if (ensure_ccl_stats_ws(e)) return -1;
@@ -193,8 +202,10 @@ int cart_plane_ccl_table(cart_engine *e, int n_frames, const uint8_t *planes, si
     if (!e) return fail("engine is NULL");
     if (!planes || !ids || !table) return fail("NULL pointer");
     if (max_components < 1) return fail("max_components must be positive");
+    if (n_frames <= 0) return fail("n_frames must be positive");
     const Geometry &g = e->g;
     if (planes_step < (size_t)g.w || ids_step < (size_t)g.w * 4 || (ids_step & 3) || (ids_frame_stride & 3)) return fail("bad step");
+    if (misaligned4(ids)) return fail("ids must be 4-byte aligned");
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     HIP_TRY(hipSetDevice(e->params.device_id));
     if (ensure_ccl_stats_ws(e)) return -1;
@@ -292,6 +303,7 @@ int cart_plane_temporal_vote(cart_engine *e, const uint8_t *planes, size_t plane
     for (int k = 0; k < n_prev; ++k) {
         if (!prev_planes[k] || !flows[k]) return fail("NULL entry in the temporal tables");
         if (prev_steps[k] < (size_t)g.w || flow_steps[k] < (size_t)g.w * 4 || (flow_steps[k] & 3)) return fail("bad step in the temporal tables");
+        if (misaligned4(flows[k])) return fail("flow images must be 4-byte aligned");
         t.prev[k] = prev_planes[k]; t.prev_step[k] = prev_steps[k]; t.flow[k] = flows[k]; t.flow_step[k] = flow_steps[k];
     }
     HIP_TRY(hipSetDevice(e->params.device_id));
@@ -308,6 +320,7 @@ int cart_reproject_depth(cart_engine *e, int n_frames, const int16_t *disp, size
     const Geometry &g = e->g;
     if (disp_step < (size_t)g.w * 2 || (disp_step & 1) || (disp_frame_stride & 1) || xyz_step < (size_t)g.w * 12 || (xyz_step & 3) || (xyz_frame_stride & 3))
         return fail("bad step");
+    if (misaligned4(xyz)) return fail("xyz must be 4-byte aligned");
     HIP_TRY(hipSetDevice(e->params.device_id));
     QMatrix q;
     std::memcpy(q.q, Q, sizeof(q.q));

@@ -271,7 +271,8 @@ __global__ __launch_bounds__(256) void temporal_vote_kernel(const uint8_t *plane
     const int px = blockIdx.x * 64 + threadIdx.x, py = blockIdx.y * 4 + threadIdx.y;
     if (px >= w || py >= h) return;
     int votes[3] = {0, 0, 0};
-    votes[planes[(size_t)py * pstep + px]]++;
+    // a label byte above CART_PLANE_UNKNOWN (not a label) counts as UNKNOWN: it must not index past the array
+    votes[min((int)planes[(size_t)py * pstep + px], (int)CART_PLANE_UNKNOWN)]++;
     int x = px, y = py;
     for (int k = 0; k < t.n_prev; ++k) {
         // the reference reads the flow at the ORIGINAL pixel, not at the tracked position (:212-213)
@@ -279,7 +280,7 @@ __global__ __launch_bounds__(256) void temporal_vote_kernel(const uint8_t *plane
         x -= (int16_t)(f.x >> 5);  // S10.5 -> whole pixels (:216-217)
         y -= (int16_t)(f.y >> 5);
         if (x < 0 || y < 0 || x >= w || y >= h) continue;
-        votes[t.prev[k][(size_t)y * t.prev_step[k] + x]]++;
+        votes[min((int)t.prev[k][(size_t)y * t.prev_step[k] + x], (int)CART_PLANE_UNKNOWN)]++;
     }
     int best = votes[CART_PLANE_HORIZONTAL] > votes[CART_PLANE_VERTICAL] ? CART_PLANE_HORIZONTAL : CART_PLANE_VERTICAL;
     if (votes[best] == 0) best = CART_PLANE_UNKNOWN;

@@ -177,13 +177,14 @@ int cart_compute_disparity_multi(cart_engine *engine, int n_frames,
                                  int16_t *const *out, size_t out_step, void *stream);
 
 /* replaces: cart::disparity::interpolate (interpolation.cu:85-99) on its own; in place like the
- * reference's (the engine double-buffers internally).  min_disp16 / max_disp as disparity.hpp:27-28. */
+ * reference's (the engine double-buffers internally).  min_disp16 / max_disp as disparity.hpp:27-28.
+ * n_frames in [1, max_inflight]. */
 int cart_interpolate(cart_engine *engine, int n_frames, int16_t *disp, size_t step, size_t frame_stride,
                      int radius, int iterations, int min_disp16, int max_disp, void *stream);
 
 /* replaces: ImageDisparityDerivativeModule::runInternal (src/modules/disparity/derivative.cu:151-184):
  * out = CV_16SC2-shaped (ch0 vertical, ch1 horizontal), hist = 1x256 CV_32SC2-shaped device
- * buffer (512 int32 per frame), overwritten. */
+ * buffer (512 int32 per frame), overwritten.  out, out_step and out_frame_stride on 4 bytes (a pixel is written as one word). */
 int cart_disparity_derivative(cart_engine *engine, int n_frames,
                               const int16_t *disp, size_t disp_step, size_t disp_frame_stride,
                               int16_t *out, size_t out_step, size_t out_frame_stride,
@@ -219,7 +220,8 @@ int cart_plane_classify_multi(cart_engine *engine, int n_frames,
 
 /* replaces: the temporal-voting branch of classifyPlanes (planeseg.cu:199-240) with the tables the module builds at
  * :303-347: prev_planes[k] = unsmoothed planes of frame id-(k+1), flows[k] = optical flow of frame id-k (CV_16SC2-shaped,
- * S10.5 fixed point).  n_prev <= 8.  The pointer arrays are HOST arrays of DEVICE pointers.  Single frame: temporal
+ * S10.5 fixed point, each image and its step on 4 bytes).  n_prev <= 8.  A label byte above CART_PLANE_UNKNOWN counts as UNKNOWN.
+ * The pointer arrays are HOST arrays of DEVICE pointers.  Single frame: temporal
  * smoothing makes frames depend on each other, so it does not shard. */
 #define CART_MAX_TEMPORAL 8
 int cart_plane_temporal_vote(cart_engine *engine, const uint8_t *planes, size_t planes_step, int n_prev,
@@ -229,7 +231,8 @@ int cart_plane_temporal_vote(cart_engine *engine, const uint8_t *planes, size_t 
 
 /* New stage (no reference counterpart; BASELINE config 3 "plane CCL"): 4-connected components of
  * the label map over labels {0,1}; id = smallest linear index y*width+x of the component,
- * UNKNOWN pixels -> -1.  n_components (device, one int32 per frame) may be NULL. */
+ * UNKNOWN pixels -> -1.  n_components (device, one int32 per frame) may be NULL.  n_frames in [1, max_inflight]; ids, ids_step
+ * and ids_frame_stride on 4 bytes (the same for the two entry points below). */
 int cart_plane_ccl(cart_engine *engine, int n_frames,
                    const uint8_t *planes, size_t planes_step, size_t planes_frame_stride,
                    int32_t *ids, size_t ids_step, size_t ids_frame_stride,
@@ -287,7 +290,8 @@ int cart_plane_classify_dev(cart_engine *engine, int n_frames,
 
 /* replaces: DepthModule::runInternal (src/modules/depth.cpp:9-25): disparity x16 -> float (1/16) and
  * cv::cuda::reprojectImageTo3D(Q, 3 channels).  Q = row-major 4x4 (HOST pointer, copied), out = CV_32FC3-shaped.
- * Floating point: results are within 1e-4 relative of the CPU restatement. */
+ * Floating point: results are within 1e-4 relative of the CPU restatement (the same single-precision operations in the same order,
+ * built without contraction).  xyz, xyz_step and xyz_frame_stride on 4 bytes. */
 int cart_reproject_depth(cart_engine *engine, int n_frames,
                          const int16_t *disp, size_t disp_step, size_t disp_frame_stride, const float Q[16],
                          float *xyz, size_t xyz_step, size_t xyz_frame_stride, void *stream);

@@ -471,14 +471,15 @@ void cart_oracle_temporal_vote(const uint8_t *planes, int w, int h, int n_prev, 
     for (int py = 0; py < h; py++)
         for (int px = 0; px < w; px++) {
             int votes[3] = {0, 0, 0};
-            votes[planes[(size_t)py * w + px]]++;
+            /* a label byte above 2 (not a label) counts as UNKNOWN */
+            votes[planes[(size_t)py * w + px] > 2 ? 2 : planes[(size_t)py * w + px]]++;
             int x = px, y = py;
             for (int k = 0; k < n_prev; k++) {
                 int16_t fx = flows[k][((size_t)py * w + px) * 2 + 0], fy = flows[k][((size_t)py * w + px) * 2 + 1];
                 fx = (int16_t)(fx >> 5); fy = (int16_t)(fy >> 5);
                 x -= fx; y -= fy;
                 if (x < 0 || y < 0 || x >= w || y >= h) continue;
-                votes[prev_planes[k][(size_t)y * w + x]]++;
+                votes[prev_planes[k][(size_t)y * w + x] > 2 ? 2 : prev_planes[k][(size_t)y * w + x]]++;
             }
             int best = votes[0] > votes[1] ? 0 : 1;
             if (votes[best] == 0) best = 2;

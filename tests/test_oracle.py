@@ -138,6 +138,42 @@ def test_derivatives_classify_ccl():
     assert (ids[pl2 == 2] == -1).all()
 
 
+def _np_temporal_vote(planes, prev, flows):
+    """planeseg.cu:199-240 in numpy: a vote per image for HORIZONTAL or VERTICAL, every other label byte (UNKNOWN and anything above it) for neither."""
+    h, w = planes.shape
+    votes = np.zeros((2, h, w), np.int64)
+    for c in (0, 1):
+        votes[c] += planes == c
+    y, x = np.indices((h, w))
+    for p, f in zip(prev, flows):
+        x = x - (f[..., 0].astype(np.int64) >> 5)     # the flow at the ORIGINAL pixel; a position outside the image is kept for the next step
+        y = y - (f[..., 1].astype(np.int64) >> 5)
+        inside = (x >= 0) & (x < w) & (y >= 0) & (y < h)
+        label = p[np.clip(y, 0, h - 1), np.clip(x, 0, w - 1)]
+        for c in (0, 1):
+            votes[c] += inside & (label == c)
+    best = np.where(votes[0] > votes[1], 0, 1)
+    return np.where(np.maximum(votes[0], votes[1]) == 0, 2, best).astype(np.uint8)
+
+
+@pytest.mark.parametrize("labels", [(0, 1, 2), (0, 1, 2, 2, 3, 255)], ids=["labels", "bytes_above_two"])
+def test_temporal_vote_matches_numpy_also_with_label_bytes_above_two(labels):
+    """A label byte above 2 is no label: it counts as UNKNOWN and must not index past the three votes."""
+    rng = np.random.default_rng(len(labels))
+    h, w = 23, 37
+    for n_prev in (0, 1, 8):
+        images = [rng.choice(np.array(labels, np.uint8), (h, w)) for _ in range(n_prev + 1)]
+        flows = [rng.integers(-200, 201, (h, w, 2)).astype(np.int16) for _ in range(n_prev)]
+        for a in images:
+            a[2:6, 4:12] = max(labels)
+        for f in flows:
+            f[2:6, 4:12] = 0
+        got = O.temporal_vote(images[0], images[1:], flows)
+        assert all((got == c).any() for c in (0, 1, 2))
+        assert (got == _np_temporal_vote(images[0], images[1:], flows)).all(), n_prev
+        assert (got == O.temporal_vote(np.minimum(images[0], 2), [np.minimum(a, 2) for a in images[1:]], flows)).all()
+
+
 def test_find_peaks_and_params():
     rng = np.random.default_rng(11)
     for k in range(30):
