@@ -116,6 +116,21 @@ class MotionParams(C.Structure):
     _fields_ = [(n, C.c_double) for n in ("min_disparity", "flow_threshold", "disparity_threshold")] + [(n, C.c_int32) for n in ("radius", "support_percent")]
 
 
+class DenseEgoParams(C.Structure):
+    # mirrors cart_dense_ego_params (include/cart_engine.h, spec S26); the defaults are cart_dense_ego_default_params'
+    _fields_ = [(n, C.c_double) for n in ("min_disparity", "flow_threshold", "disparity_threshold", "disparity_weight")] + \
+               [(n, C.c_int32) for n in ("iterations", "stride", "min_inliers")]
+
+
+class DenseEgoResult(C.Structure):
+    # mirrors cart_dense_ego_result (include/cart_engine.h, spec S26)
+    _fields_ = [("R", C.c_double * 9), ("t", C.c_double * 3), ("rms_initial", C.c_double), ("rms", C.c_double)] + \
+               [(n, C.c_int32) for n in ("status", "n_candidates", "n_initial", "n_inliers", "steps", "reserved")]
+
+
+DENSE_EGO_MAX_ITERATIONS = 16   # CART_DENSE_EGO_MAX_ITERATIONS
+
+
 PLACE_MODES = {0: "unknown", 1: "fast", 2: "mixed", 3: "uniform"}                                       # CART_PLACE_MODE_*
 PLACE_STOPS = {0: "nothing to do", 1: "fast set found", 2: "uniform", 3: "tries", 4: "time", 5: "memory"}   # CART_PLACE_STOP_*
 
@@ -200,6 +215,11 @@ PROTOTYPES = {
     "cart_motion_default_params": (None, [C.POINTER(MotionParams)]),
     "cart_motion_segment": (_i, [_vp, C.POINTER(EgoCamera), C.POINTER(C.c_double), C.POINTER(MotionParams), _vp, _sz, _vp, _sz, _vp, _sz, _i, _i,
                                  _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp]),
+    "cart_dense_ego_default_params": (None, [C.POINTER(DenseEgoParams)]),
+    "cart_dense_ego_create": (_i, [_vp, _i, _i, C.POINTER(_vp)]),
+    "cart_dense_ego_destroy": (None, [_vp]),
+    "cart_dense_ego_refine": (_i, [_vp, C.POINTER(EgoCamera), C.POINTER(C.c_double), C.POINTER(DenseEgoParams), _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz,
+                                   _i, _i, _vp, _vp]),
     "cart_optical_flow": (_i, [_vp, _vp, _sz, _vp, _sz, _i, _i, _i, _vp, _sz, _vp]),
     "cart_flow_default_params": (None, [C.POINTER(FlowParams)]),
     "cart_flow_pyramid_levels": (_i, [_i, _i, _i, C.POINTER(_i), C.POINTER(_i)]),

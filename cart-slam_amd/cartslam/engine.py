@@ -10,7 +10,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import EgoCamera, EgoParams, EngineParams, MatchParams, MotionParams, PlaneMapParams, PlaneParams, SuperpixelParams
+from ._lib import DenseEgoParams, EgoCamera, EgoParams, EngineParams, MatchParams, MotionParams, PlaneMapParams, PlaneParams, SuperpixelParams
 
 INVALID = -32768  # CARTSLAM_DISPARITY_INVALID, reference include/modules/disparity.hpp:17
 
@@ -1005,6 +1005,74 @@ def motion_segment(engine, camera, rel, disp_cur, disp_prev, flow, params=None, 
         raise EngineError("cart_motion_segment: " + _lib.load().cart_last_error(None).decode())
     out = MotionSegmentation(res, rawl, labels, static)
     return out if raw else MotionSegmentation(*[t.cpu().numpy() if t is not None else None for t in out])
+
+
+DENSE_EGO_RESULT_DTYPE = np.dtype([("R", "<f8", 9), ("t", "<f8", 3), ("rms_initial", "<f8"), ("rms", "<f8"), ("status", "<i4"), ("n_candidates", "<i4"),
+                                   ("n_initial", "<i4"), ("n_inliers", "<i4"), ("steps", "<i4"), ("reserved", "<i4")])   # cart_dense_ego_result
+
+
+def dense_ego_params(**fields):
+    """cart_dense_ego_default_params (spec S26) with the given fields replaced."""
+    p = DenseEgoParams()
+    _lib.load().cart_dense_ego_default_params(C.byref(p))
+    for k, v in fields.items():
+        if k not in dict(DenseEgoParams._fields_):
+            raise ValueError(f"cart_dense_ego_params has no field {k}")
+        setattr(p, k, v)
+    return p
+
+
+class DenseEgo(_DeviceObject):
+    """Dense refinement of a relative pose from flow and disparity (cart_dense_ego_* in the C ABI, spec S26 in DESIGN.md 7.8): Gauss-Newton
+    over every static pixel of frames of up to max_width x max_height.  A context manager; close() destroys the device object."""
+    _name = "dense_ego"
+
+    def __init__(self, engine, max_width, max_height):
+        self.max_width, self.max_height = int(max_width), int(max_height)
+        super().__init__(engine, self.max_width, self.max_height)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def refine(self, camera, rel, disp_cur, disp_prev, flow, params=None, mask=None, stream=None, raw=False):
+        """camera = EgoCamera or (fx, fy, cx, cy, baseline); rel = 12 numbers, the 3 x 4 (R | t) to refine (host); disp_cur / disp_prev int16
+        [h, w] (x16), flow int16 [h, w, 2] (S10.5), mask uint8 [h, w] (motion_segment's labels) or None: device tensors are taken as they
+        are (rows may be pitched), host arrays go up.  stream = a torch stream (default: the current one).  -> the result as a
+        DENSE_EGO_RESULT_DTYPE array of one record (host); raw=True returns the device tensor (136 bytes as float64) with no host round
+        trip."""
+        import torch
+        cam = camera if isinstance(camera, EgoCamera) else EgoCamera(*[float(v) for v in camera])
+        p = params if params is not None else dense_ego_params()
+
+        def dev(a, dtype):
+            if a is None or isinstance(a, torch.Tensor):
+                return a
+            return torch.as_tensor(np.ascontiguousarray(a), dtype=dtype).cuda()
+        with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):   # uploads and the result's allocation on the call's stream
+            dc, dp, fl, mk = dev(disp_cur, torch.int16), dev(disp_prev, torch.int16), dev(flow, torch.int16), dev(mask, torch.uint8)
+        for t, dtype, dims, what in ((dc, torch.int16, 2, "disp_cur"), (dp, torch.int16, 2, "disp_prev"), (fl, torch.int16, 3, "flow"), (mk, torch.uint8, 2, "mask")):
+            if t is None and what == "mask":
+                continue
+            if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.dim() != dims or tuple(t.shape[:2]) != tuple(dc.shape[:2]) or (dims == 3 and t.shape[2] != 2):
+                raise EngineError(f"{what} must be a device tensor of {dtype} and of the frame's size")
+        h, w = int(dc.shape[0]), int(dc.shape[1])
+        args = []
+        for t, inner in ((dc, 1), (dp, 1), (fl, 2), (mk, 1)):
+            args += list(_geom(t, inner)[1:3]) if t is not None else [None, 0]
+        res = torch.empty(DENSE_EGO_RESULT_DTYPE.itemsize // 8, dtype=torch.float64, device=dc.device)   # every byte is written by the call
+        host_rel = (C.c_double * 12)(*[float(v) for v in np.asarray(rel, np.float64).reshape(-1)])
+        sp = C.c_void_p(stream.cuda_stream) if stream is not None else _stream_ptr()
+        self._check(self._lib.cart_dense_ego_refine(self._h, C.byref(cam), host_rel, C.byref(p), *args, w, h, C.c_void_p(res.data_ptr()), sp),
+                    "cart_dense_ego_refine")
+        if raw:
+            return res
+        if stream is not None:
+            stream.synchronize()
+        return res.cpu().numpy().view(DENSE_EGO_RESULT_DTYPE).reshape(-1)
 
 
 def plane_cluster(planes, offsets, neighbours):

@@ -347,6 +347,31 @@ struct MotionArgs {
 };
 void launch_motion_residual(const MotionArgs &a, hipStream_t s);
 void launch_motion_filter(const MotionArgs &a, hipStream_t s);
+// ---- dense ego-motion refinement (dense_ego_kernels.hip) ----
+constexpr int kDenseLanes = 256;    // threads of a workgroup = virtual lanes of the S26 sums
+constexpr int kDenseSums = 28;      // 21 upper entries of H (row-major, i <= j), the 6 of g, e2
+constexpr int kDenseWords = 29;     // 8-byte words of a row partial: the sums, then (count, candidates) as two int32
+constexpr int kDenseCols = 4;       // sampled columns of a lane whose loads are issued together
+struct DenseEgoState {              // what stays on the device between the launches of one call
+    double R[9], t[3];
+    double rms_initial;
+    int32_t n_initial, n_candidates, steps, stop;
+};
+struct DenseEgoArgs {
+    cart_ego_camera cam;
+    cart_dense_ego_params p;
+    double rel0[12];
+    const int16_t *disp_cur; size_t disp_cur_step;
+    const int16_t *disp_prev; size_t disp_prev_step;
+    const int16_t *flow; size_t flow_step;
+    const uint8_t *mask; size_t mask_step;       // may be NULL
+    int w, h, ni, nj;                            // the image and its sample grid
+    int rows_cap;                                // rows of the partial table: word k of sampled row j is partial[k * rows_cap + j]
+    double *partial;
+    DenseEgoState *state;
+    cart_dense_ego_result *result;
+};
+void launch_dense_ego(const DenseEgoArgs &a, hipStream_t s);   // the 2 (iterations + 1) launches of one call
 void launch_narrow_copy(const void *src, void *dst, size_t bytes, int blocks, hipStream_t s);
 int kernel_count();
 

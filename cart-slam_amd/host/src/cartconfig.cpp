@@ -16,6 +16,7 @@
 #include "cartslam_amd/modules/egomotion.hpp"
 #include "cartslam_amd/modules/features.hpp"
 #include "cartslam_amd/modules/matches.hpp"
+#include "cartslam_amd/modules/denseego.hpp"
 #include "cartslam_amd/modules/motionseg.hpp"
 #include "cartslam_amd/modules/planefit.hpp"
 #include "cartslam_amd/modules/planemap.hpp"
@@ -170,6 +171,7 @@ void applyModuleConfig(const Value &modulesConfig, std::shared_ptr<System> syste
             o.obstaclePercent = get(moduleConfig, "obstacle_percent", o.obstaclePercent);
             o.poseFile = get<std::string>(moduleConfig, "pose_file", "");   // absent: the pose of the ego_motion module
             o.planesKey = get<std::string>(moduleConfig, "planes_key", o.planesKey);   // "planes_static": the static world only (motion_seg)
+            o.poseKey = get<std::string>(moduleConfig, "pose_key", o.poseKey);         // "dense_ego": the refined trajectory
             system->addModule<PlaneMapModule>(o);
         } else if (moduleType == "motion_seg") {  // extension (spec S25): which pixels moved on their own, from disparity, optflow and ego_motion
             MotionSegOptions o;
@@ -187,6 +189,23 @@ void applyModuleConfig(const Value &modulesConfig, std::shared_ptr<System> syste
             o.planes = get(moduleConfig, "planes", o.planes);
             o.components = get(moduleConfig, "components", o.components);
             system->addModule<MotionSegModule>(o);
+        } else if (moduleType == "dense_ego") {  // extension (spec S26): ego_motion's relative pose refined over every static pixel
+            DenseEgoOptions o;
+            const CameraIntrinsics K = dataSource->getCameraIntrinsics();   // as for ego_motion
+            o.fx = get(moduleConfig, "fx", (double)K.Q[11]);
+            o.fy = get(moduleConfig, "fy", (double)K.Q[11]);
+            o.cx = get(moduleConfig, "cx", -(double)K.Q[3]);
+            o.cy = get(moduleConfig, "cy", -(double)K.Q[7]);
+            o.baseline = get(moduleConfig, "baseline", K.Q[14] != 0 ? std::fabs(1.0 / (double)K.Q[14]) : 0.0);
+            o.minDisparity = get(moduleConfig, "min_disparity", o.minDisparity);
+            o.flowThreshold = get(moduleConfig, "flow_threshold", o.flowThreshold);
+            o.disparityThreshold = get(moduleConfig, "disparity_threshold", o.disparityThreshold);
+            o.disparityWeight = get(moduleConfig, "disparity_weight", o.disparityWeight);
+            o.iterations = get(moduleConfig, "iterations", o.iterations);
+            o.stride = get(moduleConfig, "stride", o.stride);
+            o.minInliers = get(moduleConfig, "min_inliers", o.minInliers);
+            o.useMotion = get(moduleConfig, "use_motion", o.useMotion);
+            system->addModule<DenseEgoModule>(o);
         } else if (endsWith(moduleType, "_visualization")) {
             std::cerr << "[cartconfig] skipping GUI module type " << moduleType << " (out of scope)\n";
         } else {

@@ -19,6 +19,7 @@
 #include "cartslam_amd/modules/egomotion.hpp"
 #include "cartslam_amd/modules/features.hpp"
 #include "cartslam_amd/modules/matches.hpp"
+#include "cartslam_amd/modules/denseego.hpp"
 #include "cartslam_amd/modules/motionseg.hpp"
 #include "cartslam_amd/timing.hpp"
 #include "cartslam_amd/modules/planefit.hpp"
@@ -108,6 +109,13 @@ int main(int argc, char **argv) {
                     std::ofstream o(dump + "/" + std::to_string(id) + "_" + CARTSLAM_KEY_EGO_MOTION + ".bin", std::ios::binary);
                     o.write(reinterpret_cast<const char *>(&ego->result), sizeof(ego->result));
                     o.write(reinterpret_cast<const char *>(ego->pose), sizeof(ego->pose));
+                }
+                if (run->hasData(CARTSLAM_KEY_DENSE_EGO)) {   // the 136-byte cart_dense_ego_result, then the chained pose as 12 doubles
+                    auto dense = run->getData<cart_dense_ego_result>(CARTSLAM_KEY_DENSE_EGO_RESULT);
+                    auto chained = run->getData<cart::EgoMotion>(CARTSLAM_KEY_DENSE_EGO);
+                    std::ofstream o(dump + "/" + std::to_string(id) + "_" + CARTSLAM_KEY_DENSE_EGO + ".bin", std::ios::binary);
+                    o.write(reinterpret_cast<const char *>(dense.get()), sizeof(*dense));
+                    o.write(reinterpret_cast<const char *>(chained->pose), sizeof(chained->pose));
                 }
                 if (run->hasData(CARTSLAM_KEY_PLANE_MAP)) {   // int64 ox, oz; int32 Nx, Nz; double cell_size; the 16-byte cells; the u8 classes
                     auto pm = run->getData<cart::PlaneMap>(CARTSLAM_KEY_PLANE_MAP);

@@ -55,7 +55,8 @@ PlaneMapModule::PlaneMapModule(const PlaneMapOptions &options)
     this->requiresData.push_back(module_dependency_t(CARTSLAM_KEY_DISPARITY));
     if (options.planesKey.empty()) throw std::invalid_argument("planes_key must name a blackboard image");
     this->requiresData.push_back(module_dependency_t(options.planesKey));
-    if (options.poseFile.empty()) this->requiresData.push_back(module_dependency_t(CARTSLAM_KEY_EGO_MOTION));
+    if (options.poseKey.empty()) throw std::invalid_argument("pose_key must name a blackboard pose");
+    if (options.poseFile.empty()) this->requiresData.push_back(module_dependency_t(options.poseKey));
     this->requiresData.push_back(module_dependency_t(CARTSLAM_KEY_PLANE_MAP, -1));   // one frame at a time, in order
     this->providesData.push_back(CARTSLAM_KEY_PLANE_MAP);
 }
@@ -73,7 +74,7 @@ system_data_t PlaneMapModule::runInternal(System &, SystemRunData &data) {
         throw std::runtime_error("PlaneMapModule: " + options.planesKey + " must be a CV_8UC1 image of the disparity's size");
     double pose[12];
     if (options.poseFile.empty()) {   // a frame whose ego_motion.status is 0 carries the kept pose
-        std::memcpy(pose, data.getData<EgoMotion>(CARTSLAM_KEY_EGO_MOTION)->pose, sizeof(pose));
+        std::memcpy(pose, data.getData<EgoMotion>(options.poseKey)->pose, sizeof(pose));
     } else {
         const size_t line = (size_t)data.id - 1;
         if (data.id < 1 || line >= poses.size() || !poseGiven[line])

@@ -639,6 +639,63 @@ int cart_motion_segment(cart_engine *engine, const cart_ego_camera *camera, cons
                         uint8_t *raw, size_t raw_step, uint8_t *labels, size_t labels_step, const uint8_t *planes, size_t planes_step,
                         uint8_t *planes_static, size_t planes_static_step, void *stream);
 
+/* ---- Dense ego-motion refinement from flow and disparity (spec S26) ----------------------------------------------
+ * An extension: the reference estimates no pose.  Gauss-Newton refinement of a relative pose (cart_ego_result's, p_cur = R p_prev + t)
+ * over every static pixel: the inputs are cart_motion_segment's.  fp64 with + - * / sqrt only, every sum in a fixed two-level order,
+ * no floating-point atomics: restated in tests/np_dense_ego.py.
+ *   Sample grid: pixels (x, y) = (i stride, j stride) inside the image.  A pixel is a candidate (independent of the pose) iff it passes
+ *   gates 1-3 of S25 (giving d_c, xp, yp, d_p) and mask is NULL or mask[y][x] != 1 (MOVING).
+ *   At the pose (R, t): Zp, Xp, Yp and q as S25's gate 4 with rel[4r + c] = R[3r + c], rel[4r + 3] = t[r]; eu, ev, ed as S25.  A
+ *   candidate contributes iff q.z > 0, eu eu + ev ev < flow_threshold^2 and ed ed < disparity_threshold^2.
+ *   Rows: a = fx / q.z, b = -((fx q.x) / (q.z q.z)), c = fy / q.z, d = -((fy q.y) / (q.z q.z)), g = -((fx baseline) / (q.z q.z)),
+ *     Ju = (b q.y, a q.z - b q.x, -(a q.y), a, 0, b), Jv = (d q.y - c q.z, -(d q.x), c q.x, 0, c, d) (S23), Jd = (g q.y, -(g q.x), 0, 0, 0, g);
+ *     H_ij = (Ju_i Ju_j + Jv_i Jv_j) + wd (Jd_i Jd_j) for i <= j, g_i = (Ju_i eu + Jv_i ev) + wd (Jd_i ed),
+ *     e2 = (eu eu + ev ev) + wd (ed ed), wd = disparity_weight: 28 sums and an integer count.
+ *   Order of every sum: for sampled row j, virtual lane l of 256 starts at +0.0 and adds its contributing pixels of sampled columns
+ *   l, l + 256, ... in ascending order, then v[l] += v[l ^ o] for o = 1, 2, 4 .. 128 and lane 0 holds the row's partial; virtual lane l
+ *   then adds the partials of sampled rows l, l + 256, ... (every row, ascending) and the same butterfly follows.
+ *   Iteration: (R, t) = rel0; an evaluation there gives n_initial and rms_initial; up to `iterations` times: evaluate, stop if the count
+ *   is below min_inliers, solve H delta = -g by S23's unpivoted Cholesky (stop at a pivot that is not > 0), update the pose as S23
+ *   does, steps += 1; a last evaluation gives n_inliers and rms = sqrt(sum e2 / n) (0.0 at n = 0).
+ *   Acceptance is the consumer's: take (R, t) iff status == 1, all 12 entries are finite and n_inliers >= n_initial, else keep rel0. */
+typedef struct cart_dense_ego_params {
+    double min_disparity;                     /* pixels, finite, > 0 */
+    double flow_threshold;                    /* pixels, finite, > 0 */
+    double disparity_threshold;               /* pixels, finite, > 0 */
+    double disparity_weight;                  /* finite, >= 0 */
+    int32_t iterations;                       /* 0..16 */
+    int32_t stride;                           /* 1..16 */
+    int32_t min_inliers;                      /* 6..2^30 */
+} cart_dense_ego_params;
+void cart_dense_ego_default_params(cart_dense_ego_params *p); /* extension: 1.0, 2.0, 1.0, 1.0, 4, 1, 1024 (build-owned, untuned) */
+#define CART_DENSE_EGO_MAX_ITERATIONS 16
+typedef struct cart_dense_ego_result {
+    double R[9], t[3];                        /* the pose after `steps` updates; rel0's when status is 0 */
+    double rms_initial, rms;                  /* sqrt(sum e2 / n) at rel0 and at (R, t) */
+    int32_t status;                           /* 1 iff steps > 0 */
+    int32_t n_candidates;                     /* the pose-independent count */
+    int32_t n_initial, n_inliers;             /* contributing pixels at rel0 and at (R, t) */
+    int32_t steps, reserved;
+} cart_dense_ego_result;
+
+typedef struct cart_dense_ego cart_dense_ego;
+/* Extension.  The workspace for frames of up to max_width x max_height (1..16384 each): one row partial per image row and the pose
+ * state; nothing is allocated per call.  The sizes are checked before the engine. */
+int cart_dense_ego_create(cart_engine *engine, int max_width, int max_height, cart_dense_ego **out);
+/* Extension.  Keeps the device it was created on, so it may be destroyed after its engine. */
+void cart_dense_ego_destroy(cart_dense_ego *obj);
+/* Extension.  One frame: rel0 = HOST double [12] as cart_motion_segment's rel (all finite, |R entries| <= 2, |t entries| <= 1e6);
+ * disp_cur / disp_prev = device int16 x16 (2-byte aligned), flow = device int16 x 2 in S10.5 (4-byte aligned), mask = device u8 labels
+ * of cart_motion_segment or NULL, all width x height (1..16384 each and within the object's maxima), steps in bytes and multiples of
+ * the alignment.  result = DEVICE record (8-byte aligned, overlapping no input).  Checked in this order, all before any device call:
+ * params, camera, rel0, sizes, object, then pointers, alignment and steps; a refused call touches no output.  2 (iterations + 1) plain
+ * launches on `stream`, no host synchronisation: the pose stays on the device between them, and after a stop the later launches leave
+ * at once. */
+int cart_dense_ego_refine(cart_dense_ego *obj, const cart_ego_camera *camera, const double *rel0, const cart_dense_ego_params *params,
+                          const int16_t *disp_cur, size_t disp_cur_step, const int16_t *disp_prev, size_t disp_prev_step,
+                          const int16_t *flow, size_t flow_step, const uint8_t *mask, size_t mask_step, int width, int height,
+                          cart_dense_ego_result *result, void *stream);
+
 /* Stand-in for ImageOpticalFlowModule's device work (src/modules/optflow.cpp:96-140: cvtColor x2 +
  * cv::cuda::NvidiaOpticalFlow_2_0::calc(current, previous), NVIDIA fixed-function hardware): dense census block
  * matching (oracle S15).  cur / prev = the reference images of frame id and id-1 (1-channel gray or 3-channel BGR),
