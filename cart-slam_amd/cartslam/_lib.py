@@ -122,6 +122,16 @@ class DenseEgoParams(C.Structure):
                [(n, C.c_int32) for n in ("iterations", "stride", "min_inliers")]
 
 
+class PlaceParams(C.Structure):
+    # mirrors cart_place_params (include/cart_engine.h, spec S27); the defaults are cart_place_default_params'
+    _fields_ = [(n, C.c_int32) for n in ("max_distance", "ratio", "min_score", "max_candidates")] + [("min_gap", C.c_uint64)]
+
+
+class PlaceCandidate(C.Structure):
+    # mirrors cart_place_candidate (include/cart_engine.h, spec S27)
+    _fields_ = [("slot", C.c_int32), ("score", C.c_int32), ("frame_id", C.c_uint64)]
+
+
 class DenseEgoResult(C.Structure):
     # mirrors cart_dense_ego_result (include/cart_engine.h, spec S26)
     _fields_ = [("R", C.c_double * 9), ("t", C.c_double * 3), ("rms_initial", C.c_double), ("rms", C.c_double)] + \
@@ -220,6 +230,13 @@ PROTOTYPES = {
     "cart_dense_ego_destroy": (None, [_vp]),
     "cart_dense_ego_refine": (_i, [_vp, C.POINTER(EgoCamera), C.POINTER(C.c_double), C.POINTER(DenseEgoParams), _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz,
                                    _i, _i, _vp, _vp]),
+    "cart_place_default_params": (None, [C.POINTER(PlaceParams)]),
+    "cart_place_create": (_i, [_vp, _i, _i, C.POINTER(_vp)]),
+    "cart_place_destroy": (None, [_vp]),
+    "cart_place_clear": (_i, [_vp, _vp]),
+    "cart_place_insert": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, C.c_uint64, C.POINTER(C.c_int32), _vp]),
+    "cart_place_query": (_i, [_vp, C.POINTER(PlaceParams), _vp, _sz, _vp, C.c_uint64, _vp, _vp, _vp, _vp]),
+    "cart_place_slot": (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)]),
     "cart_optical_flow": (_i, [_vp, _vp, _sz, _vp, _sz, _i, _i, _i, _vp, _sz, _vp]),
     "cart_flow_default_params": (None, [C.POINTER(FlowParams)]),
     "cart_flow_pyramid_levels": (_i, [_i, _i, _i, C.POINTER(_i), C.POINTER(_i)]),

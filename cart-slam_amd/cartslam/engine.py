@@ -10,7 +10,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import DenseEgoParams, EgoCamera, EgoParams, EngineParams, MatchParams, MotionParams, PlaneMapParams, PlaneParams, SuperpixelParams
+from ._lib import DenseEgoParams, EgoCamera, EgoParams, EngineParams, MatchParams, MotionParams, PlaceParams, PlaneMapParams, PlaneParams, SuperpixelParams
 
 INVALID = -32768  # CARTSLAM_DISPARITY_INVALID, reference include/modules/disparity.hpp:17
 
@@ -1005,6 +1005,107 @@ def motion_segment(engine, camera, rel, disp_cur, disp_prev, flow, params=None, 
         raise EngineError("cart_motion_segment: " + _lib.load().cart_last_error(None).decode())
     out = MotionSegmentation(res, rawl, labels, static)
     return out if raw else MotionSegmentation(*[t.cpu().numpy() if t is not None else None for t in out])
+
+
+PLACE_CANDIDATE_DTYPE = np.dtype([("slot", "<i4"), ("score", "<i4"), ("frame_id", "<u8")])   # cart_place_candidate
+
+
+def place_params(**fields):
+    """cart_place_default_params (spec S27) with the given fields replaced."""
+    p = PlaceParams()
+    _lib.load().cart_place_default_params(C.byref(p))
+    for k, v in fields.items():
+        if k not in dict(PlaceParams._fields_):
+            raise ValueError(f"cart_place_params has no field {k}")
+        setattr(p, k, v)
+    return p
+
+
+class PlaceDB(_DeviceObject):
+    """Place recognition over a device-resident ring of stored frames (cart_place_* in the C ABI, spec S27 in DESIGN.md 7.9): `capacity`
+    slots of up to max_features ORB features each; query() scores a frame's descriptors against every stored frame in two launches."""
+    _name = "place"
+
+    def __init__(self, engine, max_features=_lib.ORB_DEFAULT_FEATURES, capacity=256):
+        self.max_features, self.capacity = int(max_features), int(capacity)
+        super().__init__(engine, self.max_features, self.capacity)
+
+    def _rows(self, desc, count, what, full=False):
+        """-> (descriptor tensor, step, device int32 count): host arrays go up; a device count needs max_features rows.  full: a shorter
+        set is copied into a buffer of max_features rows, the extent cart_place_query's overlap check takes the query set to have."""
+        import torch
+        if not isinstance(desc, torch.Tensor):
+            desc = torch.from_numpy(np.ascontiguousarray(desc, dtype=np.uint8).reshape(-1, _lib.ORB_DESCRIPTOR_BYTES)).cuda()
+        if desc.dtype != torch.uint8 or not desc.is_cuda or desc.dim() != 2 or desc.shape[1] != _lib.ORB_DESCRIPTOR_BYTES or (desc.shape[0] > 1 and desc.stride(1) != 1):
+            raise EngineError(f"{what} must be a uint8 CUDA tensor [n, 32] with unit column stride")
+        rows = int(desc.shape[0])
+        if count is None:
+            count = rows
+        if not isinstance(count, torch.Tensor) and int(count) > rows:
+            raise EngineError("count exceeds the descriptor rows")
+        if rows == 0 or (full and rows < self.max_features):   # an empty tensor has no address: one unread row
+            padded = torch.zeros((self.max_features if full else 1, _lib.ORB_DESCRIPTOR_BYTES), dtype=torch.uint8, device=desc.device)
+            padded[:rows] = desc
+            desc = padded
+        if not isinstance(count, torch.Tensor):
+            count = torch.tensor([int(count)], dtype=torch.int32, device=desc.device)
+        elif count.dtype != torch.int32 or not count.is_cuda or count.numel() != 1:
+            raise EngineError("count must be one int32 on the device")
+        elif rows < self.max_features:
+            raise EngineError("with a device count the tensors must hold max_features rows")
+        return desc, (desc.stride(0) if desc.shape[0] > 1 else _lib.ORB_DESCRIPTOR_BYTES), count
+
+    def insert(self, desc, keypoints, frame_id, landmarks=None, count=None):
+        """Stores a frame: desc uint8 [n, 32] (rows may be pitched), keypoints float32 device [>= n, 7] or a KEYPOINT_DTYPE array, landmarks
+        float64 [>= n, 4] (EgoMotion.triangulate's) or None, count = a device int32, an int or None (= n).  -> the slot taken.  No
+        host synchronisation."""
+        import torch
+        de, step, cnt = self._rows(desc, count, "desc")
+        need = self.max_features if isinstance(count, torch.Tensor) else int(de.shape[0])
+        kp = keypoints
+        if not isinstance(kp, torch.Tensor):
+            kp = torch.from_numpy(np.ascontiguousarray(kp).view(np.float32).reshape(-1, 7)).cuda()
+        if kp.shape[0] == 0:
+            kp = torch.zeros((1, 7), dtype=torch.float32, device=de.device)
+        lm = landmarks
+        if lm is not None and not isinstance(lm, torch.Tensor):
+            lm = torch.from_numpy(np.ascontiguousarray(lm, dtype=np.float64).reshape(-1, 4)).cuda()
+        if lm is not None and lm.shape[0] == 0:
+            lm = torch.zeros((1, 4), dtype=torch.float64, device=de.device)
+        if kp.dtype != torch.float32 or not kp.is_cuda or not kp.is_contiguous() or kp.dim() != 2 or kp.shape[1] != 7 or kp.shape[0] < need:
+            raise EngineError("keypoints must be a contiguous float32 CUDA tensor [>= n, 7] (the cart_keypoint records)")
+        if lm is not None and (lm.dtype != torch.float64 or not lm.is_cuda or not lm.is_contiguous() or lm.dim() != 2 or lm.shape[1] != 4 or lm.shape[0] < need):
+            raise EngineError("landmarks must be a contiguous float64 CUDA tensor [>= n, 4]")
+        slot = C.c_int32(-1)
+        self._check(self._lib.cart_place_insert(self._h, C.c_void_p(de.data_ptr()), step, C.c_void_p(kp.data_ptr()),
+                                                C.c_void_p(lm.data_ptr()) if lm is not None else None, C.c_void_p(cnt.data_ptr()), int(frame_id),
+                                                C.byref(slot), _stream_ptr()), "cart_place_insert")
+        return slot.value
+
+    def query(self, desc, frame_id, params=None, count=None, want_scores=True):
+        """Scores desc (as insert's) of frame frame_id against every slot.  -> (scores int32 [capacity] or None, candidates int64
+        [max_candidates, 2] holding the 16-byte cart_place_candidate records (view them as PLACE_CANDIDATE_DTYPE on the host), n int32
+        [1]), all device tensors: no host synchronisation.  Records from n on are not written."""
+        import torch
+        p = params if params is not None else place_params()
+        de, step, cnt = self._rows(desc, count, "desc", full=True)
+        scores = torch.empty(self.capacity, dtype=torch.int32, device=de.device) if want_scores else None
+        cand = torch.zeros((max(int(p.max_candidates), 1), 2), dtype=torch.int64, device=de.device)
+        n = torch.zeros(1, dtype=torch.int32, device=de.device)
+        self._check(self._lib.cart_place_query(self._h, C.byref(p), C.c_void_p(de.data_ptr()), step, C.c_void_p(cnt.data_ptr()), int(frame_id),
+                                               C.c_void_p(scores.data_ptr()) if scores is not None else None, C.c_void_p(cand.data_ptr()),
+                                               C.c_void_p(n.data_ptr()), _stream_ptr()), "cart_place_query")
+        return scores, cand, n
+
+    def slot(self, k):
+        """-> (desc, keypoints, landmarks or None, count) of slot k as device addresses (ints) into the ring, for cart_matcher_match and
+        cart_ego_estimate; the descriptor step is 32.  Host only."""
+        ptrs = [C.c_void_p() for _ in range(4)]
+        self._check(self._lib.cart_place_slot(self._h, int(k), *[C.byref(q) for q in ptrs]), "cart_place_slot")
+        return tuple(q.value for q in ptrs)
+
+    def clear(self):
+        self._check(self._lib.cart_place_clear(self._h, _stream_ptr()), "cart_place_clear")
 
 
 DENSE_EGO_RESULT_DTYPE = np.dtype([("R", "<f8", 9), ("t", "<f8", 3), ("rms_initial", "<f8"), ("rms", "<f8"), ("status", "<i4"), ("n_candidates", "<i4"),

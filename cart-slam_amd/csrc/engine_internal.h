@@ -372,6 +372,48 @@ struct DenseEgoArgs {
     cart_dense_ego_result *result;
 };
 void launch_dense_ego(const DenseEgoArgs &a, hipStream_t s);   // the 2 (iterations + 1) launches of one call
+// ---- place recognition over an ORB keyframe database (place_kernels.hip) ----
+#ifndef CART_PLACE_QUERIES_PER_LANE
+#define CART_PLACE_QUERIES_PER_LANE 1   // the A/B of DESIGN.md 7.9 builds the library a second time with 2
+#endif
+constexpr int kPlaceLaneQueries = CART_PLACE_QUERIES_PER_LANE;
+constexpr int kPlaceRows = kMatchRows * kPlaceLaneQueries;   // queries of a place_score workgroup = rows of the partial table's blocks
+constexpr int kPlaceMaxSlots = 1024;       // capacity limit = threads of place_select
+constexpr int kPlaceMaxCandidates = 16;
+constexpr int kPlaceOccupied = 1, kPlaceHasLandmarks = 2;   // PlaceSlotHeader::flags
+struct PlaceSlotHeader {                   // 16 bytes per slot, device memory: what a query needs to know about a slot
+    int32_t count, flags;
+    uint64_t frame_id;
+};
+struct PlaceStore {                        // the ring: slot k's rows start at row k * max_features of each array
+    uint8_t *desc;                         // [capacity][max_features][32]
+    cart_keypoint *kp;                     // [capacity][max_features]
+    double *landmarks;                     // [capacity][max_features][4]
+    PlaceSlotHeader *hdr;                  // [capacity]
+    int max_features, capacity;
+};
+struct PlaceInsertArgs {
+    PlaceStore db;
+    const uint8_t *desc; size_t desc_step;
+    const cart_keypoint *kp;
+    const double *landmarks;               // may be NULL
+    const int32_t *count;
+    uint64_t frame_id;
+    int slot;
+};
+struct PlaceQueryArgs {
+    PlaceStore db;
+    cart_place_params p;
+    const uint8_t *q_desc; size_t q_step;
+    const int32_t *q_count;
+    uint64_t frame_id;
+    int32_t *partial;                      // [query blocks][capacity] votes of one workgroup
+    int32_t *scores;                       // may be NULL
+    cart_place_candidate *candidates;
+    int32_t *n_candidates;
+};
+void launch_place_insert(const PlaceInsertArgs &a, hipStream_t s);
+void launch_place_query(const PlaceQueryArgs &a, hipStream_t s);   // the two launches of one query
 void launch_narrow_copy(const void *src, void *dst, size_t bytes, int blocks, hipStream_t s);
 int kernel_count();
 

@@ -6,33 +6,15 @@
 //   match_merge  folds the partials of a row in chunk order into the forward records / the backward best query.
 //   match_select acceptance rule and the ordered compaction, one workgroup of 1024 threads.
 // The set sizes are read on the device; the grids are sized by the matcher's capacity and surplus workgroups leave at once.
-#include "engine_internal.h"
+#include "match_device.h"
 
 namespace cart_amd {
 
 namespace {
-constexpr int kNoKey = 0x7fffffff;   // no admissible column yet: distance field 0x7fff
-constexpr int kNoDist = 0x7fff;
-
-__device__ __forceinline__ int clamp_count(const int32_t *p, int cap) { return min(max(*p, 0), cap); }
-
 struct MatchSide {
     const uint8_t *desc; size_t step;
     const cart_keypoint *kp;
 };
-
-// 32 descriptor bytes as 8 little-endian dwords (dword loads when pointer and step allow them)
-__device__ __forceinline__ void load_desc(const uint8_t *row, bool aligned, unsigned v[8]) {
-    if (aligned) {
-        const unsigned *p = reinterpret_cast<const unsigned *>(row);
-#pragma unroll
-        for (int k = 0; k < 8; ++k) v[k] = p[k];
-    } else {
-#pragma unroll
-        for (int k = 0; k < 8; ++k)
-            v[k] = (unsigned)row[4 * k] | ((unsigned)row[4 * k + 1] << 8) | ((unsigned)row[4 * k + 2] << 16) | ((unsigned)row[4 * k + 3] << 24);
-    }
-}
 
 // kSwap = false: rows are the queries (dx = row - column); true: rows are the train set (dx = column - row)
 template <bool kSwap>
@@ -46,10 +28,10 @@ __device__ __forceinline__ void match_rows(const MatchArgs &a, const MatchSide &
     float qx = 0.f, qy = 0.f;
     int qo = 0;
     if (live) {
-        load_desc(R.desc + (size_t)row * R.step, ((reinterpret_cast<uintptr_t>(R.desc) | R.step) & 3) == 0, q);
+        load_desc(R.desc + (size_t)row * R.step, desc_aligned(R.desc, R.step), q);
         if (gate) { qx = R.kp[row].x; qy = R.kp[row].y; qo = R.kp[row].octave; }
     }
-    const bool c_aligned = ((reinterpret_cast<uintptr_t>(Cs.desc) | Cs.step) & 3) == 0;
+    const bool c_aligned = desc_aligned(Cs.desc, Cs.step);
     const int col_end = min(ncols, (chunk + 1) * a.chunk_len);
     int best = kNoKey, second = kNoDist;
     for (int c0 = chunk * a.chunk_len; c0 < col_end; c0 += kMatchTile) {
@@ -65,8 +47,7 @@ __device__ __forceinline__ void match_rows(const MatchArgs &a, const MatchSide &
         __syncthreads();
         for (int t = 0; t < nt; ++t) {
             const uint4 lo = s_desc[t][0], hi = s_desc[t][1];
-            int d = __popc(q[0] ^ lo.x) + __popc(q[1] ^ lo.y) + __popc(q[2] ^ lo.z) + __popc(q[3] ^ lo.w) +
-                    __popc(q[4] ^ hi.x) + __popc(q[5] ^ hi.y) + __popc(q[6] ^ hi.z) + __popc(q[7] ^ hi.w);
+            int d = hamming256(q, lo, hi);
             if (gate) {   // uniform
                 const float4 g = s_gate[t];
                 const float dx = kSwap ? g.x - qx : qx - g.x, dy = kSwap ? g.y - qy : qy - g.y;   // one float32 subtraction each (S22)
@@ -75,9 +56,7 @@ __device__ __forceinline__ void match_rows(const MatchArgs &a, const MatchSide &
                                 (a.p.max_octave_diff < 0 || od <= a.p.max_octave_diff);
                 d = ok ? d : kNoDist;
             }
-            const int key = (d << 16) | (c0 + t);
-            second = min(second, max(best, key) >> 16);   // the loser of (best, key) is a candidate for the second distance
-            best = min(best, key);
+            match_update(best, second, (d << 16) | (c0 + t));
         }
     }
     if (!live) return;

@@ -17,6 +17,7 @@
 #include "cartslam_amd/modules/features.hpp"
 #include "cartslam_amd/modules/matches.hpp"
 #include "cartslam_amd/modules/denseego.hpp"
+#include "cartslam_amd/modules/loopclosure.hpp"
 #include "cartslam_amd/modules/motionseg.hpp"
 #include "cartslam_amd/modules/planefit.hpp"
 #include "cartslam_amd/modules/planemap.hpp"
@@ -206,6 +207,30 @@ void applyModuleConfig(const Value &modulesConfig, std::shared_ptr<System> syste
             o.minInliers = get(moduleConfig, "min_inliers", o.minInliers);
             o.useMotion = get(moduleConfig, "use_motion", o.useMotion);
             system->addModule<DenseEgoModule>(o);
+        } else if (moduleType == "loop_closure") {  // extension (spec S27): keyframes recognised in a device-resident ring and verified by a relative pose
+            LoopClosureOptions o;
+            const CameraIntrinsics K = dataSource->getCameraIntrinsics();   // as for ego_motion
+            o.fx = get(moduleConfig, "fx", (double)K.Q[11]);
+            o.fy = get(moduleConfig, "fy", (double)K.Q[11]);
+            o.cx = get(moduleConfig, "cx", -(double)K.Q[3]);
+            o.cy = get(moduleConfig, "cy", -(double)K.Q[7]);
+            o.baseline = get(moduleConfig, "baseline", K.Q[14] != 0 ? std::fabs(1.0 / (double)K.Q[14]) : 0.0);
+            o.maxDistance = get(moduleConfig, "max_distance", o.maxDistance);
+            o.ratio = get(moduleConfig, "ratio", o.ratio);
+            o.minScore = get(moduleConfig, "min_score", o.minScore);
+            o.maxCandidates = get(moduleConfig, "max_candidates", o.maxCandidates);
+            o.minGap = (uint64_t)get(moduleConfig, "min_gap", (int)o.minGap);
+            o.capacity = get(moduleConfig, "capacity", o.capacity);
+            o.keyframeInterval = get(moduleConfig, "keyframe_interval", o.keyframeInterval);
+            o.verify = get(moduleConfig, "verify", o.verify);
+            o.minInliers = get(moduleConfig, "min_inliers", o.minInliers);
+            o.seed = (uint64_t)get(moduleConfig, "seed", 0);
+            o.minDisparity = get(moduleConfig, "min_disparity", o.minDisparity);
+            o.inlierThreshold = get(moduleConfig, "inlier_threshold", o.inlierThreshold);
+            o.hypotheses = get(moduleConfig, "hypotheses", o.hypotheses);
+            o.refineIterations = get(moduleConfig, "refine_iterations", o.refineIterations);
+            o.poseKey = get<std::string>(moduleConfig, "pose_key", o.poseKey);   // "dense_ego": keyframes are stored with the refined pose
+            system->addModule<LoopClosureModule>(o);
         } else if (endsWith(moduleType, "_visualization")) {
             std::cerr << "[cartconfig] skipping GUI module type " << moduleType << " (out of scope)\n";
         } else {

@@ -20,6 +20,7 @@
 #include "cartslam_amd/modules/features.hpp"
 #include "cartslam_amd/modules/matches.hpp"
 #include "cartslam_amd/modules/denseego.hpp"
+#include "cartslam_amd/modules/loopclosure.hpp"
 #include "cartslam_amd/modules/motionseg.hpp"
 #include "cartslam_amd/timing.hpp"
 #include "cartslam_amd/modules/planefit.hpp"
@@ -116,6 +117,11 @@ int main(int argc, char **argv) {
                     std::ofstream o(dump + "/" + std::to_string(id) + "_" + CARTSLAM_KEY_DENSE_EGO + ".bin", std::ios::binary);
                     o.write(reinterpret_cast<const char *>(dense.get()), sizeof(*dense));
                     o.write(reinterpret_cast<const char *>(chained->pose), sizeof(chained->pose));
+                }
+                if (run->hasData(CARTSLAM_KEY_LOOP_CLOSURE)) {   // the 336-byte LoopClosure record
+                    auto loop = run->getData<cart::LoopClosure>(CARTSLAM_KEY_LOOP_CLOSURE);
+                    std::ofstream o(dump + "/" + std::to_string(id) + "_" + CARTSLAM_KEY_LOOP_CLOSURE + ".bin", std::ios::binary);
+                    o.write(reinterpret_cast<const char *>(loop.get()), sizeof(*loop));
                 }
                 if (run->hasData(CARTSLAM_KEY_PLANE_MAP)) {   // int64 ox, oz; int32 Nx, Nz; double cell_size; the 16-byte cells; the u8 classes
                     auto pm = run->getData<cart::PlaneMap>(CARTSLAM_KEY_PLANE_MAP);

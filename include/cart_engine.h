@@ -696,6 +696,62 @@ int cart_dense_ego_refine(cart_dense_ego *obj, const cart_ego_camera *camera, co
                           const int16_t *flow, size_t flow_step, const uint8_t *mask, size_t mask_step, int width, int height,
                           cart_dense_ego_result *result, void *stream);
 
+/* ---- Place recognition over an ORB keyframe database (spec S27) --------------------------------------------------
+ * An extension: the reference has no such stage.  A device-resident ring of stored frames (descriptors, keypoints, optional landmarks)
+ * and one call that scores the current frame's descriptors against every stored frame.  Integer and deterministic, restated in
+ * tests/np_place.py.
+ *   Ring: `capacity` slots of up to max_features features; insert number m (from 0 since create / clear) replaces slot m mod capacity.
+ *   Eligible: slot k is occupied and frame_id_k + min_gap <= frame_id of the query (uint64; a sum that wraps is not eligible).
+ *   Vote: for query i < nq, (j1, d1, d2) = S22's forward record over all j < n_k without a gate; i votes for k iff j1 >= 0, d1 <=
+ *   max_distance and (ratio == 0 or d2 < 0 or 100 d1 < ratio d2).  No cross-check.  score_k = the number of votes (0 for an empty slot).
+ *   scores[k] = score_k for an eligible slot, -1 for every other slot below capacity.
+ *   Candidates: the eligible slots with score >= min_score under (score descending, frame id ascending, slot ascending), the first
+ *   max_candidates of them. */
+typedef struct cart_place_params {
+    int32_t max_distance;                     /* 0..256 */
+    int32_t ratio;                            /* 0..100, 0 = off */
+    int32_t min_score;                        /* 0..65536 */
+    int32_t max_candidates;                   /* 1..16 */
+    uint64_t min_gap;                         /* frames between a stored frame and a query that may find it */
+} cart_place_params;
+void cart_place_default_params(cart_place_params *p); /* extension: 64, 80, 30, 4, 50 (build-owned, untuned) */
+#define CART_PLACE_MAX_CAPACITY 1024
+#define CART_PLACE_MAX_CANDIDATES 16
+typedef struct cart_place_candidate {
+    int32_t slot, score;
+    uint64_t frame_id;
+} cart_place_candidate;
+
+typedef struct cart_place_db cart_place_db;
+/* Extension.  The ring and the query's workspace for max_features in 1..65536 and capacity in 1..1024, all allocated here: 92 bytes
+ * (32 descriptor + 28 keypoint + 32 landmark) x max_features x capacity, 16 bytes per slot and a partial table of 4 bytes x capacity x
+ * ceil(max_features / 128).  The sizes are checked before the engine. */
+int cart_place_create(cart_engine *engine, int max_features, int capacity, cart_place_db **out);
+/* Extension.  Keeps the device it was created on, so it may be destroyed after its engine. */
+void cart_place_destroy(cart_place_db *db);
+/* Extension.  Empties every slot on `stream`; the next insert is number 0. */
+int cart_place_clear(cart_place_db *db, void *stream);
+/* Extension.  Stores a frame: desc = device rows of 32 bytes desc_step (>= 32) apart, kp = device cart_keypoint records (4-byte
+ * aligned), landmarks = device double [..][4] as cart_ego_triangulate writes them (8-byte aligned) or NULL, count = DEVICE int32,
+ * clamped to [0, max_features] on the device; rows at or beyond it are never read.  slot_out (HOST, may be NULL) = the slot taken.
+ * One launch on `stream`, no host synchronisation; the slot's header (count, frame id) is written by that launch, so a query queued
+ * behind it sees the frame and a query queued before it does not. */
+int cart_place_insert(cart_place_db *db, const uint8_t *desc, size_t desc_step, const cart_keypoint *kp, const double *landmarks,
+                      const int32_t *count, uint64_t frame_id, int32_t *slot_out, void *stream);
+/* Extension.  Scores the query set (q_desc rows q_step >= 32 bytes apart, q_count = DEVICE int32 clamped to [0, max_features]) of
+ * frame frame_id against every slot.  Device outputs: scores = int32 [capacity] (may be NULL), candidates = [params->max_candidates]
+ * records (8-byte aligned) of which the first *n_candidates are written, n_candidates = their number.  No output may overlap another
+ * or the query descriptors, whose extent this check takes as max_features rows whatever the count.  Checked in this order, all before any device call: params, object, then pointers, alignment and steps; a
+ * refused call touches no output.  Two launches on `stream` whatever the capacity, no host synchronisation. */
+int cart_place_query(cart_place_db *db, const cart_place_params *params, const uint8_t *q_desc, size_t q_step, const int32_t *q_count,
+                     uint64_t frame_id, int32_t *scores, cart_place_candidate *candidates, int32_t *n_candidates, void *stream);
+/* Extension.  HOST getter, no device work: device pointers into slot `slot` -- its descriptor rows (32 bytes apart), keypoints,
+ * landmarks (NULL if the insert gave none) and count -- for cart_matcher_match and cart_ego_estimate; each of the four may be NULL (not
+ * asked for).  They stay valid until the object is destroyed and describe the stored frame until the slot is overwritten or
+ * cleared.  Fails for a slot that no insert has taken since create / clear. */
+int cart_place_slot(cart_place_db *db, int slot, const uint8_t **desc, const cart_keypoint **kp, const double **landmarks,
+                    const int32_t **count);
+
 /* Stand-in for ImageOpticalFlowModule's device work (src/modules/optflow.cpp:96-140: cvtColor x2 +
  * cv::cuda::NvidiaOpticalFlow_2_0::calc(current, previous), NVIDIA fixed-function hardware): dense census block
  * matching (oracle S15).  cur / prev = the reference images of frame id and id-1 (1-channel gray or 3-channel BGR),
