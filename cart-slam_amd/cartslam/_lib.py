@@ -141,6 +141,14 @@ class DenseEgoResult(C.Structure):
 DENSE_EGO_MAX_ITERATIONS = 16   # CART_DENSE_EGO_MAX_ITERATIONS
 
 
+class FusionParams(C.Structure):
+    # mirrors cart_fusion_params (include/cart_engine.h, spec S28); the defaults are cart_fusion_default_params' (build-owned, untuned)
+    _fields_ = [(n, C.c_double) for n in ("min_disparity", "agree_threshold", "splat_radius")] + [(n, C.c_int32) for n in ("max_weight", "min_age")]
+
+
+FUSION_NONE, FUSION_MEASURED, FUSION_AGREED, FUSION_REPLACED, FUSION_PREDICTED = range(5)   # CART_FUSION_*
+
+
 PLACE_MODES = {0: "unknown", 1: "fast", 2: "mixed", 3: "uniform"}                                       # CART_PLACE_MODE_*
 PLACE_STOPS = {0: "nothing to do", 1: "fast set found", 2: "uniform", 3: "tries", 4: "time", 5: "memory"}   # CART_PLACE_STOP_*
 
@@ -237,6 +245,11 @@ PROTOTYPES = {
     "cart_place_insert": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, C.c_uint64, C.POINTER(C.c_int32), _vp]),
     "cart_place_query": (_i, [_vp, C.POINTER(PlaceParams), _vp, _sz, _vp, C.c_uint64, _vp, _vp, _vp, _vp]),
     "cart_place_slot": (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)]),
+    "cart_fusion_default_params": (None, [C.POINTER(FusionParams)]),
+    "cart_fusion_create": (_i, [_vp, _i, _i, C.POINTER(_vp)]),
+    "cart_fusion_destroy": (None, [_vp]),
+    "cart_fusion_update": (_i, [_vp, C.POINTER(EgoCamera), C.POINTER(C.c_double), C.POINTER(FusionParams), _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz,
+                                _i, _i, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp]),
     "cart_optical_flow": (_i, [_vp, _vp, _sz, _vp, _sz, _i, _i, _i, _vp, _sz, _vp]),
     "cart_flow_default_params": (None, [C.POINTER(FlowParams)]),
     "cart_flow_pyramid_levels": (_i, [_i, _i, _i, C.POINTER(_i), C.POINTER(_i)]),

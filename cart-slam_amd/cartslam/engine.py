@@ -10,7 +10,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import DenseEgoParams, EgoCamera, EgoParams, EngineParams, MatchParams, MotionParams, PlaceParams, PlaneMapParams, PlaneParams, SuperpixelParams
+from ._lib import DenseEgoParams, EgoCamera, EgoParams, EngineParams, FusionParams, MatchParams, MotionParams, PlaceParams, PlaneMapParams, PlaneParams, SuperpixelParams
 
 INVALID = -32768  # CARTSLAM_DISPARITY_INVALID, reference include/modules/disparity.hpp:17
 
@@ -1174,6 +1174,81 @@ class DenseEgo(_DeviceObject):
         if stream is not None:
             stream.synchronize()
         return res.cpu().numpy().view(DENSE_EGO_RESULT_DTYPE).reshape(-1)
+
+
+def fusion_params(**fields):
+    """cart_fusion_default_params (spec S28; the defaults are build-owned and untuned) with the given fields replaced."""
+    p = FusionParams()
+    _lib.load().cart_fusion_default_params(C.byref(p))
+    for k, v in fields.items():
+        if k not in dict(FusionParams._fields_):
+            raise ValueError(f"cart_fusion_params has no field {k}")
+        setattr(p, k, v)
+    return p
+
+
+class DisparityFusion(_DeviceObject):
+    """Temporal disparity fusion through ego-motion (cart_fusion_* in the C ABI, spec S28 in DESIGN.md 7.10): the previous call's fused
+    disparity, forward-projected through the relative pose into a z-buffer, fused with this frame's disparity, for frames of up to
+    max_width x max_height.  A context manager; close() destroys the device object."""
+    _name = "fusion"
+
+    def __init__(self, engine, max_width, max_height):
+        self.max_width, self.max_height = int(max_width), int(max_height)
+        super().__init__(engine, self.max_width, self.max_height)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def update(self, camera, rel, disp_cur, prev=None, mask_prev=None, mask_cur=None, params=None, source=True, raw=False, stream=None):
+        """camera = EgoCamera or (fx, fy, cx, cy, baseline); rel = 12 numbers, the 3 x 4 (R | t) with p_cur = R p_prev + t (host; None is
+        allowed without prev); disp_cur int16 [h, w] (x16); prev = (fused, age) of the previous call or None (no previous frame);
+        mask_prev / mask_cur uint8 [h, w] (motion_segment's labels of the previous / this frame) or None.  Device tensors are taken as they
+        are (rows may be pitched), host arrays go up.  stream = a torch stream (default: the current one).
+        -> (fused int16 [h, w], age uint8 [h, w], source uint8 [h, w] or None when source is false, counts int32 [5]) as numpy arrays;
+        raw=True returns the device tensors with no host round trip."""
+        import torch
+        cam = camera if isinstance(camera, EgoCamera) else EgoCamera(*[float(v) for v in camera])
+        p = params if params is not None else fusion_params()
+        pd, pa = prev if prev is not None else (None, None)
+
+        def dev(a, dtype):
+            if a is None or isinstance(a, torch.Tensor):
+                return a
+            return torch.as_tensor(np.ascontiguousarray(a), dtype=dtype).cuda()
+        with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):   # uploads and allocations on the call's stream
+            dc, pd, pa, mp, mc = dev(disp_cur, torch.int16), dev(pd, torch.int16), dev(pa, torch.uint8), dev(mask_prev, torch.uint8), dev(mask_cur, torch.uint8)
+            if not isinstance(dc, torch.Tensor) or dc.dim() != 2:
+                raise EngineError("disp_cur must be an int16 [h, w] image")
+            h, w = int(dc.shape[0]), int(dc.shape[1])
+            fused = torch.empty((h, w), dtype=torch.int16, device=dc.device)
+            age = torch.empty((h, w), dtype=torch.uint8, device=dc.device)
+            src = torch.empty((h, w), dtype=torch.uint8, device=dc.device) if source else None
+            counts = torch.empty(5, dtype=torch.int32, device=dc.device)
+        if (pd is None) != (pa is None):
+            raise EngineError("prev must be the pair (fused, age) of the previous call")
+        for t, dtype, what in ((dc, torch.int16, "disp_cur"), (pd, torch.int16, "prev[0]"), (pa, torch.uint8, "prev[1]"), (mp, torch.uint8, "mask_prev"), (mc, torch.uint8, "mask_cur")):
+            if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != dtype or t.dim() != 2 or tuple(t.shape) != (h, w)):
+                raise EngineError(f"{what} must be a device tensor of {dtype} and of the frame's size")
+        args = []
+        for t in (dc, pd, pa, mp, mc):
+            args += list(_geom(t, 1)[1:3]) if t is not None else [None, 0]
+        args += [w, h]
+        for t in (fused, age, src):
+            args += list(_geom(t, 1)[1:3]) if t is not None else [None, 0]
+        host_rel = (C.c_double * 12)(*[float(v) for v in np.asarray(rel, np.float64).reshape(-1)]) if rel is not None else None
+        sp = C.c_void_p(stream.cuda_stream) if stream is not None else _stream_ptr()
+        self._check(self._lib.cart_fusion_update(self._h, C.byref(cam), host_rel, C.byref(p), *args, C.c_void_p(counts.data_ptr()), sp), "cart_fusion_update")
+        out = (fused, age, src, counts)
+        if raw:
+            return out
+        if stream is not None:
+            stream.synchronize()
+        return tuple(t.cpu().numpy() if t is not None else None for t in out)
 
 
 def plane_cluster(planes, offsets, neighbours):

@@ -414,6 +414,32 @@ struct PlaceQueryArgs {
 };
 void launch_place_insert(const PlaceInsertArgs &a, hipStream_t s);
 void launch_place_query(const PlaceQueryArgs &a, hipStream_t s);   // the two launches of one query
+// ---- temporal disparity fusion through ego-motion (fusion_kernels.hip) ----
+#ifndef CART_FUSION_MERGE
+#define CART_FUSION_MERGE 0           // the A/B of DESIGN.md 7.10 builds the library a second time with 1 (neighbouring lanes merge equal targets): no faster
+#endif
+constexpr int kFusionStrip = 2;       // image rows one lane of the splat kernel handles
+constexpr int kFusionRows = 8;        // image rows one lane of the fuse kernel handles
+constexpr int kFusionCounters = 6;    // int32 words of the object's counter block: the five source classes, then the workgroup ticket (read as three uint64)
+struct FusionArgs {
+    cart_ego_camera cam;
+    cart_fusion_params p;
+    double rel[12];
+    const int16_t *disp_cur; size_t disp_cur_step;
+    const int16_t *prev_disp; size_t prev_disp_step;   // NULL with prev_age: no previous frame, no splat launch
+    const uint8_t *prev_age; size_t prev_age_step;
+    const uint8_t *mask_prev; size_t mask_prev_step;   // may be NULL
+    const uint8_t *mask_cur; size_t mask_cur_step;     // may be NULL
+    int16_t *fused; size_t fused_step;
+    uint8_t *age; size_t age_step;
+    uint8_t *source; size_t source_step;               // may be NULL
+    int32_t *counts;                                   // may be NULL
+    uint32_t *zbuf;                                    // the object's z-buffer, rows of w keys; all zero between calls
+    int32_t *counters;                                 // the object's [kFusionCounters]; all zero between calls
+    int w, h;
+};
+void launch_fusion_splat(const FusionArgs &a, hipStream_t s);
+void launch_fusion_fuse(const FusionArgs &a, hipStream_t s);
 void launch_narrow_copy(const void *src, void *dst, size_t bytes, int blocks, hipStream_t s);
 int kernel_count();
 

@@ -29,6 +29,7 @@ struct PlaneMapOptions {
     double cellSize = 0.25, minDisparity = 1.0, maxDepth = 20.0, maxLateral = 10.0, heightQuantum = 0.05;   // cart_plane_map_default_params
     int minVotes = 3, obstaclePercent = 50;
     std::string planesKey = "planes";   // the blackboard image the map votes with; "planes_static" (motion_seg) maps the static world only
+    std::string disparityKey = "disparity";   // the blackboard CV_16SC1 image the map votes with; "disparity_fused" = temporal_fusion's
     std::string poseKey = "ego_motion";   // the blackboard EgoMotion whose accumulated pose the map takes; "dense_ego" = the refined trajectory
     std::string poseFile;   // KITTI poses/NN.txt: 12 numbers per line, line id - 1 belongs to frame id; empty = the "ego_motion" module's pose
 };

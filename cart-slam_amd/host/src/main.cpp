@@ -20,6 +20,7 @@
 #include "cartslam_amd/modules/features.hpp"
 #include "cartslam_amd/modules/matches.hpp"
 #include "cartslam_amd/modules/denseego.hpp"
+#include "cartslam_amd/modules/fusion.hpp"
 #include "cartslam_amd/modules/loopclosure.hpp"
 #include "cartslam_amd/modules/motionseg.hpp"
 #include "cartslam_amd/timing.hpp"
@@ -144,6 +145,18 @@ int main(int argc, char **argv) {
                         const auto bytes = run->getData<cart::image_t>(k)->downloadTight();
                         o.write(reinterpret_cast<const char *>(bytes.data()), (std::streamsize)bytes.size());
                     }
+                }
+                if (run->hasData(CARTSLAM_KEY_DISPARITY_FUSED)) {   // int32 width, height; fused (int16), age, source (u8); the five int32 counts
+                    auto fused = run->getData<cart::image_t>(CARTSLAM_KEY_DISPARITY_FUSED);
+                    std::ofstream o(dump + "/" + std::to_string(id) + "_" + CARTSLAM_KEY_DISPARITY_FUSED + ".bin", std::ios::binary);
+                    const int32_t shape[2] = {fused->cols, fused->rows};
+                    o.write(reinterpret_cast<const char *>(shape), sizeof(shape));
+                    for (const char *k : {CARTSLAM_KEY_DISPARITY_FUSED, CARTSLAM_KEY_DISPARITY_AGE, CARTSLAM_KEY_DISPARITY_SOURCE}) {
+                        const auto bytes = run->getData<cart::image_t>(k)->downloadTight();
+                        o.write(reinterpret_cast<const char *>(bytes.data()), (std::streamsize)bytes.size());
+                    }
+                    auto counts = run->getData<cart::FusionCounts>(CARTSLAM_KEY_DISPARITY_FUSION_COUNTS);
+                    o.write(reinterpret_cast<const char *>(counts->pixels), sizeof(counts->pixels));
                 }
                 if (run->hasData(CARTSLAM_KEY_PLANES_EQ_LABEL_PLANES)) {   // f64 [max_label + 1][4]
                     auto lp = run->getData<std::vector<cart::Vec4d>>(CARTSLAM_KEY_PLANES_EQ_LABEL_PLANES);

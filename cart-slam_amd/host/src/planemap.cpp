@@ -52,7 +52,8 @@ PlaneMapModule::PlaneMapModule(const PlaneMapOptions &options)
             poseGiven.push_back(n == 12);
         }
     }
-    this->requiresData.push_back(module_dependency_t(CARTSLAM_KEY_DISPARITY));
+    if (options.disparityKey.empty()) throw std::invalid_argument("disparity_key must name a blackboard image");
+    this->requiresData.push_back(module_dependency_t(options.disparityKey));
     if (options.planesKey.empty()) throw std::invalid_argument("planes_key must name a blackboard image");
     this->requiresData.push_back(module_dependency_t(options.planesKey));
     if (options.poseKey.empty()) throw std::invalid_argument("pose_key must name a blackboard pose");
@@ -67,9 +68,9 @@ PlaneMapModule::~PlaneMapModule() {
 }
 
 system_data_t PlaneMapModule::runInternal(System &, SystemRunData &data) {
-    auto disparity = data.getData<image_t>(CARTSLAM_KEY_DISPARITY);
+    auto disparity = data.getData<image_t>(options.disparityKey);
     auto planes = data.getData<image_t>(options.planesKey);
-    if (disparity->empty() || disparity->type() != CV_16SC1) throw std::runtime_error("Disparity must be of type CV_16SC1");
+    if (!disparity || disparity->empty() || disparity->type() != CV_16SC1) throw std::runtime_error("Disparity must be of type CV_16SC1");
     if (!planes || planes->empty() || planes->type() != CV_8UC1 || planes->rows != disparity->rows || planes->cols != disparity->cols)
         throw std::runtime_error("PlaneMapModule: " + options.planesKey + " must be a CV_8UC1 image of the disparity's size");
     double pose[12];

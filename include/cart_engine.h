@@ -752,6 +752,63 @@ int cart_place_query(cart_place_db *db, const cart_place_params *params, const u
 int cart_place_slot(cart_place_db *db, int slot, const uint8_t **desc, const cart_keypoint **kp, const double **landmarks,
                     const int32_t **count);
 
+/* ---- Temporal disparity fusion through ego-motion (spec S28) ------------------------------------------------------
+ * An extension: the reference has no such stage.  The previous call's fused disparity is forward-projected through the relative pose
+ * into a z-buffer of this frame and fused with this frame's disparity; an age channel counts how long a pixel's depth has been
+ * confirmed.  No optical flow.  fp64 with + - * / floor only (ceil(a) = -floor(-a)), every sum in the written order, integers after
+ * the projection, the only atomics are integer maxima and counter additions: restated in tests/np_fusion.py.
+ *   Source: previous pixel (xp, yp) with a_p = prev_age >= 1, s_p = prev_disp != -32768, d_p = s_p / 16.0 >= min_disparity and
+ *   mask_prev absent or != 1.  Zp, Xp, Yp and q as S25's gate 4, q.z > 0; u = (fx q.x) / q.z + cx, v = (fy q.y) / q.z + cy,
+ *   sw = floor(((fx baseline) / q.z) 16.0 + 0.5), kept iff 1 <= sw <= 32767 (as doubles; a NaN drops the source).
+ *   Targets: columns x0 = ceil(u - r) and x1 = floor(u + r) (once when they are equal, none when x0 > x1), rows y0, y1 from v likewise,
+ *   r = splat_radius; each is tested against the image as a double before it is converted.  To every target (x, y) inside the image:
+ *     key = ((sw >> 4) << 16) | (c << 12) | ((sw & 15) << 8) | a_p,  c = 15 - min(15, floor(16 max(|x - u|, |y - v|)))
+ *   and the z-buffer (uint32 per pixel, 0 = empty) keeps the maximum key: the whole-pixel disparity decides occlusion, then the
+ *   closeness to the pixel centre, then the fraction, then the age.
+ *   Fusion at (x, y): P = the z-buffer key, 0 where mask_cur == 1; s_w = ((P >> 16) << 4) | ((P >> 8) & 15), a_w = P & 255; the current
+ *   pixel is valid iff s_c = disp_cur != -32768 and s_c / 16.0 >= min_disparity.
+ *     valid, P == 0                                   -> fused s_c, age 1, source 1 (MEASURED)
+ *     valid, e = (double)(s_c - s_w) / 16.0, e e <= agree_threshold^2
+ *                                                     -> fused (w s_w + s_c + (w + 1) / 2) / (w + 1) in integer division with
+ *                                                        w = min(a_w, max_weight), age min(a_w + 1, 255), source 2 (AGREED)
+ *     valid, otherwise                                -> fused s_c, age 1, source 3 (REPLACED)
+ *     invalid, P != 0, a_w >= min_age                 -> fused s_w, age a_w - 1, source 4 (PREDICTED)
+ *     else                                            -> fused s_c unchanged, age 0, source 0 (NONE) */
+typedef struct cart_fusion_params {
+    double min_disparity;                     /* pixels, finite, > 0 */
+    double agree_threshold;                   /* pixels, finite, > 0 */
+    double splat_radius;                      /* pixels, finite, 0.5 <= r < 1 */
+    int32_t max_weight;                       /* 1..255 */
+    int32_t min_age;                          /* 1..255 */
+} cart_fusion_params;
+void cart_fusion_default_params(cart_fusion_params *p); /* extension: 1.0, 1.0, 0.75, 4, 2 (build-owned, untuned) */
+#define CART_FUSION_NONE 0
+#define CART_FUSION_MEASURED 1
+#define CART_FUSION_AGREED 2
+#define CART_FUSION_REPLACED 3
+#define CART_FUSION_PREDICTED 4
+
+typedef struct cart_fusion cart_fusion;
+/* Extension.  The z-buffer (4 bytes per pixel) and the counters for frames of up to max_width x max_height (1..16384 each), zeroed
+ * here once: every call leaves them all zero again.  The sizes are checked before the engine. */
+int cart_fusion_create(cart_engine *engine, int max_width, int max_height, cart_fusion **out);
+/* Extension.  Keeps the device it was created on, so it may be destroyed after its engine. */
+void cart_fusion_destroy(cart_fusion *obj);
+/* Extension.  One frame, width x height (1..16384 each and within the object's maxima), every image the caller's device memory with its
+ * step in bytes.  rel = HOST double [12] as cart_motion_segment's (all finite, |R entries| <= 2, |t entries| <= 1e6); it may be NULL
+ * only when prev_disp and prev_age are.  disp_cur = int16 x16; prev_disp (int16 x16) and prev_age (u8) = the previous call's fused and
+ * age, both NULL for a frame without a predecessor (nothing is predicted, mask_prev is not read, one launch); mask_prev / mask_cur =
+ * u8 labels of cart_motion_segment or NULL.  Outputs: fused int16 x16, age u8, source u8 (may be NULL), counts = DEVICE int32 [5], the
+ * pixels per source class (4-byte aligned, may be NULL).  int16 images and their steps are 2-byte aligned.  No output may overlap
+ * another output or an input: each such pair is refused by name.  Checked in this order, all before any device call: params, camera,
+ * rel, sizes (also against the object's), object, then pointers, alignment, steps and overlaps; a refused call touches no output.  At
+ * most two plain launches on `stream`, no host synchronisation. */
+int cart_fusion_update(cart_fusion *obj, const cart_ego_camera *camera, const double *rel, const cart_fusion_params *params,
+                       const int16_t *disp_cur, size_t disp_cur_step, const int16_t *prev_disp, size_t prev_disp_step,
+                       const uint8_t *prev_age, size_t prev_age_step, const uint8_t *mask_prev, size_t mask_prev_step,
+                       const uint8_t *mask_cur, size_t mask_cur_step, int width, int height, int16_t *fused, size_t fused_step,
+                       uint8_t *age, size_t age_step, uint8_t *source, size_t source_step, int32_t *counts, void *stream);
+
 /* Stand-in for ImageOpticalFlowModule's device work (src/modules/optflow.cpp:96-140: cvtColor x2 +
  * cv::cuda::NvidiaOpticalFlow_2_0::calc(current, previous), NVIDIA fixed-function hardware): dense census block
  * matching (oracle S15).  cur / prev = the reference images of frame id and id-1 (1-channel gray or 3-channel BGR),
