@@ -44,6 +44,50 @@ def _geom(t, inner):
     return n, C.c_void_p(t.data_ptr()), step, fs
 
 
+def _pitched(t, inner):
+    """-> [data_ptr, step_bytes] of one image for a C-ABI call, [None, 0] for an absent optional one."""
+    return list(_geom(t, inner)[1:3]) if t is not None else [None, 0]
+
+
+def _default_params(struct_type, c_name, fields):
+    """cart_<c_name>_default_params as a `struct_type` with the given fields replaced: what the public *_params functions do."""
+    p = struct_type()
+    getattr(_lib.load(), f"cart_{c_name}_default_params")(C.byref(p))
+    known = dict(struct_type._fields_)
+    for k, v in fields.items():
+        if k not in known:
+            raise ValueError(f"cart_{c_name}_params has no field {k}")
+        setattr(p, k, v)
+    return p
+
+
+def _camera(camera):
+    """EgoCamera or (fx, fy, cx, cy, baseline) -> EgoCamera."""
+    return camera if isinstance(camera, EgoCamera) else EgoCamera(*[float(v) for v in camera])
+
+
+def _pose12(m):
+    """12 numbers, a 3 x 4 pose in row order -> the host array a C-ABI call takes; None stays None."""
+    return (C.c_double * 12)(*[float(v) for v in np.asarray(m, np.float64).reshape(-1)]) if m is not None else None
+
+
+def _to_device(a, dtype, via_host=False):
+    """A host array goes up as a tensor of `dtype`; None stays None.  A tensor is taken as it is, or with via_host copied through the host
+    like an array (contiguous, converted to `dtype`)."""
+    import torch
+    if a is None or (isinstance(a, torch.Tensor) and not via_host):
+        return a
+    return torch.as_tensor(np.ascontiguousarray(a.cpu() if isinstance(a, torch.Tensor) else a), dtype=dtype).cuda()
+
+
+def _check_frame_image(t, dtype, what, frame, channels=None):
+    """t must be a tensor of `dtype` with the [h, w] of the tensor `frame`, and [h, w, channels] when channels is given."""
+    import torch
+    if (not isinstance(t, torch.Tensor) or t.dtype != dtype or t.dim() != (2 if channels is None else 3) or tuple(t.shape[:2]) != tuple(frame.shape[:2])
+            or (channels is not None and t.shape[2] != channels)):
+        raise EngineError(f"{what} must be a device tensor of {dtype} and of the frame's size")
+
+
 def flow_pyramid_levels(w, h, levels):
     """-> [(w_l, h_l)] of the levels spec S21 builds for a w x h frame when `levels` are asked for (cart_flow_pyramid_levels; host only)."""
     lib = _lib.load()
@@ -453,7 +497,7 @@ class Engine:
 
 class _DeviceObject:
     """A C-ABI object made on an engine: cart_<_name>_create(engine, ..., &out) and cart_<_name>_destroy.  A failing call
-    raises EngineError with the library's last error."""
+    raises EngineError with the library's last error.  A context manager: leaving the block closes the object."""
     _name = None
 
     def __init__(self, engine, *args):
@@ -470,6 +514,13 @@ class _DeviceObject:
         if getattr(self, "_h", None):
             getattr(self._lib, f"cart_{self._name}_destroy")(self._h)
             self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
 
     def __del__(self):
         try:
@@ -710,13 +761,7 @@ MATCH_DTYPE = np.dtype([("query", "<i4"), ("train", "<i4"), ("distance", "<i4"),
 
 def match_params(**fields):
     """cart_match_default_params (spec S22) with the given fields replaced."""
-    p = MatchParams()
-    _lib.load().cart_match_default_params(C.byref(p))
-    for k, v in fields.items():
-        if k not in dict(MatchParams._fields_):
-            raise ValueError(f"cart_match_params has no field {k}")
-        setattr(p, k, v)
-    return p
+    return _default_params(MatchParams, "match", fields)
 
 
 class OrbMatcher(_DeviceObject):
@@ -788,13 +833,7 @@ EGO_HYPOTHESIS_DTYPE = np.dtype([("qerr", "<u8"), ("count", "<i4"), ("skipped", 
 
 def ego_params(**fields):
     """cart_ego_default_params (spec S23) with the given fields replaced."""
-    p = EgoParams()
-    _lib.load().cart_ego_default_params(C.byref(p))
-    for k, v in fields.items():
-        if k not in dict(EgoParams._fields_):
-            raise ValueError(f"cart_ego_params has no field {k}")
-        setattr(p, k, v)
-    return p
+    return _default_params(EgoParams, "ego", fields)
 
 
 class EgoMotion(_DeviceObject):
@@ -805,7 +844,7 @@ class EgoMotion(_DeviceObject):
     def __init__(self, engine, camera, max_features=_lib.ORB_DEFAULT_FEATURES):
         """camera = EgoCamera or (fx, fy, cx, cy, baseline)."""
         self.max_features = int(max_features)
-        self.camera = camera if isinstance(camera, EgoCamera) else EgoCamera(*[float(v) for v in camera])
+        self.camera = _camera(camera)
         super().__init__(engine, self.max_features)
 
     def _rows(self, a, dtype, width, what):
@@ -890,13 +929,7 @@ PLANE_MAP_CELL_DTYPE = np.dtype([("horizontal", "<u4"), ("vertical", "<u4"), ("y
 
 def plane_map_params(**fields):
     """cart_plane_map_default_params (spec S24) with the given fields replaced."""
-    p = PlaneMapParams()
-    _lib.load().cart_plane_map_default_params(C.byref(p))
-    for k, v in fields.items():
-        if k not in dict(PlaneMapParams._fields_):
-            raise ValueError(f"cart_plane_map_params has no field {k}")
-        setattr(p, k, v)
-    return p
+    return _default_params(PlaneMapParams, "plane_map", fields)
 
 
 class PlaneMap(_DeviceObject):
@@ -907,7 +940,7 @@ class PlaneMap(_DeviceObject):
 
     def __init__(self, engine, camera, cells_x, cells_z, params=None):
         """camera = EgoCamera or (fx, fy, cx, cy, baseline); params = PlaneMapParams (default: plane_map_params())."""
-        self.camera = camera if isinstance(camera, EgoCamera) else EgoCamera(*[float(v) for v in camera])
+        self.camera = _camera(camera)
         self.cells_x, self.cells_z = int(cells_x), int(cells_z)
         self.params = params if params is not None else plane_map_params()
         super().__init__(engine, self.cells_x, self.cells_z, C.byref(self.params))
@@ -917,16 +950,13 @@ class PlaneMap(_DeviceObject):
         raw=True takes the two device tensors as they are (rows may be pitched) with no conversion or upload.  -> (ox, oz)."""
         import torch
         if not raw:
-            disp = torch.as_tensor(np.ascontiguousarray(disp.cpu() if isinstance(disp, torch.Tensor) else disp), dtype=torch.int16).cuda()
-            planes = torch.as_tensor(np.ascontiguousarray(planes.cpu() if isinstance(planes, torch.Tensor) else planes), dtype=torch.uint8).cuda()
+            disp, planes = _to_device(disp, torch.int16, via_host=True), _to_device(planes, torch.uint8, via_host=True)
         if not isinstance(disp, torch.Tensor) or not isinstance(planes, torch.Tensor) or disp.dtype != torch.int16 or planes.dtype != torch.uint8:
             raise EngineError("disp must be an int16 and planes a uint8 device tensor")
         if disp.dim() != 2 or planes.shape != disp.shape:
             raise EngineError("disp and planes must be [h, w] images of one size")
-        _, dp, ds, _ = _geom(disp, 1)
-        _, pp, ps, _ = _geom(planes, 1)
-        host_pose = (C.c_double * 12)(*[float(v) for v in np.asarray(pose, np.float64).reshape(-1)])
-        self._check(self._lib.cart_plane_map_update(self._h, C.byref(self.camera), host_pose, dp, ds, pp, ps, int(disp.shape[1]), int(disp.shape[0]),
+        images = _pitched(disp, 1) + _pitched(planes, 1)
+        self._check(self._lib.cart_plane_map_update(self._h, C.byref(self.camera), _pose12(pose), *images, int(disp.shape[1]), int(disp.shape[0]),
                                                     _stream_ptr()), "cart_plane_map_update")
         return self.window()[:2]
 
@@ -957,13 +987,7 @@ class PlaneMap(_DeviceObject):
 
 def motion_params(**fields):
     """cart_motion_default_params (spec S25) with the given fields replaced."""
-    p = MotionParams()
-    _lib.load().cart_motion_default_params(C.byref(p))
-    for k, v in fields.items():
-        if k not in dict(MotionParams._fields_):
-            raise ValueError(f"cart_motion_params has no field {k}")
-        setattr(p, k, v)
-    return p
+    return _default_params(MotionParams, "motion", fields)
 
 
 MotionSegmentation = collections.namedtuple("MotionSegmentation", "residual raw labels planes_static")
@@ -976,32 +1000,23 @@ def motion_segment(engine, camera, rel, disp_cur, disp_prev, flow, params=None, 
     otherwise host arrays go up and numpy arrays come back.  -> MotionSegmentation(residual int16 [h, w, 4] or None when residual is
     false, raw uint8 [h, w], labels uint8 [h, w], planes_static uint8 [h, w] or None when planes is)."""
     import torch
-    cam = camera if isinstance(camera, EgoCamera) else EgoCamera(*[float(v) for v in camera])
+    cam = _camera(camera)
     p = params if params is not None else motion_params()
-
-    def dev(a, dtype):
-        if raw or a is None:
-            return a
-        return torch.as_tensor(np.ascontiguousarray(a.cpu() if isinstance(a, torch.Tensor) else a), dtype=dtype).cuda()
-    dc, dp, fl, pl = dev(disp_cur, torch.int16), dev(disp_prev, torch.int16), dev(flow, torch.int16), dev(planes, torch.uint8)
-    for t, dtype, dims, what in ((dc, torch.int16, 2, "disp_cur"), (dp, torch.int16, 2, "disp_prev"), (fl, torch.int16, 3, "flow"), (pl, torch.uint8, 2, "planes")):
-        if t is None and what == "planes":
-            continue
-        if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.dim() != dims or tuple(t.shape[:2]) != tuple(dc.shape[:2]) or (dims == 3 and t.shape[2] != 2):
-            raise EngineError(f"{what} must be a device tensor of {dtype} and of the frame's size")
+    dc, dp, fl, pl = disp_cur, disp_prev, flow, planes
+    if not raw:   # device tensors go through the host too
+        dc, dp, fl, pl = (_to_device(a, dtype, via_host=True) for a, dtype in ((dc, torch.int16), (dp, torch.int16), (fl, torch.int16), (pl, torch.uint8)))
+    for t, dtype, what, channels in ((dc, torch.int16, "disp_cur", None), (dp, torch.int16, "disp_prev", None), (fl, torch.int16, "flow", 2), (pl, torch.uint8, "planes", None)):
+        if t is not None or what != "planes":
+            _check_frame_image(t, dtype, what, dc, channels)
     h, w = int(dc.shape[0]), int(dc.shape[1])
     res = torch.empty((h, w, 4), dtype=torch.int16, device=dc.device) if residual else None
     rawl = torch.empty((h, w), dtype=torch.uint8, device=dc.device)
     labels = torch.empty((h, w), dtype=torch.uint8, device=dc.device)
     static = torch.empty((h, w), dtype=torch.uint8, device=dc.device) if pl is not None else None
-    args = []
-    for t, inner in ((dc, 1), (dp, 1), (fl, 2)):
-        args += list(_geom(t, inner)[1:3])
-    args += [w, h]
+    args = _pitched(dc, 1) + _pitched(dp, 1) + _pitched(fl, 2) + [w, h]
     for t, inner in ((res, 2), (rawl, 1), (labels, 1), (pl, 1), (static, 1)):
-        args += list(_geom(t, inner)[1:3]) if t is not None else [None, 0]
-    host_rel = (C.c_double * 12)(*[float(v) for v in np.asarray(rel, np.float64).reshape(-1)])
-    if _lib.load().cart_motion_segment(engine._h, C.byref(cam), host_rel, C.byref(p), *args, _stream_ptr()) != 0:
+        args += _pitched(t, inner)
+    if _lib.load().cart_motion_segment(engine._h, C.byref(cam), _pose12(rel), C.byref(p), *args, _stream_ptr()) != 0:
         raise EngineError("cart_motion_segment: " + _lib.load().cart_last_error(None).decode())
     out = MotionSegmentation(res, rawl, labels, static)
     return out if raw else MotionSegmentation(*[t.cpu().numpy() if t is not None else None for t in out])
@@ -1012,13 +1027,7 @@ PLACE_CANDIDATE_DTYPE = np.dtype([("slot", "<i4"), ("score", "<i4"), ("frame_id"
 
 def place_params(**fields):
     """cart_place_default_params (spec S27) with the given fields replaced."""
-    p = PlaceParams()
-    _lib.load().cart_place_default_params(C.byref(p))
-    for k, v in fields.items():
-        if k not in dict(PlaceParams._fields_):
-            raise ValueError(f"cart_place_params has no field {k}")
-        setattr(p, k, v)
-    return p
+    return _default_params(PlaceParams, "place", fields)
 
 
 class PlaceDB(_DeviceObject):
@@ -1114,13 +1123,7 @@ DENSE_EGO_RESULT_DTYPE = np.dtype([("R", "<f8", 9), ("t", "<f8", 3), ("rms_initi
 
 def dense_ego_params(**fields):
     """cart_dense_ego_default_params (spec S26) with the given fields replaced."""
-    p = DenseEgoParams()
-    _lib.load().cart_dense_ego_default_params(C.byref(p))
-    for k, v in fields.items():
-        if k not in dict(DenseEgoParams._fields_):
-            raise ValueError(f"cart_dense_ego_params has no field {k}")
-        setattr(p, k, v)
-    return p
+    return _default_params(DenseEgoParams, "dense_ego", fields)
 
 
 class DenseEgo(_DeviceObject):
@@ -1132,13 +1135,6 @@ class DenseEgo(_DeviceObject):
         self.max_width, self.max_height = int(max_width), int(max_height)
         super().__init__(engine, self.max_width, self.max_height)
 
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False
-
     def refine(self, camera, rel, disp_cur, disp_prev, flow, params=None, mask=None, stream=None, raw=False):
         """camera = EgoCamera or (fx, fy, cx, cy, baseline); rel = 12 numbers, the 3 x 4 (R | t) to refine (host); disp_cur / disp_prev int16
         [h, w] (x16), flow int16 [h, w, 2] (S10.5), mask uint8 [h, w] (motion_segment's labels) or None: device tensors are taken as they
@@ -1146,28 +1142,18 @@ class DenseEgo(_DeviceObject):
         DENSE_EGO_RESULT_DTYPE array of one record (host); raw=True returns the device tensor (136 bytes as float64) with no host round
         trip."""
         import torch
-        cam = camera if isinstance(camera, EgoCamera) else EgoCamera(*[float(v) for v in camera])
+        cam = _camera(camera)
         p = params if params is not None else dense_ego_params()
-
-        def dev(a, dtype):
-            if a is None or isinstance(a, torch.Tensor):
-                return a
-            return torch.as_tensor(np.ascontiguousarray(a), dtype=dtype).cuda()
         with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):   # uploads and the result's allocation on the call's stream
-            dc, dp, fl, mk = dev(disp_cur, torch.int16), dev(disp_prev, torch.int16), dev(flow, torch.int16), dev(mask, torch.uint8)
-        for t, dtype, dims, what in ((dc, torch.int16, 2, "disp_cur"), (dp, torch.int16, 2, "disp_prev"), (fl, torch.int16, 3, "flow"), (mk, torch.uint8, 2, "mask")):
-            if t is None and what == "mask":
-                continue
-            if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.dim() != dims or tuple(t.shape[:2]) != tuple(dc.shape[:2]) or (dims == 3 and t.shape[2] != 2):
-                raise EngineError(f"{what} must be a device tensor of {dtype} and of the frame's size")
+            dc, dp, fl, mk = _to_device(disp_cur, torch.int16), _to_device(disp_prev, torch.int16), _to_device(flow, torch.int16), _to_device(mask, torch.uint8)
+        for t, dtype, what, channels in ((dc, torch.int16, "disp_cur", None), (dp, torch.int16, "disp_prev", None), (fl, torch.int16, "flow", 2), (mk, torch.uint8, "mask", None)):
+            if t is not None or what != "mask":
+                _check_frame_image(t, dtype, what, dc, channels)
         h, w = int(dc.shape[0]), int(dc.shape[1])
-        args = []
-        for t, inner in ((dc, 1), (dp, 1), (fl, 2), (mk, 1)):
-            args += list(_geom(t, inner)[1:3]) if t is not None else [None, 0]
+        args = _pitched(dc, 1) + _pitched(dp, 1) + _pitched(fl, 2) + _pitched(mk, 1)
         res = torch.empty(DENSE_EGO_RESULT_DTYPE.itemsize // 8, dtype=torch.float64, device=dc.device)   # every byte is written by the call
-        host_rel = (C.c_double * 12)(*[float(v) for v in np.asarray(rel, np.float64).reshape(-1)])
         sp = C.c_void_p(stream.cuda_stream) if stream is not None else _stream_ptr()
-        self._check(self._lib.cart_dense_ego_refine(self._h, C.byref(cam), host_rel, C.byref(p), *args, w, h, C.c_void_p(res.data_ptr()), sp),
+        self._check(self._lib.cart_dense_ego_refine(self._h, C.byref(cam), _pose12(rel), C.byref(p), *args, w, h, C.c_void_p(res.data_ptr()), sp),
                     "cart_dense_ego_refine")
         if raw:
             return res
@@ -1178,13 +1164,7 @@ class DenseEgo(_DeviceObject):
 
 def fusion_params(**fields):
     """cart_fusion_default_params (spec S28; the defaults are build-owned and untuned) with the given fields replaced."""
-    p = FusionParams()
-    _lib.load().cart_fusion_default_params(C.byref(p))
-    for k, v in fields.items():
-        if k not in dict(FusionParams._fields_):
-            raise ValueError(f"cart_fusion_params has no field {k}")
-        setattr(p, k, v)
-    return p
+    return _default_params(FusionParams, "fusion", fields)
 
 
 class DisparityFusion(_DeviceObject):
@@ -1197,13 +1177,6 @@ class DisparityFusion(_DeviceObject):
         self.max_width, self.max_height = int(max_width), int(max_height)
         super().__init__(engine, self.max_width, self.max_height)
 
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False
-
     def update(self, camera, rel, disp_cur, prev=None, mask_prev=None, mask_cur=None, params=None, source=True, raw=False, stream=None):
         """camera = EgoCamera or (fx, fy, cx, cy, baseline); rel = 12 numbers, the 3 x 4 (R | t) with p_cur = R p_prev + t (host; None is
         allowed without prev); disp_cur int16 [h, w] (x16); prev = (fused, age) of the previous call or None (no previous frame);
@@ -1212,16 +1185,12 @@ class DisparityFusion(_DeviceObject):
         -> (fused int16 [h, w], age uint8 [h, w], source uint8 [h, w] or None when source is false, counts int32 [5]) as numpy arrays;
         raw=True returns the device tensors with no host round trip."""
         import torch
-        cam = camera if isinstance(camera, EgoCamera) else EgoCamera(*[float(v) for v in camera])
+        cam = _camera(camera)
         p = params if params is not None else fusion_params()
         pd, pa = prev if prev is not None else (None, None)
-
-        def dev(a, dtype):
-            if a is None or isinstance(a, torch.Tensor):
-                return a
-            return torch.as_tensor(np.ascontiguousarray(a), dtype=dtype).cuda()
         with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):   # uploads and allocations on the call's stream
-            dc, pd, pa, mp, mc = dev(disp_cur, torch.int16), dev(pd, torch.int16), dev(pa, torch.uint8), dev(mask_prev, torch.uint8), dev(mask_cur, torch.uint8)
+            dc, pd, pa = _to_device(disp_cur, torch.int16), _to_device(pd, torch.int16), _to_device(pa, torch.uint8)
+            mp, mc = _to_device(mask_prev, torch.uint8), _to_device(mask_cur, torch.uint8)
             if not isinstance(dc, torch.Tensor) or dc.dim() != 2:
                 raise EngineError("disp_cur must be an int16 [h, w] image")
             h, w = int(dc.shape[0]), int(dc.shape[1])
@@ -1232,17 +1201,11 @@ class DisparityFusion(_DeviceObject):
         if (pd is None) != (pa is None):
             raise EngineError("prev must be the pair (fused, age) of the previous call")
         for t, dtype, what in ((dc, torch.int16, "disp_cur"), (pd, torch.int16, "prev[0]"), (pa, torch.uint8, "prev[1]"), (mp, torch.uint8, "mask_prev"), (mc, torch.uint8, "mask_cur")):
-            if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != dtype or t.dim() != 2 or tuple(t.shape) != (h, w)):
-                raise EngineError(f"{what} must be a device tensor of {dtype} and of the frame's size")
-        args = []
-        for t in (dc, pd, pa, mp, mc):
-            args += list(_geom(t, 1)[1:3]) if t is not None else [None, 0]
-        args += [w, h]
-        for t in (fused, age, src):
-            args += list(_geom(t, 1)[1:3]) if t is not None else [None, 0]
-        host_rel = (C.c_double * 12)(*[float(v) for v in np.asarray(rel, np.float64).reshape(-1)]) if rel is not None else None
+            if t is not None:
+                _check_frame_image(t, dtype, what, dc)
+        args = [v for t in (dc, pd, pa, mp, mc) for v in _pitched(t, 1)] + [w, h] + [v for t in (fused, age, src) for v in _pitched(t, 1)]
         sp = C.c_void_p(stream.cuda_stream) if stream is not None else _stream_ptr()
-        self._check(self._lib.cart_fusion_update(self._h, C.byref(cam), host_rel, C.byref(p), *args, C.c_void_p(counts.data_ptr()), sp), "cart_fusion_update")
+        self._check(self._lib.cart_fusion_update(self._h, C.byref(cam), _pose12(rel), C.byref(p), *args, C.c_void_p(counts.data_ptr()), sp), "cart_fusion_update")
         out = (fused, age, src, counts)
         if raw:
             return out

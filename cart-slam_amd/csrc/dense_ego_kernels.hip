@@ -9,22 +9,18 @@
 //                    the 6 x 6 system (ego_solve.h, S23's), updates the pose in device memory and, at a stop, writes the result.
 // The pose of evaluation 0 is the call's rel0 (a kernel argument); later evaluations read the state the previous step wrote.  After a
 // stop (too few inliers, a pivot that is not > 0, or the last evaluation) the state's flag makes every later launch leave at once.
-// fp64 with + - * / sqrt only; the library is built with -ffp-contract=off, so every product and sum below is rounded on its own.
+// fp64 with + - * / sqrt only, in the association order of warp_device.h, which holds the warp chain.
 // No floating-point atomics: the result cannot depend on execution order.
 
 #include "engine_internal.h"
 #include "ego_solve.h"
+#include "warp_device.h"
 
 #pragma clang fp contract(off)
 
 namespace cart_amd {
 
 namespace {
-
-template <typename T>
-__device__ __forceinline__ T *row_ptr(T *base, size_t step, int y) {   // pitched rows are addressed in bytes
-    return reinterpret_cast<T *>(reinterpret_cast<uintptr_t>(base) + (size_t)y * step);
-}
 
 // Lane 0 of the ascending butterfly over the workgroup's 256 lanes, for every sum and the two counts: on return lanes 0 .. 27 hold the
 // total of sum `lane` in tot, and every lane holds the counts.
@@ -55,11 +51,11 @@ __device__ __forceinline__ void dense_reduce(double (&acc)[kDenseSums], int &cnt
 __global__ __launch_bounds__(kDenseLanes) void dense_ego_rows_kernel(DenseEgoArgs a, int eval) {
     const DenseEgoState *st = a.state;
     if (eval > 0 && st->stop) return;   // uniform
-    double R[9], t[3];
+    double P[12];   // the pose as 3 x 4 (R | t): rel0 as it comes, later the state's R and t
 #pragma unroll
-    for (int q = 0; q < 9; ++q) R[q] = eval == 0 ? a.rel0[4 * (q / 3) + q % 3] : st->R[q];
+    for (int q = 0; q < 9; ++q) P[4 * (q / 3) + q % 3] = eval == 0 ? a.rel0[4 * (q / 3) + q % 3] : st->R[q];
 #pragma unroll
-    for (int q = 0; q < 3; ++q) t[q] = eval == 0 ? a.rel0[4 * q + 3] : st->t[q];
+    for (int q = 0; q < 3; ++q) P[4 * q + 3] = eval == 0 ? a.rel0[4 * q + 3] : st->t[q];
     const int lane = threadIdx.x, stride = a.p.stride;
     const int y = blockIdx.x * stride;
     const double fx = a.cam.fx, fy = a.cam.fy, cx = a.cam.cx, cy = a.cam.cy, wd = a.p.disparity_weight;
@@ -86,8 +82,8 @@ __global__ __launch_bounds__(kDenseLanes) void dense_ego_rows_kernel(DenseEgoArg
 #pragma unroll
         for (int r = 0; r < kDenseCols; ++r) {   // gates 1 and 2, then every gather of the group before the first use
             const int x = (i0 + r * kDenseLanes + lane) * stride;
-            const int xp = x - ((int)(int16_t)(fl[r] & 0xffff) >> 5);   // previous position = p - (flow >> 5), arithmetic shift per component
-            const int yp = y - (fl[r] >> 21);
+            const int2 prev = flow_previous(fl[r], x, y);
+            const int xp = prev.x, yp = prev.y;
             const bool ok = in[r] && sc[r] != -32768 && (double)sc[r] / 16.0 >= a.p.min_disparity && xp >= 0 && xp < a.w && yp >= 0 && yp < a.h;
             sp[r] = ok ? row_ptr(a.disp_prev, a.disp_prev_step, yp)[xp] : -32768;
         }
@@ -97,14 +93,13 @@ __global__ __launch_bounds__(kDenseLanes) void dense_ego_rows_kernel(DenseEgoArg
             if (sp[r] == -32768 || !(dp >= a.p.min_disparity)) continue;   // gate 3 (a failed gate 1 or 2 or the mask left sp invalid)
             ++ncand;
             const int x = (i0 + r * kDenseLanes + lane) * stride;
-            const int xp = x - ((int)(int16_t)(fl[r] & 0xffff) >> 5), yp = y - (fl[r] >> 21);
-            const double Zp = fxb / dp;
-            const double Xp = (((double)xp - cx) * Zp) / fx;
-            const double Yp = (((double)yp - cy) * Zp) / fy;
-            const double qx = ((R[0] * Xp + R[1] * Yp) + R[2] * Zp) + t[0];
-            const double qy = ((R[3] * Xp + R[4] * Yp) + R[5] * Zp) + t[1];
-            const double qz = ((R[6] * Xp + R[7] * Yp) + R[8] * Zp) + t[2];
+            const int2 prev = flow_previous(fl[r], x, y);
+            const int xp = prev.x, yp = prev.y;
+            const WarpPoint q = pose_carry(P, back_project(a.cam, fxb, xp, yp, dp));
+            const double qx = q.x, qy = q.y, qz = q.z;
             if (!(qz > 0)) continue;
+            // warp_device.h's projection, written out: through project_u / project_v the kernel's instructions come out in another order
+            // and a refinement takes 1 % longer (profiles/pose_warp_refactor.txt)
             const double eu = ((fx * qx) / qz + cx) - (double)x;
             const double ev = ((fy * qy) / qz + cy) - (double)y;
             const double ed = fxb / qz - (double)sc[r] / 16.0;

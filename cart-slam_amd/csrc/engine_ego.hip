@@ -45,13 +45,7 @@ void cart_ego_destroy(cart_ego *g) { destroy_object(g); }
 static int check_camera_and_params(const cart_ego_camera *cam, const cart_ego_params *p) {
     if (!cam) return fail("camera is NULL");
     if (!p) return fail("params is NULL");
-    if (!(cam->fx > 0) || !std::isfinite(cam->fx)) return fail("fx must be a positive number");
-    if (!(cam->fy > 0) || !std::isfinite(cam->fy)) return fail("fy must be a positive number");
-    if (!std::isfinite(cam->cx)) return fail("cx must be finite");
-    if (!std::isfinite(cam->cy)) return fail("cy must be finite");
-    if (!(cam->baseline > 0) || !std::isfinite(cam->baseline)) return fail("baseline must be a positive number");
-    if (!(p->min_disparity > 0) || !std::isfinite(p->min_disparity)) return fail("min_disparity must be a positive number");
-    if (!(p->inlier_threshold > 0) || !std::isfinite(p->inlier_threshold)) return fail("inlier_threshold must be a positive number");
+    if (check_camera(cam) || check_positive("min_disparity", p->min_disparity) || check_positive("inlier_threshold", p->inlier_threshold)) return -1;
     if (p->hypotheses < 1 || p->hypotheses > CART_EGO_MAX_HYPOTHESES) return fail("hypotheses must be in [1, 1024]");
     if (p->refine_iterations < 0 || p->refine_iterations > CART_EGO_MAX_REFINE) return fail("refine_iterations must be in [0, 16]");
     return 0;

@@ -6,26 +6,10 @@
 
 using namespace cart_amd;
 
-namespace {
-
-struct Extent {   // one device argument, for the checks: `rows` rows of `row_bytes`, `step` apart
-    const char *name;
-    const void *ptr;
-    size_t step, elem, row_bytes;
-    int rows;
-    uintptr_t begin() const { return reinterpret_cast<uintptr_t>(ptr); }
-    uintptr_t end() const { return begin() + (size_t)(rows - 1) * step + row_bytes; }
-};
-
-bool overlap(const Extent &a, const Extent &b) { return a.begin() < b.end() && b.begin() < a.end(); }
-
-}  // namespace
-
 extern "C" {
 
-struct cart_fusion : DeviceObject {
-    using DeviceObject::DeviceObject;
-    int max_width = 0, max_height = 0;
+struct cart_fusion : SizedObject {
+    using SizedObject::SizedObject;
     uint32_t *zbuf = nullptr;      // [max_height * max_width]; a call uses the first width * height keys
     int32_t *counters = nullptr;   // [kFusionCounters]
 };
@@ -36,14 +20,11 @@ void cart_fusion_default_params(cart_fusion_params *p) {
 }
 
 int cart_fusion_create(cart_engine *e, int max_width, int max_height, cart_fusion **out) {
-    if (max_width < 1 || max_width > 16384) return fail("max_width must be in [1, 16384]");
-    if (max_height < 1 || max_height > 16384) return fail("max_height must be in [1, 16384]");
+    if (check_max_size(max_width, max_height)) return -1;
     if (!e || !out) return fail("bad arguments");
     HIP_TRY(hipSetDevice(e->params.device_id));
-    cart_fusion *f = new (std::nothrow) cart_fusion(e);
+    cart_fusion *f = new (std::nothrow) cart_fusion(e, max_width, max_height);
     if (!f) return fail("out of host memory");
-    f->max_width = max_width;
-    f->max_height = max_height;
     const size_t zbytes = (size_t)max_width * max_height * sizeof(uint32_t);
     if (f->alloc(&f->zbuf, zbytes) || f->alloc(&f->counters, kFusionCounters * sizeof(int32_t)) || f->create_event() ||
         hipMemset(f->zbuf, 0, zbytes) != hipSuccess || hipMemset(f->counters, 0, kFusionCounters * sizeof(int32_t)) != hipSuccess ||
@@ -62,49 +43,33 @@ int cart_fusion_update(cart_fusion *f, const cart_ego_camera *cam, const double 
                        const uint8_t *mask_prev, size_t mask_prev_step, const uint8_t *mask_cur, size_t mask_cur_step, int w, int h, int16_t *fused,
                        size_t fused_step, uint8_t *age, size_t age_step, uint8_t *source, size_t source_step, int32_t *counts, void *stream_) {
     if (!p) return fail("params is NULL");
-    if (!(p->min_disparity > 0) || !std::isfinite(p->min_disparity)) return fail("min_disparity must be a positive number");
-    if (!(p->agree_threshold > 0) || !std::isfinite(p->agree_threshold)) return fail("agree_threshold must be a positive number");
+    if (check_positive("min_disparity", p->min_disparity) || check_positive("agree_threshold", p->agree_threshold)) return -1;
     if (!(p->splat_radius >= 0.5 && p->splat_radius < 1.0)) return fail("splat_radius must be in [0.5, 1)");
     if (p->max_weight < 1 || p->max_weight > 255) return fail("max_weight must be in [1, 255]");
     if (p->min_age < 1 || p->min_age > 255) return fail("min_age must be in [1, 255]");
     if (check_camera(cam)) return -1;
     if (!rel && (prev_disp || prev_age)) return fail("rel is NULL although a previous frame is given");
-    for (int k = 0; rel && k < 12; ++k) {
-        const double bound = k % 4 == 3 ? 1e6 : 2.0;
-        if (!std::isfinite(rel[k]) || std::fabs(rel[k]) > bound)
-            return fail("rel[" + std::to_string(k) + "] must be finite and within " + (k % 4 == 3 ? "1e6 (translation)" : "2 (rotation)"));
-    }
-    if (w < 1 || w > 16384) return fail("width must be in [1, 16384]");
-    if (h < 1 || h > 16384) return fail("height must be in [1, 16384]");
-    if (f && (w > f->max_width || h > f->max_height))
-        return fail("width x height exceeds the object's " + std::to_string(f->max_width) + " x " + std::to_string(f->max_height));
+    if (rel && check_pose("rel", rel)) return -1;
+    if (check_frame_size(w, h)) return -1;
     if (!f) return fail("bad arguments");
+    if (f->check_fits(w, h)) return -1;
     if (!disp_cur) return fail("disp_cur is NULL");
     if ((prev_disp == nullptr) != (prev_age == nullptr)) return fail("prev_disp and prev_age must be given together");
     if (!fused) return fail("fused is NULL");
     if (!age) return fail("age is NULL");
     if (!prev_disp) mask_prev = nullptr;   // nothing is projected: not read
-    const auto image = [&](const char *name, const void *ptr, size_t step, size_t elem) { return Extent{name, ptr, step, elem, (size_t)w * elem, h}; };
+    const auto image = [&](const char *name, const void *ptr, size_t step, size_t elem) { return Extent::image(name, ptr, step, elem, w, h); };
     // the inputs, then the outputs: an output is checked against everything before it
     const Extent all[] = {image("disp_cur", disp_cur, disp_cur_step, 2), image("prev_disp", prev_disp, prev_disp_step, 2), image("prev_age", prev_age, prev_age_step, 1),
                           image("mask_prev", mask_prev, mask_prev_step, 1), image("mask_cur", mask_cur, mask_cur_step, 1), image("fused", fused, fused_step, 2),
                           image("age", age, age_step, 1), image("source", source, source_step, 1), Extent{"counts", counts, 20, 4, 20, 1}};
     constexpr int kInputs = 5, kAll = 9;
-    for (const Extent &x : all) {
-        if (!x.ptr) continue;
-        const bool is_counts = &x == &all[kAll - 1];
-        if (is_counts) {
-            if (x.begin() % 4) return fail("counts must be 4-byte aligned");
-            continue;
-        }
-        if ((x.begin() % x.elem) || (x.step % x.elem)) return fail(std::string(x.name) + " and its step must be " + std::to_string(x.elem) + "-byte aligned");
-        if (x.step < x.row_bytes) return fail(std::string(x.name) + "_step is below the row size");
-    }
+    for (int i = 0; i < kAll - 1; ++i)
+        if (all[i].ptr && check_pitched(all[i])) return -1;
+    if (all[kAll - 1].begin() % 4) return fail("counts must be 4-byte aligned");   // not pitched: its own wording
     // No output may overlap another buffer: the fuse kernel writes its pixels while other workgroups still read theirs, and two outputs
     // in one place would hold whichever store came last.
-    for (int i = kInputs; i < kAll; ++i)
-        for (int j = 0; all[i].ptr && j < i; ++j)
-            if (all[j].ptr && overlap(all[j], all[i])) return fail(std::string(all[j].name) + " and " + all[i].name + " must not overlap");
+    if (check_outputs_apart(all, kInputs, kAll)) return -1;
 
     FusionArgs a;
     std::memset(&a, 0, sizeof(a));

@@ -1,5 +1,6 @@
 // engine_host.h -- what the host translation units of the C ABI share (cart_engine.hip, engine_*.hip): error reporting, the
-// engine with its slot and slab pools, the scoped slot lease, the per-slot workspaces and the lifecycle of the device objects.
+// engine with its slot and slab pools, the scoped slot lease, the per-slot workspaces, the lifecycle of the device objects and the
+// argument checks the entry points share.
 // Private to csrc/; the host <-> kernel contract is engine_internal.h.
 #pragma once
 
@@ -22,7 +23,29 @@ extern thread_local std::string g_last_error;   // cart_last_error
 extern thread_local int g_last_slot;            // first slot of this thread's most recent compute lease (cart_debug_read)
 
 int fail(const std::string &msg);   // sets g_last_error, returns -1
-int check_camera(const cart_ego_camera *cam);   // fx, fy, baseline > 0 and all finite, else fail() naming the field (engine_planemap.hip)
+
+// ---- argument checks shared by the entry points (engine_checks.hip): each returns 0, or fail() with the message quoted ----
+int check_positive(const char *name, double v);   // "<name> must be a positive number" unless v > 0 and finite
+int check_camera(const cart_ego_camera *cam);     // "camera is NULL"; fx, fy, baseline positive numbers, "cx / cy must be finite"
+int check_pose(const char *name, const double *m);   // "<name> is NULL"; "<name>[k] must be finite and within 2 (rotation) / 1e6 (translation)", 3 x 4 row-major
+int check_frame_size(int w, int h);               // "width / height must be in [1, 16384]"
+int check_max_size(int max_width, int max_height);   // the same for "max_width / max_height"
+
+struct Extent {   // one device argument, for the checks: `rows` rows of `row_bytes`, `step` apart; elem = the alignment of the pointer and the step
+    const char *name;
+    const void *ptr;
+    size_t step, elem, row_bytes;
+    int rows;
+    static Extent image(const char *name, const void *ptr, size_t step, size_t elem, int w, int h) {   // a w x h image of elem-byte pixels
+        return Extent{name, ptr, step, elem, (size_t)w * elem, h};
+    }
+    uintptr_t begin() const { return reinterpret_cast<uintptr_t>(ptr); }
+    uintptr_t end() const { return begin() + (size_t)(rows - 1) * step + row_bytes; }
+};
+int check_pitched(const Extent &x);               // "<name> and its step must be <elem>-byte aligned", then "<name>_step is below the row size"
+bool overlap(const Extent &a, const Extent &b);
+// all[first_output .. n) are the outputs: each against every entry before it, "<earlier> and <later> must not overlap"; NULL entries are skipped
+int check_outputs_apart(const Extent *all, int first_output, int n);
 
 #define HIP_TRY(expr)                                                                               \
     do {                                                                                            \
@@ -195,6 +218,13 @@ class ObjectCall {
     hipStream_t stream;
     std::unique_lock<std::mutex> lk;   // released after the record above
     bool entered = false;
+};
+
+// A device object made for frames of up to max_width x max_height (cart_dense_ego, cart_fusion).
+struct SizedObject : DeviceObject {
+    int max_width, max_height;
+    SizedObject(const cart_engine *e, int max_width, int max_height) : DeviceObject(e), max_width(max_width), max_height(max_height) {}
+    int check_fits(int w, int h) const;   // "width x height exceeds the object's W x H" (engine_checks.hip)
 };
 
 template <typename T>

@@ -5,26 +5,6 @@
 
 using namespace cart_amd;
 
-namespace {
-
-struct Image {   // one pitched argument, for the checks
-    const char *name;
-    const void *ptr;
-    size_t step, elem;   // elem = bytes per pixel = the alignment of the pointer and the step
-    uintptr_t begin() const { return reinterpret_cast<uintptr_t>(ptr); }
-    uintptr_t end(int w, int h) const { return begin() + (size_t)(h - 1) * step + (size_t)w * elem; }
-};
-
-int check_image(const Image &im, int w) {
-    if ((im.begin() % im.elem) || (im.step % im.elem)) return fail(std::string(im.name) + " and its step must be " + std::to_string(im.elem) + "-byte aligned");
-    if (im.step < (size_t)w * im.elem) return fail(std::string(im.name) + "_step is below the row size");
-    return 0;
-}
-
-bool overlap(const Image &a, const Image &b, int w, int h) { return a.begin() < b.end(w, h) && b.begin() < a.end(w, h); }
-
-}  // namespace
-
 extern "C" {
 
 void cart_motion_default_params(cart_motion_params *p) {
@@ -37,37 +17,28 @@ int cart_motion_segment(cart_engine *e, const cart_ego_camera *cam, const double
                         int16_t *residual, size_t residual_step, uint8_t *raw, size_t raw_step, uint8_t *labels, size_t labels_step, const uint8_t *planes,
                         size_t planes_step, uint8_t *planes_static, size_t planes_static_step, void *stream_) {
     if (!p) return fail("params is NULL");
-    if (!(p->min_disparity > 0) || !std::isfinite(p->min_disparity)) return fail("min_disparity must be a positive number");
-    if (!(p->flow_threshold > 0) || !std::isfinite(p->flow_threshold)) return fail("flow_threshold must be a positive number");
-    if (!(p->disparity_threshold > 0) || !std::isfinite(p->disparity_threshold)) return fail("disparity_threshold must be a positive number");
+    if (check_positive("min_disparity", p->min_disparity) || check_positive("flow_threshold", p->flow_threshold) ||
+        check_positive("disparity_threshold", p->disparity_threshold))
+        return -1;
     if (p->radius < 0 || p->radius > kMotionMaxRadius) return fail("radius must be in [0, 4]");
     if (p->support_percent < 1 || p->support_percent > 100) return fail("support_percent must be in [1, 100]");
-    if (check_camera(cam)) return -1;
-    if (!rel) return fail("rel is NULL");
-    for (int k = 0; k < 12; ++k) {
-        const double bound = k % 4 == 3 ? 1e6 : 2.0;
-        if (!std::isfinite(rel[k]) || std::fabs(rel[k]) > bound)
-            return fail("rel[" + std::to_string(k) + "] must be finite and within " + (k % 4 == 3 ? "1e6 (translation)" : "2 (rotation)"));
-    }
-    if (w < 1 || w > 16384) return fail("width must be in [1, 16384]");
-    if (h < 1 || h > 16384) return fail("height must be in [1, 16384]");
+    if (check_camera(cam) || check_pose("rel", rel) || check_frame_size(w, h)) return -1;
     if (!e) return fail("bad arguments");
-    const Image in[] = {{"disp_cur", disp_cur, disp_cur_step, 2}, {"disp_prev", disp_prev, disp_prev_step, 2}, {"flow", flow, flow_step, 4},
-                        {"raw", raw, raw_step, 1}, {"labels", labels, labels_step, 1}};
-    const Image res{"residual", residual, residual_step, 8}, pl{"planes", planes, planes_step, 1}, ps{"planes_static", planes_static, planes_static_step, 1};
-    for (const Image &im : in)
-        if (!im.ptr) return fail(std::string(im.name) + " is NULL");
+    const auto image = [&](const char *name, const void *ptr, size_t step, size_t elem) { return Extent::image(name, ptr, step, elem, w, h); };
+    // the inputs, then the outputs from kOutputs on: an output is checked against everything before it
+    enum { kDispCur, kDispPrev, kFlow, kPlanes, kResidual, kRaw, kLabels, kPlanesStatic, kAll, kOutputs = kResidual };
+    const Extent all[] = {image("disp_cur", disp_cur, disp_cur_step, 2), image("disp_prev", disp_prev, disp_prev_step, 2), image("flow", flow, flow_step, 4),
+                          image("planes", planes, planes_step, 1), image("residual", residual, residual_step, 8), image("raw", raw, raw_step, 1),
+                          image("labels", labels, labels_step, 1), image("planes_static", planes_static, planes_static_step, 1)};
+    static_assert(sizeof(all) / sizeof(all[0]) == kAll, "one entry per index");
+    for (int i : {kDispCur, kDispPrev, kFlow, kRaw, kLabels})   // the required ones
+        if (!all[i].ptr) return fail(std::string(all[i].name) + " is NULL");
     if ((planes == nullptr) != (planes_static == nullptr)) return fail("planes and planes_static must be given together");
-    for (const Image &im : in)
-        if (check_image(im, w)) return -1;
-    if (residual && check_image(res, w)) return -1;
-    if (planes && (check_image(pl, w) || check_image(ps, w))) return -1;
+    for (int i : {kDispCur, kDispPrev, kFlow, kRaw, kLabels, kResidual, kPlanes, kPlanesStatic})   // the required ones first, then the optional ones given
+        if (all[i].ptr && check_pitched(all[i])) return -1;
     // No output may overlap another buffer: the filter reads `raw` and `planes` beside the pixels other blocks write, the residual kernel gathers
     // from `disp_prev` anywhere, and two outputs in one place would hold whichever store came last.
-    const Image *all[] = {&in[0], &in[1], &in[2], planes ? &pl : nullptr, residual ? &res : nullptr, &in[3], &in[4], planes ? &ps : nullptr};
-    for (int i = 4; i < 8; ++i)   // the outputs, each against everything before it
-        for (int j = 0; all[i] && j < i; ++j)
-            if (all[j] && overlap(*all[j], *all[i], w, h)) return fail(std::string(all[j]->name) + " and " + all[i]->name + " must not overlap");
+    if (check_outputs_apart(all, kOutputs, kAll)) return -1;
 
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     HIP_TRY(hipSetDevice(e->params.device_id));

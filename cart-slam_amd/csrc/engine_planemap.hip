@@ -5,18 +5,6 @@
 
 using namespace cart_amd;
 
-namespace cart_amd {
-int check_camera(const cart_ego_camera *cam) {   // as cart_ego_*'s; shared with engine_motion.hip (engine_host.h)
-    if (!cam) return fail("camera is NULL");
-    if (!(cam->fx > 0) || !std::isfinite(cam->fx)) return fail("fx must be a positive number");
-    if (!(cam->fy > 0) || !std::isfinite(cam->fy)) return fail("fy must be a positive number");
-    if (!std::isfinite(cam->cx)) return fail("cx must be finite");
-    if (!std::isfinite(cam->cy)) return fail("cy must be finite");
-    if (!(cam->baseline > 0) || !std::isfinite(cam->baseline)) return fail("baseline must be a positive number");
-    return 0;
-}
-}  // namespace cart_amd
-
 extern "C" {
 
 struct cart_plane_map : DeviceObject {
@@ -43,9 +31,7 @@ int cart_plane_map_create(cart_engine *e, int cells_x, int cells_z, const cart_p
     if (cells_z < 32 || cells_z > 4096 || cells_z % 16) return fail("cells_z must be a multiple of 16 in [32, 4096]");
     if (!p) return fail("params is NULL");
     if (!(p->cell_size >= 0.01) || !std::isfinite(p->cell_size)) return fail("cell_size must be a number >= 0.01");
-    if (!(p->min_disparity > 0) || !std::isfinite(p->min_disparity)) return fail("min_disparity must be a positive number");
-    if (!(p->max_depth > 0) || !std::isfinite(p->max_depth)) return fail("max_depth must be a positive number");
-    if (!(p->max_lateral > 0) || !std::isfinite(p->max_lateral)) return fail("max_lateral must be a positive number");
+    if (check_positive("min_disparity", p->min_disparity) || check_positive("max_depth", p->max_depth) || check_positive("max_lateral", p->max_lateral)) return -1;
     if (!(p->height_quantum >= 0.001) || !std::isfinite(p->height_quantum)) return fail("height_quantum must be a number >= 0.001");
     if (!e || !out) return fail("bad arguments");
     HIP_TRY(hipSetDevice(e->params.device_id));
@@ -71,20 +57,12 @@ int cart_plane_map_clear(cart_plane_map *m) {
 
 int cart_plane_map_update(cart_plane_map *m, const cart_ego_camera *cam, const double *pose, const int16_t *disp, size_t disp_step, const uint8_t *planes,
                           size_t planes_step, int w, int h, void *stream_) {
-    if (check_camera(cam)) return -1;
-    if (!pose) return fail("pose is NULL");
-    for (int k = 0; k < 12; ++k) {
-        const double bound = k % 4 == 3 ? 1e6 : 2.0;
-        if (!std::isfinite(pose[k]) || std::fabs(pose[k]) > bound)
-            return fail("pose[" + std::to_string(k) + "] must be finite and within " + (k % 4 == 3 ? "1e6 (translation)" : "2 (rotation)"));
-    }
-    if (w < 1 || w > 16384) return fail("width must be in [1, 16384]");
-    if (h < 1 || h > 16384) return fail("height must be in [1, 16384]");
+    if (check_camera(cam) || check_pose("pose", pose) || check_frame_size(w, h)) return -1;
     if (!m) return fail("map is NULL");
     if (!disp || !planes) return fail("NULL pointer");
     if ((reinterpret_cast<uintptr_t>(disp) & 1) || (disp_step & 1)) return fail("disparity and its step must be 2-byte aligned");
     if (disp_step < (size_t)w * sizeof(int16_t)) return fail("disparity_step is below the row size");
-    if (planes_step < (size_t)w) return fail("planes_step is below the row size");
+    if (check_pitched(Extent::image("planes", planes, planes_step, 1, w, h))) return -1;
 
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     ObjectCall call(*m, stream);

@@ -8,19 +8,15 @@
 //                 one column.  It writes back the zero it found the z-buffer in (the buffer is all zero between calls, no clear launch) and
 //                 counts the source classes by wave ballots; a workgroup adds its counts to the object's counters in three 64-bit integer
 //                 atomics, and the workgroup that finishes last moves those to the caller's `counts` and zeroes them again.
-// fp64 with + - * / floor only; the library is built with -ffp-contract=off, so every product and sum below is rounded on its own.
+// fp64 with + - * / floor only, in the association order of warp_device.h, which holds the warp chain.
 // The only atomics are integer maxima and additions: the result cannot depend on execution order.
 
 #include "engine_internal.h"
+#include "warp_device.h"
 
 namespace cart_amd {
 
 namespace {
-
-template <typename T>
-__device__ __forceinline__ T *row_ptr(T *base, size_t step, int y) {   // pitched rows are addressed in bytes
-    return reinterpret_cast<T *>(reinterpret_cast<uintptr_t>(base) + (size_t)y * step);
-}
 
 __device__ __forceinline__ double dabs(double v) { return v < 0.0 ? -v : v; }
 
@@ -31,17 +27,10 @@ __device__ __forceinline__ void splat_targets(const FusionArgs &a, int xp, int y
     const double dp = (double)s / 16.0;
     if (age < 1u || s == -32768 || !(dp >= a.p.min_disparity) || mask == 1u) return;
     const double fxb = a.cam.fx * a.cam.baseline;
-    const double Zp = fxb / dp;
-    const double Xp = (((double)xp - a.cam.cx) * Zp) / a.cam.fx;
-    const double Yp = (((double)yp - a.cam.cy) * Zp) / a.cam.fy;
-    const double *R = a.rel;
-    const double qx = ((R[0] * Xp + R[1] * Yp) + R[2] * Zp) + R[3];
-    const double qy = ((R[4] * Xp + R[5] * Yp) + R[6] * Zp) + R[7];
-    const double qz = ((R[8] * Xp + R[9] * Yp) + R[10] * Zp) + R[11];
-    if (!(qz > 0)) return;
-    const double u = (a.cam.fx * qx) / qz + a.cam.cx;
-    const double v = (a.cam.fy * qy) / qz + a.cam.cy;
-    const double swd = floor((fxb / qz) * 16.0 + 0.5);
+    const WarpPoint q = pose_carry(a.rel, back_project(a.cam, fxb, xp, yp, dp));
+    if (!(q.z > 0)) return;
+    const double u = project_u(a.cam, q), v = project_v(a.cam, q);
+    const double swd = floor((fxb / q.z) * 16.0 + 0.5);
     if (!(swd >= 1.0 && swd <= 32767.0)) return;
     const unsigned sw = (unsigned)(int)swd;
     const double r = a.p.splat_radius;

@@ -8,19 +8,15 @@
 //                    counts are separable: one pass of row sums over the staged rows (both counts packed in 16 bits), one pass of
 //                    column sums over those -- (2 radius + 1) (1 + (tile rows + 2 radius) / tile rows) LDS reads per pixel against
 //                    (2 radius + 1)^2 for the direct walk (22 against 81 at radius 4).
-// fp64 with + - * / floor only; the library is built with -ffp-contract=off, so every product and sum below is rounded on its own.
+// fp64 with + - * / floor only, in the association order of warp_device.h, which holds the warp chain.
 // No atomics: the result cannot depend on execution order.
 
 #include "engine_internal.h"
+#include "warp_device.h"
 
 namespace cart_amd {
 
 namespace {
-
-template <typename T>
-__device__ __forceinline__ T *row_ptr(T *base, size_t step, int y) {   // pitched rows are addressed in bytes
-    return reinterpret_cast<T *>(reinterpret_cast<uintptr_t>(base) + (size_t)y * step);
-}
 
 __device__ __forceinline__ int16_t quantise(double e) {   // Q(e) = clamp(floor(16 e + 0.5), -32767, 32767)
     const double v = floor(e * 16.0 + 0.5);
@@ -43,8 +39,9 @@ __global__ __launch_bounds__(256) void motion_residual_kernel(MotionArgs a) {
 #pragma unroll
     for (int r = 0; r < kMotionStrip; ++r) {   // gates 1 and 2, then every gather of the strip before the first use
         dc[r] = (double)sc[r] / 16.0;
-        xp[r] = x - ((int)(int16_t)(fl[r] & 0xffff) >> 5);   // previous position = p - (flow >> 5), arithmetic shift per component
-        yp[r] = (y0 + r) - (fl[r] >> 21);
+        const int2 prev = flow_previous(fl[r], x, y0 + r);
+        xp[r] = prev.x;
+        yp[r] = prev.y;
         const bool ok = in[r] && sc[r] != -32768 && dc[r] >= a.p.min_disparity && xp[r] >= 0 && xp[r] < a.w && yp[r] >= 0 && yp[r] < a.h;
         sp[r] = ok ? row_ptr(a.disp_prev, a.disp_prev_step, yp[r])[xp[r]] : -32768;
     }
@@ -56,17 +53,11 @@ __global__ __launch_bounds__(256) void motion_residual_kernel(MotionArgs a) {
         short4 rec = make_short4(-32768, -32768, -32768, 2);
         const double dp = (double)sp[r] / 16.0;
         if (sp[r] != -32768 && dp >= a.p.min_disparity) {   // gate 3 (a failed gate 1 or 2 left sp invalid)
-            const double Zp = fxb / dp;
-            const double Xp = (((double)xp[r] - a.cam.cx) * Zp) / a.cam.fx;
-            const double Yp = (((double)yp[r] - a.cam.cy) * Zp) / a.cam.fy;
-            const double *R = a.rel;
-            const double qx = ((R[0] * Xp + R[1] * Yp) + R[2] * Zp) + R[3];
-            const double qy = ((R[4] * Xp + R[5] * Yp) + R[6] * Zp) + R[7];
-            const double qz = ((R[8] * Xp + R[9] * Yp) + R[10] * Zp) + R[11];
-            if (qz > 0) {                                    // gate 4
-                const double eu = ((a.cam.fx * qx) / qz + a.cam.cx) - (double)x;
-                const double ev = ((a.cam.fy * qy) / qz + a.cam.cy) - (double)(y0 + r);
-                const double ed = fxb / qz - dc[r];
+            const WarpPoint q = pose_carry(a.rel, back_project(a.cam, fxb, xp[r], yp[r], dp));
+            if (q.z > 0) {                                   // gate 4
+                const double eu = project_u(a.cam, q) - (double)x;
+                const double ev = project_v(a.cam, q) - (double)(y0 + r);
+                const double ed = fxb / q.z - dc[r];
                 const bool moving = eu * eu + ev * ev > ft2 || ed * ed > dt2;
                 rec = make_short4(quantise(eu), quantise(ev), quantise(ed), moving ? 1 : 0);
             }

@@ -5,9 +5,10 @@
 //                       lanes that hold the same key (compare with the lane below, ballot the run heads, segmented suffix reduction)
 //                       and only the run heads issue the global atomics.  Counts, minima and maxima are integers: exact in any order.
 //   plane_map_classify  cell -> class
-// fp64 with + - * / floor only; the library is built with -ffp-contract=off, so every product and sum below is rounded on its own.
+// fp64 with + - * / floor only, in the association order of warp_device.h, which holds the warp chain.
 
 #include "engine_internal.h"
+#include "warp_device.h"
 
 namespace cart_amd {
 
@@ -34,16 +35,14 @@ __device__ __forceinline__ int vote_key(const PlaneMapVoteArgs &a, int x, int y,
     if (!(d >= a.p.min_disparity)) return -1;
     const double Z = (a.cam.fx * a.cam.baseline) / d;
     if (!(Z <= a.p.max_depth)) return -1;
-    const double X = (((double)x - a.cam.cx) * Z) / a.cam.fx;
+    const double X = back_project_x(a.cam, x, Z);
     if (!(X >= -a.p.max_lateral && X <= a.p.max_lateral)) return -1;
-    const double Y = (((double)y - a.cam.cy) * Z) / a.cam.fy;
-    const double *P = a.pose;
-    const double Xw = ((P[0] * X + P[1] * Y) + P[2] * Z) + P[3];
-    const double Zw = ((P[8] * X + P[9] * Y) + P[10] * Z) + P[11];
+    const WarpPoint p{X, back_project_y(a.cam, y, Z), Z};   // Y only after the X gate
+    const double Xw = pose_row(a.pose, 0, p), Zw = pose_row(a.pose, 2, p);
     const double gx = floor(Xw / a.p.cell_size), gz = floor(Zw / a.p.cell_size);
     if (!(gx >= a.ox && gx < a.ox + (double)a.grid.nx && gz >= a.oz && gz < a.oz + (double)a.grid.nz)) return -1;
     if (l == 1u) {
-        const double Yw = ((P[4] * X + P[5] * Y) + P[6] * Z) + P[7];
+        const double Yw = pose_row(a.pose, 1, p);
         double qd = floor(Yw / a.p.height_quantum);
         qd = qd < -1073741824.0 ? -1073741824.0 : (qd > 1073741824.0 ? 1073741824.0 : qd);
         q = (int)qd;

@@ -5,7 +5,7 @@ usage: kernel_asm_diff.py PARENT.s[,PARENT2.s...] BRANCH.s[,BRANCH2.s...] [name-
 
 For every kernel of either side: VGPRs, SGPRs, LDS bytes, private segment, instruction count (parent / branch) and whether the
 instruction streams are identical after stripping comments and assembler directives and renumbering the .LBB labels.
-Wrote profiles/wta_refactor.txt."""
+Wrote profiles/wta_refactor.txt and profiles/pose_warp_refactor.txt."""
 import re
 import subprocess
 import sys
@@ -52,7 +52,7 @@ def main():
         ident = pb[n] == bb[n]
         same += ident
         cnt = lambda x: sum(1 for l in x if not l.endswith(":"))
-        d = re.sub(r"\(.*\)$", "", d).replace("void ", "").replace("cart_amd::", "")
+        d = re.sub(r"\(.*\)$", "", d.replace("(anonymous namespace)::", "")).replace("void ", "").replace("cart_amd::", "")
         print("%-66s %4s/%-4s %4s/%-4s %6s/%-6s %3s/%-3s %5d/%-5d  %s" % (
             d, p["vgpr_count"], b["vgpr_count"], p["sgpr_count"], b["sgpr_count"], p["group_segment_fixed_size"], b["group_segment_fixed_size"],
             p["private_segment_fixed_size"], b["private_segment_fixed_size"], cnt(pb[n]), cnt(bb[n]), "identical" if ident else "DIFFERENT"))

@@ -127,3 +127,21 @@ def test_integer_uniqueness_threshold_is_the_float_compare_exhaustively():
     from cartslam.engine import uniq_table
     for ratio in range(101):
         _check_uniq_table(uniq_table(ratio), ratio)
+
+
+@pytest.mark.parametrize("name", ["match", "ego", "plane_map", "motion", "place", "dense_ego", "fusion"])
+def test_params_functions_replace_named_fields_only(name):
+    """<name>_params(**fields): the library's defaults with the named fields replaced; an unknown field names the C struct."""
+    from cartslam import _lib, engine
+    make = getattr(engine, name + "_params")
+    defaults = type(make())()
+    getattr(_lib.load(), f"cart_{name}_default_params")(C.byref(defaults))   # straight from the library, not through the function under test
+    fields = [n for n, _ in defaults._fields_]
+    assert [getattr(make(), n) for n in fields] == [getattr(defaults, n) for n in fields]
+    with pytest.raises(ValueError) as err:
+        make(nope=1)
+    assert str(err.value) == f"cart_{name}_params has no field nope"
+    for k in (fields[0], fields[-1]):
+        p = make(**{k: getattr(defaults, k) + 1})
+        assert getattr(p, k) == getattr(defaults, k) + 1
+        assert [getattr(p, n) for n in fields if n != k] == [getattr(defaults, n) for n in fields if n != k]
