@@ -146,6 +146,19 @@ class FusionParams(C.Structure):
     _fields_ = [(n, C.c_double) for n in ("min_disparity", "agree_threshold", "splat_radius")] + [(n, C.c_int32) for n in ("max_weight", "min_age")]
 
 
+class PoseGraphParams(C.Structure):
+    # mirrors cart_pose_graph_params (include/cart_engine.h, spec S29); the default is cart_pose_graph_default_params'
+    _fields_ = [("iterations", C.c_int32)]
+
+
+class PoseGraphResult(C.Structure):
+    # mirrors cart_pose_graph_result (include/cart_engine.h, spec S29)
+    _fields_ = [(n, C.c_int32) for n in ("status", "n_nodes", "n_loops", "iterations")] + [("cost_before", C.c_double), ("cost_after", C.c_double)]
+
+
+POSE_GRAPH_MAX_NODES, POSE_GRAPH_MAX_LOOPS, POSE_GRAPH_MAX_ITERATIONS = 4096, 64, 16   # CART_POSE_GRAPH_MAX_*
+
+
 FUSION_NONE, FUSION_MEASURED, FUSION_AGREED, FUSION_REPLACED, FUSION_PREDICTED = range(5)   # CART_FUSION_*
 
 
@@ -250,6 +263,16 @@ PROTOTYPES = {
     "cart_fusion_destroy": (None, [_vp]),
     "cart_fusion_update": (_i, [_vp, C.POINTER(EgoCamera), C.POINTER(C.c_double), C.POINTER(FusionParams), _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz,
                                 _i, _i, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp]),
+    "cart_pose_graph_default_params": (None, [C.POINTER(PoseGraphParams)]),
+    "cart_pose_graph_create": (_i, [_vp, _i, _i, C.POINTER(_vp)]),
+    "cart_pose_graph_destroy": (None, [_vp]),
+    "cart_pose_graph_clear": (_i, [_vp, _vp]),
+    "cart_pose_graph_size": (_i, [_vp, C.POINTER(_i), C.POINTER(_i)]),
+    "cart_pose_graph_add_node": (_i, [_vp, C.POINTER(C.c_double), C.c_double, C.c_double, C.POINTER(C.c_int32), _vp]),
+    "cart_pose_graph_add_loop": (_i, [_vp, _i, _i, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_double, C.c_double, _vp]),
+    "cart_pose_graph_optimize": (_i, [_vp, C.POINTER(PoseGraphParams), _vp, _vp]),
+    "cart_pose_graph_poses": (_i, [_vp, _i, _i, _vp, _vp]),
+    "cart_pose_graph_read": (_i, [_vp, _i, _i, C.POINTER(C.c_double)]),
     "cart_optical_flow": (_i, [_vp, _vp, _sz, _vp, _sz, _i, _i, _i, _vp, _sz, _vp]),
     "cart_flow_default_params": (None, [C.POINTER(FlowParams)]),
     "cart_flow_pyramid_levels": (_i, [_i, _i, _i, C.POINTER(_i), C.POINTER(_i)]),

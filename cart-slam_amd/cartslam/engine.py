@@ -10,7 +10,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import DenseEgoParams, EgoCamera, EgoParams, EngineParams, FusionParams, MatchParams, MotionParams, PlaceParams, PlaneMapParams, PlaneParams, SuperpixelParams
+from ._lib import DenseEgoParams, EgoCamera, EgoParams, EngineParams, FusionParams, MatchParams, MotionParams, PlaceParams, PlaneMapParams, PlaneParams, PoseGraphParams, SuperpixelParams
 
 INVALID = -32768  # CARTSLAM_DISPARITY_INVALID, reference include/modules/disparity.hpp:17
 
@@ -1115,6 +1115,66 @@ class PlaceDB(_DeviceObject):
 
     def clear(self):
         self._check(self._lib.cart_place_clear(self._h, _stream_ptr()), "cart_place_clear")
+
+
+POSE_GRAPH_RESULT_DTYPE = np.dtype([("status", "<i4"), ("n_nodes", "<i4"), ("n_loops", "<i4"), ("iterations", "<i4"), ("cost_before", "<f8"),
+                                   ("cost_after", "<f8")])   # cart_pose_graph_result
+
+
+def pose_graph_params(**fields):
+    """cart_pose_graph_default_params (spec S29) with the given fields replaced."""
+    return _default_params(PoseGraphParams, "pose_graph", fields)
+
+
+class PoseGraph(_DeviceObject):
+    """Pose-graph optimisation over keyframes (cart_pose_graph_* in the C ABI, spec S29 in DESIGN.md 7.11): nodes are camera-to-world poses
+    in insertion order with an odometry edge between neighbours, loop edges join any two nodes, optimize() runs Gauss-Newton over all nodes
+    but the first on the device.  Stateful in call order."""
+    _name = "pose_graph"
+
+    def __init__(self, engine, max_nodes=1024, max_loops=64):
+        self.max_nodes, self.max_loops = int(max_nodes), int(max_loops)
+        super().__init__(engine, self.max_nodes, self.max_loops)
+
+    def add_node(self, pose, w_rot, w_trans):
+        """pose = 12 numbers (3 x 4 camera-to-world, KITTI row order, host); the weights of the odometry edge to the previous node.
+        -> the node's index.  No host synchronisation."""
+        node = C.c_int32(-1)
+        self._check(self._lib.cart_pose_graph_add_node(self._h, _pose12(pose), float(w_rot), float(w_trans), C.byref(node), _stream_ptr()), "cart_pose_graph_add_node")
+        return node.value
+
+    def add_loop(self, a, b, R, t, w_rot, w_trans):
+        """The loop edge p_b = R p_a + t between nodes a and b: R = 9 numbers in row order, t = 3 (host)."""
+        Rh = (C.c_double * 9)(*[float(v) for v in np.asarray(R, np.float64).reshape(-1)])
+        th = (C.c_double * 3)(*[float(v) for v in np.asarray(t, np.float64).reshape(-1)])
+        self._check(self._lib.cart_pose_graph_add_loop(self._h, int(a), int(b), Rh, th, float(w_rot), float(w_trans), _stream_ptr()), "cart_pose_graph_add_loop")
+
+    def optimize(self, iterations=None, params=None, raw=False):
+        """`iterations` Gauss-Newton steps (default: pose_graph_params()'s 4) -> the POSE_GRAPH_RESULT_DTYPE record [1] (synchronises);
+        raw=True: the device tensor of 4 doubles that holds it, no host synchronisation."""
+        import torch
+        p = params if params is not None else (pose_graph_params(iterations=int(iterations)) if iterations is not None else pose_graph_params())
+        out = torch.zeros(POSE_GRAPH_RESULT_DTYPE.itemsize // 8, dtype=torch.float64, device="cuda")
+        self._check(self._lib.cart_pose_graph_optimize(self._h, C.byref(p), C.c_void_p(out.data_ptr()), _stream_ptr()), "cart_pose_graph_optimize")
+        return out if raw else out.cpu().numpy().view(POSE_GRAPH_RESULT_DTYPE)
+
+    def poses(self, first=0, count=None, raw=False):
+        """-> float64 [count, 12], the estimates of nodes first .. first + count - 1 (default: all); raw=True: the device tensor, no
+        host synchronisation."""
+        import torch
+        n = self.size()[0] - int(first) if count is None else int(count)
+        out = torch.zeros((max(n, 0), 12), dtype=torch.float64, device="cuda")
+        self._check(self._lib.cart_pose_graph_poses(self._h, int(first), n, C.c_void_p(out.data_ptr()) if n > 0 else C.c_void_p(8), _stream_ptr()), "cart_pose_graph_poses")
+        return out if raw else out.cpu().numpy()
+
+    def size(self):
+        """-> (nodes, loops); host only."""
+        nodes, loops = C.c_int(0), C.c_int(0)
+        self._check(self._lib.cart_pose_graph_size(self._h, C.byref(nodes), C.byref(loops)), "cart_pose_graph_size")
+        return nodes.value, loops.value
+
+    def clear(self):
+        self._check(self._lib.cart_pose_graph_clear(self._h, _stream_ptr()), "cart_pose_graph_clear")
 
 
 DENSE_EGO_RESULT_DTYPE = np.dtype([("R", "<f8", 9), ("t", "<f8", 3), ("rms_initial", "<f8"), ("rms", "<f8"), ("status", "<i4"), ("n_candidates", "<i4"),

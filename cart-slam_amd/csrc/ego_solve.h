@@ -54,4 +54,21 @@ __device__ inline void ego_update(const double d[6], double R[9], double t[3]) {
     for (int k = 0; k < 3; ++k) t[k] = tn[k];
 }
 
+// the right-multiplying form (spec S29): R <- R Rq, t <- t + R upsilon with the R from before the update
+__device__ inline void ego_update_right(const double d[6], double R[9], double t[3]) {
+    const double hx = 0.5 * d[0], hy = 0.5 * d[1], hz = 0.5 * d[2];
+    const double s = sqrt(((1.0 + hx * hx) + hy * hy) + hz * hz);
+    const double w = 1.0 / s, x = hx / s, y = hy / s, z = hz / s;
+    const double Rq[9] = {1.0 - 2.0 * (y * y + z * z), 2.0 * (x * y - w * z), 2.0 * (x * z + w * y),
+                          2.0 * (x * y + w * z), 1.0 - 2.0 * (x * x + z * z), 2.0 * (y * z - w * x),
+                          2.0 * (x * z - w * y), 2.0 * (y * z + w * x), 1.0 - 2.0 * (x * x + y * y)};
+    double Rn[9], tn[3];
+    for (int r = 0; r < 3; ++r) {
+        for (int c = 0; c < 3; ++c) Rn[3 * r + c] = (R[3 * r] * Rq[c] + R[3 * r + 1] * Rq[3 + c]) + R[3 * r + 2] * Rq[6 + c];
+        tn[r] = t[r] + ((R[3 * r] * d[3] + R[3 * r + 1] * d[4]) + R[3 * r + 2] * d[5]);
+    }
+    for (int k = 0; k < 9; ++k) R[k] = Rn[k];
+    for (int k = 0; k < 3; ++k) t[k] = tn[k];
+}
+
 }  // namespace cart_amd

@@ -440,6 +440,42 @@ struct FusionArgs {
 };
 void launch_fusion_splat(const FusionArgs &a, hipStream_t s);
 void launch_fusion_fuse(const FusionArgs &a, hipStream_t s);
+// ---- pose-graph optimisation over keyframes (posegraph_kernels.hip) ----
+constexpr int kPgMaxNodes = 4096, kPgMaxLoops = 64, kPgMaxIterations = 16;
+constexpr int kPgLinDoubles = 120;     // per odometry edge: Haa [36], Hbb [36], Hba [36], ga [6], gb [6]
+constexpr int kPgLoopDoubles = 84;     // per loop edge: the U block at a [36], at b [36], ga [6], gb [6]
+constexpr int kPgFacDoubles = 80;      // per node: L [36] (lower entries), 1 / diagonal [6], the sub-diagonal block [36], 2 unused
+struct PgEdge {                        // 128 bytes; p_b = R p_a + t
+    double R[9], t[3], w_rot, w_trans;
+    int32_t a, b, pad[2];
+};
+struct PoseGraphStore {
+    double *odom, *est, *snap;         // [max_nodes][12] each
+    PgEdge *edges;                     // [max_nodes + max_loops]: the odometry edge (n - 1, n) at n, loop e at max_nodes + e
+    double *lin, *lin_loop, *fac;      // [max_nodes][kPgLinDoubles], [max_loops][kPgLoopDoubles], [max_nodes][kPgFacDoubles]
+    double *cols;                      // [max_nodes * 6][1 + 6 max_loops]: column 0 the right-hand side b, 1 + 6 e + c column c of loop e
+    double *lc, *lr;                   // the loop system: columns of 6 max_loops + 1 rows (the last row is the right-hand side); its rows
+    double *cd, *ld;                   // the diagonal of C and of its factor, [6 max_loops] each
+    int max_nodes, max_loops;
+};
+struct PoseGraphNodeArgs {
+    PoseGraphStore g;
+    double pose[12], w_rot, w_trans;
+    int n;                             // the new node's index
+};
+struct PoseGraphLoopArgs {
+    PoseGraphStore g;
+    PgEdge edge;
+    int e;                             // the new loop's index
+};
+struct PoseGraphArgs {
+    PoseGraphStore g;
+    int n_nodes, n_loops, iterations;
+    cart_pose_graph_result *result;    // may be NULL
+};
+void launch_pose_graph_add_node(const PoseGraphNodeArgs &a, hipStream_t s);
+void launch_pose_graph_add_loop(const PoseGraphLoopArgs &a, hipStream_t s);
+void launch_pose_graph_optimize(const PoseGraphArgs &a, hipStream_t s);   // one launch whatever the counts
 void launch_narrow_copy(const void *src, void *dst, size_t bytes, int blocks, hipStream_t s);
 int kernel_count();
 

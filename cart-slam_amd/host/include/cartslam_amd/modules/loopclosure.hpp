@@ -1,7 +1,7 @@
 // modules/loopclosure.hpp -- an extension module (the reference recognises no place): every keyframe's left ORB features are scored
 // against a device-resident ring of earlier keyframes through cart_place_* (include/cart_engine.h, spec DESIGN.md S27), the best
 // candidates are verified by a cross-checked match and a relative pose (cart_matcher_match, cart_ego_estimate), and the frame is stored.
-// Factory type "loop_closure".  Pose-graph optimisation is not done here: the module ends at the verified constraint.
+// Factory type "loop_closure".  Pose-graph optimisation is not done here: the module ends at the verified constraint, which modules/posegraph.hpp consumes.
 #pragma once
 #include <memory>
 #include <mutex>

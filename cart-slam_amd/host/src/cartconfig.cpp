@@ -23,6 +23,7 @@
 #include "cartslam_amd/modules/planefit.hpp"
 #include "cartslam_amd/modules/planemap.hpp"
 #include "cartslam_amd/modules/planeseg.hpp"
+#include "cartslam_amd/modules/posegraph.hpp"
 #include "cartslam_amd/modules/superpixels.hpp"
 
 #define CART_CONFIG_KEY_DATA_SOURCE "data_source"
@@ -80,6 +81,7 @@ bool endsWith(const std::string &s, const std::string &suffix) { return s.size()
 void applyModuleConfig(const Value &modulesConfig, std::shared_ptr<System> system) {
     if (!modulesConfig.is_array()) throw std::runtime_error("Modules configuration is not an array.");
     auto dataSource = system->getDataSource();
+    int loopKeyframeInterval = 0;   // of the loop_closure module, once one is configured: pose_graph must use the same keyframes
     for (const auto &moduleConfig : modulesConfig.arr) {
         if (!moduleConfig.is_object()) throw std::runtime_error("Module configuration is not an object.");
         const std::string moduleType = moduleConfig.at("type").get<std::string>();
@@ -249,6 +251,19 @@ void applyModuleConfig(const Value &modulesConfig, std::shared_ptr<System> syste
             o.refineIterations = get(moduleConfig, "refine_iterations", o.refineIterations);
             o.poseKey = get<std::string>(moduleConfig, "pose_key", o.poseKey);   // "dense_ego": keyframes are stored with the refined pose
             system->addModule<LoopClosureModule>(o);
+            loopKeyframeInterval = o.keyframeInterval;
+        } else if (moduleType == "pose_graph") {  // extension (spec S29): loop_closure's keyframes as a pose graph, optimised when a loop is accepted
+            PoseGraphOptions o;
+            o.keyframeInterval = get(moduleConfig, "keyframe_interval", o.keyframeInterval);
+            o.loopClosureInterval = loopKeyframeInterval;
+            o.maxNodes = get(moduleConfig, "max_nodes", o.maxNodes);
+            o.maxLoops = get(moduleConfig, "max_loops", o.maxLoops);
+            o.iterations = get(moduleConfig, "iterations", o.iterations);
+            o.weightRotation = get(moduleConfig, "weight_rotation", o.weightRotation);
+            o.weightTranslation = get(moduleConfig, "weight_translation", o.weightTranslation);
+            o.loopWeight = get(moduleConfig, "loop_weight", o.loopWeight);
+            o.poseKey = get<std::string>(moduleConfig, "pose_key", o.poseKey);   // "dense_ego": the refined trajectory is the odometry
+            system->addModule<PoseGraphModule>(o);
         } else if (endsWith(moduleType, "_visualization")) {
             std::cerr << "[cartconfig] skipping GUI module type " << moduleType << " (out of scope)\n";
         } else {

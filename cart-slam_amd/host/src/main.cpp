@@ -27,6 +27,7 @@
 #include "cartslam_amd/modules/planefit.hpp"
 #include "cartslam_amd/modules/planemap.hpp"
 #include "cartslam_amd/modules/planeseg.hpp"
+#include "cartslam_amd/modules/posegraph.hpp"
 
 int main(int argc, char **argv) {
     if (argc < 3) {
@@ -123,6 +124,18 @@ int main(int argc, char **argv) {
                     auto loop = run->getData<cart::LoopClosure>(CARTSLAM_KEY_LOOP_CLOSURE);
                     std::ofstream o(dump + "/" + std::to_string(id) + "_" + CARTSLAM_KEY_LOOP_CLOSURE + ".bin", std::ios::binary);
                     o.write(reinterpret_cast<const char *>(loop.get()), sizeof(*loop));
+                }
+                if (run->hasData(CARTSLAM_KEY_POSE_GRAPH)) {   // the 48-byte PoseGraphRecord, then the corrected pose as 12 doubles; every node's estimate on a frame that optimised
+                    auto record = run->getData<cart::PoseGraphRecord>(CARTSLAM_KEY_POSE_GRAPH_RESULT);
+                    auto corrected = run->getData<cart::EgoMotion>(CARTSLAM_KEY_POSE_GRAPH);
+                    std::ofstream o(dump + "/" + std::to_string(id) + "_" + CARTSLAM_KEY_POSE_GRAPH + ".bin", std::ios::binary);
+                    o.write(reinterpret_cast<const char *>(record.get()), sizeof(*record));
+                    o.write(reinterpret_cast<const char *>(corrected->pose), sizeof(corrected->pose));
+                    auto nodes = run->getData<std::vector<double>>(CARTSLAM_KEY_POSE_GRAPH_NODES);
+                    if (!nodes->empty()) {
+                        std::ofstream n(dump + "/" + std::to_string(id) + "_" + CARTSLAM_KEY_POSE_GRAPH + "_nodes.bin", std::ios::binary);
+                        n.write(reinterpret_cast<const char *>(nodes->data()), (std::streamsize)(nodes->size() * sizeof(double)));
+                    }
                 }
                 if (run->hasData(CARTSLAM_KEY_PLANE_MAP)) {   // int64 ox, oz; int32 Nx, Nz; double cell_size; the 16-byte cells; the u8 classes
                     auto pm = run->getData<cart::PlaneMap>(CARTSLAM_KEY_PLANE_MAP);

@@ -809,6 +809,60 @@ int cart_fusion_update(cart_fusion *obj, const cart_ego_camera *camera, const do
                        const uint8_t *mask_cur, size_t mask_cur_step, int width, int height, int16_t *fused, size_t fused_step,
                        uint8_t *age, size_t age_step, uint8_t *source, size_t source_step, int32_t *counts, void *stream);
 
+/* ---- Pose-graph optimisation over keyframes (spec S29) -------------------------------------------------------------
+ * An extension: the reference optimises no trajectory.  Nodes are camera-to-world poses (3 x 4, KITTI row order) in insertion order,
+ * odometry edges join consecutive nodes, loop edges any two; Gauss-Newton over all nodes but node 0 with an exact step: the odometry
+ * edges give a block-tridiagonal matrix that is factored in node order, the loop edges enter as a low-rank term (Woodbury).  fp64 with
+ * + - * / sqrt only, every sum in one written order, no atomics: restated in tests/np_posegraph.py, byte for byte.
+ *   Node n: odom_n = the pose handed in, est_n = the estimate; est_0 = odom_0 and never moves; est_n = est_{n-1} (odom_{n-1}^-1 odom_n)
+ *   at insertion, inv = (R^T, -(R^T t)).
+ *   Edge (a, b, M = (R_m, t_m), w_rot, w_trans): p_b = R_m p_a + t_m (cart_ego_result's convention).  The odometry edge (n-1, n) has
+ *   M = odom_n^-1 odom_{n-1} and the weights given with node n.
+ *   Residual: E = M (est_a^-1 est_b) = (R_e, t_e), rho = 0.5 (R_e[2,1] - R_e[1,2], R_e[0,2] - R_e[2,0], R_e[1,0] - R_e[0,1]), tau = t_e;
+ *   cost = sum over the edges, odometry first, of w_rot rho.rho + w_trans tau.tau (S23's 256 virtual lanes).
+ *   Update: R_i <- R_i Rq(omega_i), t_i <- t_i + R_i upsilon_i with S23's Rq.  The Jacobians, the step and every operation order:
+ *   DESIGN.md 7.11.  A pivot that is not > 0 in either factorisation ends the call with status 0 and every estimate as it was. */
+typedef struct cart_pose_graph_params {
+    int32_t iterations;                       /* 0..16 Gauss-Newton steps, no early exit */
+} cart_pose_graph_params;
+void cart_pose_graph_default_params(cart_pose_graph_params *p); /* extension: 4 (build-owned) */
+#define CART_POSE_GRAPH_MAX_NODES 4096
+#define CART_POSE_GRAPH_MAX_LOOPS 64
+#define CART_POSE_GRAPH_MAX_ITERATIONS 16
+typedef struct cart_pose_graph_result {
+    int32_t status;                           /* 1 = optimised (or nothing to do), 0 = a pivot was not > 0: nothing moved */
+    int32_t n_nodes, n_loops, iterations;     /* what the call saw */
+    double cost_before, cost_after;           /* both 0 for a graph without an edge; cost_after = cost_before with status 0 */
+} cart_pose_graph_result;
+
+typedef struct cart_pose_graph cart_pose_graph;
+/* Extension.  Everything for max_nodes in 1..4096 and max_loops in 0..64 is allocated here: 96 + 96 + 96 bytes per node (odom, estimate,
+ * snapshot), 128 per edge, 960 + 640 per node for the linearisation and the factor, the column workspace of max_nodes x 6 x (1 + 6
+ * max_loops) doubles (19 MB at 1024 / 64) and the loop system, about 2 (6 max_loops + 1)^2 doubles.  The sizes are checked before the engine. */
+int cart_pose_graph_create(cart_engine *engine, int max_nodes, int max_loops, cart_pose_graph **out);
+/* Extension.  Keeps the device it was created on, so it may be destroyed after its engine. */
+void cart_pose_graph_destroy(cart_pose_graph *pg);
+/* Extension.  Forgets every node and loop; ordered on `stream` like every other call.  The object is stateful in call order. */
+int cart_pose_graph_clear(cart_pose_graph *pg, void *stream);
+/* Extension.  HOST getter, no device work: the node and loop counts (either pointer may be NULL). */
+int cart_pose_graph_size(cart_pose_graph *pg, int *nodes, int *loops);
+/* Extension.  Appends a node: pose = HOST double [12] (all finite, |R entries| <= 2, |t entries| <= 1e6), the weights of the odometry
+ * edge to the previous node finite and > 0 (checked for node 0 too, where they are not used).  node_out (HOST, may be NULL) = its index.
+ * The pose travels as kernel arguments: one launch on `stream`, no host synchronisation.  A full table is refused and touches nothing. */
+int cart_pose_graph_add_node(cart_pose_graph *pg, const double *pose, double w_rot, double w_trans, int32_t *node_out, void *stream);
+/* Extension.  Appends the loop edge (a, b, (R, t)) with p_b = R p_a + t: R = HOST double [9], t = HOST double [3], all finite; a != b,
+ * both below the node count; weights finite and > 0.  One launch, no host synchronisation.  A full loop table is refused. */
+int cart_pose_graph_add_loop(cart_pose_graph *pg, int a, int b, const double *R, const double *t, double w_rot, double w_trans, void *stream);
+/* Extension.  params->iterations Gauss-Newton steps over the graph as it stands.  result = DEVICE record (8-byte aligned) or NULL.
+ * One launch on `stream` whatever the node and loop counts, no host synchronisation.  Checked in this order, all before any device
+ * call: params, object, then the pointer. */
+int cart_pose_graph_optimize(cart_pose_graph *pg, const cart_pose_graph_params *params, cart_pose_graph_result *result, void *stream);
+/* Extension.  Copies the estimates of nodes [first, first + count) as 12 doubles each to out = DEVICE memory (8-byte aligned) on `stream`;
+ * count = 0 copies nothing. */
+int cart_pose_graph_poses(cart_pose_graph *pg, int first, int count, double *out, void *stream);
+/* Extension.  The same into HOST memory, after every call queued on the object so far; synchronises.  For tests and dumps. */
+int cart_pose_graph_read(cart_pose_graph *pg, int first, int count, double *out_host);
+
 /* Stand-in for ImageOpticalFlowModule's device work (src/modules/optflow.cpp:96-140: cvtColor x2 +
  * cv::cuda::NvidiaOpticalFlow_2_0::calc(current, previous), NVIDIA fixed-function hardware): dense census block
  * matching (oracle S15).  cur / prev = the reference images of frame id and id-1 (1-channel gray or 3-channel BGR),
