@@ -70,7 +70,8 @@ class DataContainer {
 
 // include/utils/modules.hpp:5-9
 #define MODULE_NO_RETURN_VALUE (std::vector<cart::system_data_pair_t>{})
-#define MODULE_RETURN(key, value) (std::vector<cart::system_data_pair_t>{std::make_pair(std::string(key), std::shared_ptr<void>(value))})
+#define MODULE_PAIR(key, value) std::make_pair(std::string(key), std::shared_ptr<void>(value))
+#define MODULE_RETURN(key, value) (std::vector<cart::system_data_pair_t>{MODULE_PAIR(key, value)})
 #define MODULE_RETURN_ALL(...) (std::vector<cart::system_data_pair_t>{__VA_ARGS__})
-#define MODULE_MAKE_PAIR(key, valueType, ...) std::make_pair(std::string(key), std::shared_ptr<void>(std::make_shared<valueType>(__VA_ARGS__)))
+#define MODULE_MAKE_PAIR(key, valueType, ...) MODULE_PAIR(key, std::make_shared<valueType>(__VA_ARGS__))
 #define MODULE_RETURN_SHARED(key, valueType, ...) (std::vector<cart::system_data_pair_t>{MODULE_MAKE_PAIR(key, valueType, __VA_ARGS__)})

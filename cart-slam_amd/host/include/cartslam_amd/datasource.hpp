@@ -14,6 +14,12 @@ struct CameraIntrinsics {
     float Q[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
 };
 
+// The pinhole camera a module works with: every *Options struct of a module that takes one derives from this, and the factory
+// fills it from the configuration's keys or, by default, from the data source's Q (an uncalibrated source leaves fx = 0)
+struct CameraOptions {
+    double fx = 0, fy = 0, cx = 0, cy = 0, baseline = 0;
+};
+
 enum DataElementType { STEREO };
 
 class DataElement {

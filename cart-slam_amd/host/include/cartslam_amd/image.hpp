@@ -7,6 +7,8 @@
 #include <stdexcept>
 #include <vector>
 
+struct ihipStream_t;   // hipStream_t is a pointer to it (hip_runtime_api.h, which this header does not include)
+
 namespace cart {
 
 // OpenCV type codes (depth + ((channels-1) << 3)), so `type()` checks read like the reference's (planeseg.cu:255)
@@ -42,6 +44,30 @@ class DeviceImage {
 };
 
 typedef DeviceImage image_t;
+
+// What a module that runs one frame at a time owns on the device: one non-blocking stream of default priority, a device buffer
+// and the pinned host buffer its results are downloaded through.  All three start empty.  The destructor frees the buffers
+// and then destroys the stream; a C-ABI object that used them is destroyed before that, in the owner's destructor body
+// (cart_*_destroy synchronises the device).
+class DeviceScratch {
+   public:
+    DeviceScratch() = default;
+    DeviceScratch(const DeviceScratch &) = delete;
+    DeviceScratch &operator=(const DeviceScratch &) = delete;
+    ~DeviceScratch();
+
+    void create();                                      // makes the stream, once
+    void reserve(size_t devBytes, size_t hostBytes);    // the buffers only grow; growing does not keep what they held
+    void wait() const;                                  // hipStreamSynchronize
+    ihipStream_t *stream() const { return stream_; }    // hipStream_t; NULL before create()
+    template <typename T = void> T *dev() const { return static_cast<T *>(dev_); }
+    template <typename T = void> T *host() const { return static_cast<T *>(host_); }
+
+   private:
+    ihipStream_t *stream_ = nullptr;
+    void *dev_ = nullptr, *host_ = nullptr;
+    size_t devBytes_ = 0, hostBytes_ = 0;
+};
 
 struct Size {
     int width = 0, height = 0;

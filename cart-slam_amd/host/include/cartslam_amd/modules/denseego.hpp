@@ -16,8 +16,7 @@ namespace cart {
 static_assert(sizeof(cart_dense_ego_result) == 136, "cart_dense_ego_result layout");
 
 // The seven parameters are build-owned choices that no data set has tuned.
-struct DenseEgoOptions {
-    double fx = 0, fy = 0, cx = 0, cy = 0, baseline = 0;   // the factory fills them from the data source's Q
+struct DenseEgoOptions : CameraOptions {   // the factory fills the camera from the data source's Q
     double minDisparity = 1.0, flowThreshold = 2.0, disparityThreshold = 1.0, disparityWeight = 1.0;   // cart_dense_ego_default_params
     int iterations = 4, stride = 1, minInliers = 1024;
     bool useMotion = false;   // leave out the pixels "motion" calls MOVING
@@ -36,7 +35,6 @@ class DenseEgoModule : public SyncWrapperSystemModule {
     const DenseEgoOptions options;
     std::mutex mutex;                    // one frame at a time: every frame chains on the one before
     cart_dense_ego *object = nullptr;    // made for the first frame's size
-    void *stream = nullptr;              // hipStream_t
-    void *dev = nullptr, *host = nullptr;   // the result on the device and the pinned buffer it is downloaded through
+    DeviceScratch scratch;               // the one stream; the result on the device and the pinned buffer it is downloaded through
 };
 }  // namespace cart

@@ -19,8 +19,7 @@ struct EgoMotion {
 static_assert(sizeof(cart_ego_result) == 120, "cart_ego_result layout");
 
 // All defaults are build-owned choices that no data set has tuned.
-struct EgoMotionOptions {
-    double fx = 0, fy = 0, cx = 0, cy = 0, baseline = 0;   // the factory fills them from the data source's Q
+struct EgoMotionOptions : CameraOptions {   // the factory fills the camera from the data source's Q
     double minDisparity = 1.0, inlierThreshold = 2.0;      // cart_ego_default_params
     int hypotheses = 256, refineIterations = 4;
     uint64_t seed = 0;

@@ -20,8 +20,7 @@ struct FusionCounts {
 };
 
 // The five parameters are build-owned choices that no data set has tuned.
-struct TemporalFusionOptions {
-    double fx = 0, fy = 0, cx = 0, cy = 0, baseline = 0;   // the factory fills them from the data source's Q
+struct TemporalFusionOptions : CameraOptions {   // the factory fills the camera from the data source's Q
     double minDisparity = 1.0, agreeThreshold = 1.0, splatRadius = 0.75;   // cart_fusion_default_params
     int maxWeight = 4, minAge = 2;
     bool useMotion = false;               // "motion" of this frame masks the prediction, of the previous frame the sources
@@ -38,7 +37,6 @@ class TemporalFusionModule : public SyncWrapperSystemModule {
     const TemporalFusionOptions options;
     std::mutex mutex;                // one frame at a time: every frame feeds on the one before
     cart_fusion *object = nullptr;   // made for the first frame's size
-    void *stream = nullptr;          // hipStream_t
-    void *dev = nullptr, *host = nullptr;   // the counts on the device and the pinned buffer they are downloaded through
+    DeviceScratch scratch;           // the one stream; the counts on the device and the pinned buffer they are downloaded through
 };
 }  // namespace cart

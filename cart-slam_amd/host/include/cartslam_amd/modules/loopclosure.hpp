@@ -27,8 +27,7 @@ struct LoopClosure {           // all zeros on a frame that is no keyframe and o
 static_assert(sizeof(LoopClosure) == 336, "LoopClosure layout (tests/np_place.py LOOP_DTYPE)");
 
 // All defaults are build-owned choices that no data set has tuned.
-struct LoopClosureOptions {
-    double fx = 0, fy = 0, cx = 0, cy = 0, baseline = 0;   // the factory fills them from the data source's Q
+struct LoopClosureOptions : CameraOptions {   // the factory fills the camera from the data source's Q
     int maxDistance = 64, ratio = 80, minScore = 30, maxCandidates = 4;   // cart_place_default_params; the first two also rule the verifying match
     uint64_t minGap = 50;
     int capacity = 256, keyframeInterval = 5, verify = 1, minInliers = 30;
@@ -55,8 +54,7 @@ class LoopClosureModule : public SyncWrapperSystemModule {
     cart_place_db *db = nullptr;
     cart_matcher *matcher = nullptr;
     cart_ego *ego = nullptr;
-    void *stream = nullptr;              // hipStream_t
-    void *dev = nullptr, *host = nullptr;   // candidates, counts, the pose result and the match list on the device; the pinned buffer they come through
+    DeviceScratch scratch;               // the one stream; candidates, counts, the pose result and the match list on the device; the pinned buffer they come through
     std::vector<Keyframe> keyframes;     // per slot: what the ring holds there
 };
 }  // namespace cart

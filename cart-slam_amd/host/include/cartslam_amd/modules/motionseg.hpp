@@ -21,8 +21,7 @@
 
 namespace cart {
 // The five parameters are build-owned choices that no data set has tuned.
-struct MotionSegOptions {
-    double fx = 0, fy = 0, cx = 0, cy = 0, baseline = 0;   // the factory fills them from the data source's Q
+struct MotionSegOptions : CameraOptions {   // the factory fills the camera from the data source's Q
     double minDisparity = 1.0, flowThreshold = 2.0, disparityThreshold = 1.0;   // cart_motion_default_params
     int radius = 2, supportPercent = 50;
     bool planes = false, components = true;
@@ -42,7 +41,7 @@ class MotionSegModule : public SyncWrapperSystemModule {
     const MotionSegOptions options;
     std::mutex mutex;                 // guards the lazy creation and the enqueue on the one stream; released before the frame's wait, so frames overlap their host side
     cart_engine *engine = nullptr;
-    void *stream = nullptr;           // hipStream_t
+    DeviceScratch scratch;            // the one stream (no buffers)
     std::shared_ptr<Outputs> unknown; // what every frame without an estimate publishes, made once
 };
 }  // namespace cart

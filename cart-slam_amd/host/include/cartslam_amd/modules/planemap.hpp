@@ -23,8 +23,7 @@ struct PlaneMap {
 };
 
 // The grid and vote defaults are build-owned choices that no data set has tuned; 20 and 10 are the reference's gates.
-struct PlaneMapOptions {
-    double fx = 0, fy = 0, cx = 0, cy = 0, baseline = 0;   // the factory fills them from the data source's Q
+struct PlaneMapOptions : CameraOptions {   // the factory fills the camera from the data source's Q
     int cellsX = 512, cellsZ = 512;
     double cellSize = 0.25, minDisparity = 1.0, maxDepth = 20.0, maxLateral = 10.0, heightQuantum = 0.05;   // cart_plane_map_default_params
     int minVotes = 3, obstaclePercent = 50;
@@ -47,6 +46,6 @@ class PlaneMapModule : public SyncWrapperSystemModule {
     std::vector<bool> poseGiven;
     std::mutex mutex;                            // the frames arrive one at a time (the -1 dependency); this guards the lazy creation
     cart_plane_map *map = nullptr;
-    void *stream = nullptr;                      // hipStream_t
+    DeviceScratch scratch;                       // the one stream (no buffers)
 };
 }  // namespace cart

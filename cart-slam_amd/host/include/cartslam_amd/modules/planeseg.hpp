@@ -96,7 +96,7 @@ class DisparityPlaneSegmentationModule : public SyncWrapperSystemModule {
     int32_t *derivativeHistogram = nullptr;  // persistent 256-bin device histogram (planeseg.hpp:160-161)
     std::mutex engineMutex;
     std::shared_ptr<EngineHandle> engine;
-    std::shared_ptr<class PlaneCoalescer> coalescer;  // frames that wait together share one launch per stage (modules.cpp); NULL when CARTSLAM_COALESCE=0
+    std::shared_ptr<class PlaneCoalescer> coalescer;  // frames that wait together share one launch per stage (planeseg.cpp); NULL when CARTSLAM_COALESCE=0
     void ensureHistogram();
 };
 

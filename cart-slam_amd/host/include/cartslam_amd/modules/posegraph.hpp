@@ -49,8 +49,7 @@ class PoseGraphModule : public SyncWrapperSystemModule {
     const PoseGraphOptions options;
     std::mutex mutex;                    // one frame at a time: the graph is the module's state
     cart_pose_graph *graph = nullptr;
-    void *stream = nullptr;              // hipStream_t
-    void *dev = nullptr, *host = nullptr;   // the result record, then every node's estimate: on the device and the pinned buffer they come through
+    DeviceScratch scratch;               // the one stream; the result record, then every node's estimate: on the device and the pinned buffer they come through
     std::vector<uint64_t> nodeFrames;    // frame id of every node
     bool haveNode = false;
     double odomNode[12] = {}, estNode[12] = {};   // the last node: the pose it was handed in with and its estimate

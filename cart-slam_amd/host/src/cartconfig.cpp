@@ -76,6 +76,16 @@ std::shared_ptr<DataSource> createDataSource(const Value &cfg) {
     throw std::runtime_error("Unknown data source type.");
 }
 
+// The camera of a module: the configuration's keys, else Q as the source builds it (an uncalibrated source has fx = 0)
+void readCamera(const Value &moduleConfig, const DataSource &dataSource, CameraOptions &o) {
+    const CameraIntrinsics K = dataSource.getCameraIntrinsics();
+    o.fx = get(moduleConfig, "fx", (double)K.Q[11]);
+    o.fy = get(moduleConfig, "fy", (double)K.Q[11]);
+    o.cx = get(moduleConfig, "cx", -(double)K.Q[3]);
+    o.cy = get(moduleConfig, "cy", -(double)K.Q[7]);
+    o.baseline = get(moduleConfig, "baseline", K.Q[14] != 0 ? std::fabs(1.0 / (double)K.Q[14]) : 0.0);
+}
+
 bool endsWith(const std::string &s, const std::string &suffix) { return s.size() >= suffix.size() && s.compare(s.size() - suffix.size(), suffix.size(), suffix) == 0; }
 
 void applyModuleConfig(const Value &modulesConfig, std::shared_ptr<System> system) {
@@ -144,12 +154,7 @@ void applyModuleConfig(const Value &modulesConfig, std::shared_ptr<System> syste
             system->addModule<FeatureMatcherModule>(o);
         } else if (moduleType == "ego_motion") {  // extension (spec S23): frame-to-frame pose from the orb_matches module's output
             EgoMotionOptions o;
-            const CameraIntrinsics K = dataSource->getCameraIntrinsics();   // Q as the source builds it: an uncalibrated source has fx = 0
-            o.fx = get(moduleConfig, "fx", (double)K.Q[11]);
-            o.fy = get(moduleConfig, "fy", (double)K.Q[11]);
-            o.cx = get(moduleConfig, "cx", -(double)K.Q[3]);
-            o.cy = get(moduleConfig, "cy", -(double)K.Q[7]);
-            o.baseline = get(moduleConfig, "baseline", K.Q[14] != 0 ? std::fabs(1.0 / (double)K.Q[14]) : 0.0);
+            readCamera(moduleConfig, *dataSource, o);
             o.minDisparity = get(moduleConfig, "min_disparity", o.minDisparity);
             o.inlierThreshold = get(moduleConfig, "inlier_threshold", o.inlierThreshold);
             o.hypotheses = get(moduleConfig, "hypotheses", o.hypotheses);
@@ -158,12 +163,7 @@ void applyModuleConfig(const Value &modulesConfig, std::shared_ptr<System> syste
             system->addModule<EgoMotionModule>(o);
         } else if (moduleType == "plane_map") {  // extension (spec S24): disparity + planes voted into a world-frame grid through the frame's pose
             PlaneMapOptions o;
-            const CameraIntrinsics K = dataSource->getCameraIntrinsics();   // as for ego_motion
-            o.fx = get(moduleConfig, "fx", (double)K.Q[11]);
-            o.fy = get(moduleConfig, "fy", (double)K.Q[11]);
-            o.cx = get(moduleConfig, "cx", -(double)K.Q[3]);
-            o.cy = get(moduleConfig, "cy", -(double)K.Q[7]);
-            o.baseline = get(moduleConfig, "baseline", K.Q[14] != 0 ? std::fabs(1.0 / (double)K.Q[14]) : 0.0);
+            readCamera(moduleConfig, *dataSource, o);
             o.cellsX = get(moduleConfig, "cells_x", o.cellsX);
             o.cellsZ = get(moduleConfig, "cells_z", o.cellsZ);
             o.cellSize = get(moduleConfig, "cell_size", o.cellSize);
@@ -180,12 +180,7 @@ void applyModuleConfig(const Value &modulesConfig, std::shared_ptr<System> syste
             system->addModule<PlaneMapModule>(o);
         } else if (moduleType == "motion_seg") {  // extension (spec S25): which pixels moved on their own, from disparity, optflow and ego_motion
             MotionSegOptions o;
-            const CameraIntrinsics K = dataSource->getCameraIntrinsics();   // as for ego_motion
-            o.fx = get(moduleConfig, "fx", (double)K.Q[11]);
-            o.fy = get(moduleConfig, "fy", (double)K.Q[11]);
-            o.cx = get(moduleConfig, "cx", -(double)K.Q[3]);
-            o.cy = get(moduleConfig, "cy", -(double)K.Q[7]);
-            o.baseline = get(moduleConfig, "baseline", K.Q[14] != 0 ? std::fabs(1.0 / (double)K.Q[14]) : 0.0);
+            readCamera(moduleConfig, *dataSource, o);
             o.minDisparity = get(moduleConfig, "min_disparity", o.minDisparity);
             o.flowThreshold = get(moduleConfig, "flow_threshold", o.flowThreshold);
             o.disparityThreshold = get(moduleConfig, "disparity_threshold", o.disparityThreshold);
@@ -196,12 +191,7 @@ void applyModuleConfig(const Value &modulesConfig, std::shared_ptr<System> syste
             system->addModule<MotionSegModule>(o);
         } else if (moduleType == "dense_ego") {  // extension (spec S26): ego_motion's relative pose refined over every static pixel
             DenseEgoOptions o;
-            const CameraIntrinsics K = dataSource->getCameraIntrinsics();   // as for ego_motion
-            o.fx = get(moduleConfig, "fx", (double)K.Q[11]);
-            o.fy = get(moduleConfig, "fy", (double)K.Q[11]);
-            o.cx = get(moduleConfig, "cx", -(double)K.Q[3]);
-            o.cy = get(moduleConfig, "cy", -(double)K.Q[7]);
-            o.baseline = get(moduleConfig, "baseline", K.Q[14] != 0 ? std::fabs(1.0 / (double)K.Q[14]) : 0.0);
+            readCamera(moduleConfig, *dataSource, o);
             o.minDisparity = get(moduleConfig, "min_disparity", o.minDisparity);
             o.flowThreshold = get(moduleConfig, "flow_threshold", o.flowThreshold);
             o.disparityThreshold = get(moduleConfig, "disparity_threshold", o.disparityThreshold);
@@ -213,12 +203,7 @@ void applyModuleConfig(const Value &modulesConfig, std::shared_ptr<System> syste
             system->addModule<DenseEgoModule>(o);
         } else if (moduleType == "temporal_fusion") {  // extension (spec S28): the previous fused disparity carried through the pose and fused with this frame's
             TemporalFusionOptions o;
-            const CameraIntrinsics K = dataSource->getCameraIntrinsics();   // as for ego_motion
-            o.fx = get(moduleConfig, "fx", (double)K.Q[11]);
-            o.fy = get(moduleConfig, "fy", (double)K.Q[11]);
-            o.cx = get(moduleConfig, "cx", -(double)K.Q[3]);
-            o.cy = get(moduleConfig, "cy", -(double)K.Q[7]);
-            o.baseline = get(moduleConfig, "baseline", K.Q[14] != 0 ? std::fabs(1.0 / (double)K.Q[14]) : 0.0);
+            readCamera(moduleConfig, *dataSource, o);
             o.minDisparity = get(moduleConfig, "min_disparity", o.minDisparity);
             o.agreeThreshold = get(moduleConfig, "agree_threshold", o.agreeThreshold);
             o.splatRadius = get(moduleConfig, "splat_radius", o.splatRadius);
@@ -229,12 +214,7 @@ void applyModuleConfig(const Value &modulesConfig, std::shared_ptr<System> syste
             system->addModule<TemporalFusionModule>(o);
         } else if (moduleType == "loop_closure") {  // extension (spec S27): keyframes recognised in a device-resident ring and verified by a relative pose
             LoopClosureOptions o;
-            const CameraIntrinsics K = dataSource->getCameraIntrinsics();   // as for ego_motion
-            o.fx = get(moduleConfig, "fx", (double)K.Q[11]);
-            o.fy = get(moduleConfig, "fy", (double)K.Q[11]);
-            o.cx = get(moduleConfig, "cx", -(double)K.Q[3]);
-            o.cy = get(moduleConfig, "cy", -(double)K.Q[7]);
-            o.baseline = get(moduleConfig, "baseline", K.Q[14] != 0 ? std::fabs(1.0 / (double)K.Q[14]) : 0.0);
+            readCamera(moduleConfig, *dataSource, o);
             o.maxDistance = get(moduleConfig, "max_distance", o.maxDistance);
             o.ratio = get(moduleConfig, "ratio", o.ratio);
             o.minScore = get(moduleConfig, "min_score", o.minScore);

@@ -122,5 +122,32 @@ std::vector<uint8_t> DeviceImage::downloadTight() const {
     return out;
 }
 
+DeviceScratch::~DeviceScratch() {
+    if (dev_) (void)hipFree(dev_);
+    if (host_) (void)hipHostFree(host_);
+    if (stream_) (void)hipStreamDestroy(stream_);
+}
+
+void DeviceScratch::create() {
+    if (!stream_) check(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking), "hipStreamCreateWithFlags");
+}
+
+void DeviceScratch::reserve(size_t dBytes, size_t hBytes) {
+    if (dBytes > devBytes_) {
+        if (dev_) check(hipFree(dev_), "hipFree");
+        dev_ = nullptr; devBytes_ = 0;
+        check(hipMalloc(&dev_, dBytes), "hipMalloc");
+        devBytes_ = dBytes;
+    }
+    if (hBytes > hostBytes_) {
+        if (host_) check(hipHostFree(host_), "hipHostFree");
+        host_ = nullptr; hostBytes_ = 0;
+        check(hipHostMalloc(&host_, hBytes, hipHostMallocDefault), "hipHostMalloc");
+        hostBytes_ = hBytes;
+    }
+}
+
+void DeviceScratch::wait() const { check(hipStreamSynchronize(stream_), "hipStreamSynchronize"); }
+
 void DeviceImage::setTo(int byte_value) { check(hipMemset2D(data, step, byte_value, (size_t)cols * elemSize(type_), rows), "hipMemset2D"); }
 }  // namespace cart

@@ -1,20 +1,15 @@
 // loopclosure.cpp -- LoopClosureModule (cartslam_amd/modules/loopclosure.hpp): place recognition and loop verification, spec DESIGN.md S27.
 #include "cartslam_amd/modules/loopclosure.hpp"
 
-#include <hip/hip_runtime_api.h>
-
 #include <cmath>
 #include <cstring>
 
 #include "cartslam_amd/modules/denseego.hpp"
 #include "cartslam_amd/modules/features.hpp"
+#include "module_support.hpp"
 
 namespace cart {
 namespace {
-[[noreturn]] void failAbi(const char *what) { throw std::runtime_error(std::string(what) + ": " + cart_last_error(nullptr)); }
-void hipCheck(hipError_t e, const char *what) {
-    if (e != hipSuccess) throw std::runtime_error(std::string(what) + ": " + hipGetErrorString(e));
-}
 cart_place_params placeParamsOf(const LoopClosureOptions &o) { return cart_place_params{o.maxDistance, o.ratio, o.minScore, o.maxCandidates, o.minGap}; }
 
 // the module's device buffer: candidates [16] | n_candidates, match_count | cart_ego_result | matches [features]
@@ -23,24 +18,19 @@ static_assert(sizeof(cart_ego_result) <= 128, "cart_ego_result layout");
 }  // namespace
 
 LoopClosureModule::LoopClosureModule(const LoopClosureOptions &options) : SyncWrapperSystemModule("LoopClosure"), options(options) {
-    const auto positive = [](double v) { return v > 0 && std::isfinite(v); };
-    if (!positive(options.fx)) throw std::invalid_argument("fx must be a positive number (a source without calibration needs the camera keys)");
-    if (!positive(options.fy)) throw std::invalid_argument("fy must be a positive number");
-    if (!std::isfinite(options.cx)) throw std::invalid_argument("cx must be finite");
-    if (!std::isfinite(options.cy)) throw std::invalid_argument("cy must be finite");
-    if (!positive(options.baseline)) throw std::invalid_argument("baseline must be a positive number");
+    checkCamera(options);
     // the library's own checks, without a device: everything valid gets as far as the missing object
     const cart_place_params p = placeParamsOf(options);
     (void)cart_place_query(nullptr, &p, nullptr, 0, nullptr, 0, nullptr, nullptr, nullptr, nullptr);
-    if (std::strcmp(cart_last_error(nullptr), "bad arguments") != 0) throw std::invalid_argument(cart_last_error(nullptr));
+    requireLibraryAccepts();
     cart_place_db *none = nullptr;
     (void)cart_place_create(nullptr, 1, options.capacity, &none);
-    if (std::strcmp(cart_last_error(nullptr), "bad arguments") != 0) throw std::invalid_argument(cart_last_error(nullptr));
+    requireLibraryAccepts();
     if (options.keyframeInterval < 1) throw std::invalid_argument("keyframe_interval must be at least 1");
     if (options.verify < 0 || options.verify > CART_PLACE_MAX_CANDIDATES) throw std::invalid_argument("verify must be in [0, 16]");
     if (options.minInliers < 0) throw std::invalid_argument("min_inliers must not be negative");
-    if (!positive(options.minDisparity)) throw std::invalid_argument("min_disparity must be a positive number");
-    if (!positive(options.inlierThreshold)) throw std::invalid_argument("inlier_threshold must be a positive number");
+    if (!positiveNumber(options.minDisparity)) throw std::invalid_argument("min_disparity must be a positive number");
+    if (!positiveNumber(options.inlierThreshold)) throw std::invalid_argument("inlier_threshold must be a positive number");
     if (options.hypotheses < 1 || options.hypotheses > CART_EGO_MAX_HYPOTHESES) throw std::invalid_argument("hypotheses must be in [1, 1024]");
     if (options.refineIterations < 0 || options.refineIterations > CART_EGO_MAX_REFINE) throw std::invalid_argument("refine_iterations must be in [0, 16]");
     if (options.poseKey != CARTSLAM_KEY_EGO_MOTION && options.poseKey != CARTSLAM_KEY_DENSE_EGO)
@@ -57,9 +47,6 @@ LoopClosureModule::~LoopClosureModule() {
     cart_place_destroy(db);
     cart_matcher_destroy(matcher);
     cart_ego_destroy(ego);
-    if (dev) (void)hipFree(dev);
-    if (host) (void)hipHostFree(host);
-    if (stream) (void)hipStreamDestroy(static_cast<hipStream_t>(stream));
 }
 
 system_data_t LoopClosureModule::runInternal(System &, SystemRunData &data) {
@@ -77,28 +64,20 @@ system_data_t LoopClosureModule::runInternal(System &, SystemRunData &data) {
             throw std::runtime_error("LoopClosureModule: ego_motion's landmarks are missing or of another capacity than the features");
         std::lock_guard<std::mutex> lock(mutex);
         if (!db) {   // the objects keep the device of the engine they are made on, not the engine
-            cart_engine_params ep;
-            cart_engine_default_params(&ep);
-            ep.width = 64; ep.height = 32; ep.num_disparities = 0; ep.paths = 0; ep.max_inflight = 1;
-            cart_engine *engine = nullptr;
-            if (cart_engine_create(&ep, &engine) != 0) failAbi("cart_engine_create");
-            std::string error;
-            if (cart_place_create(engine, n, options.capacity, &db) != 0) error = std::string("cart_place_create: ") + cart_last_error(nullptr);
-            else if (cart_matcher_create(engine, n, &matcher) != 0) error = std::string("cart_matcher_create: ") + cart_last_error(nullptr);
-            else if (cart_ego_create(engine, n, &ego) != 0) error = std::string("cart_ego_create: ") + cart_last_error(nullptr);
-            cart_engine_destroy(engine);
-            if (!error.empty()) throw std::runtime_error(error);
+            makeOnPostEngine(64, 32, [&](cart_engine *e) -> const char * {
+                if (cart_place_create(e, n, options.capacity, &db) != 0) return "cart_place_create";
+                if (cart_matcher_create(e, n, &matcher) != 0) return "cart_matcher_create";
+                if (cart_ego_create(e, n, &ego) != 0) return "cart_ego_create";
+                return nullptr;
+            });
             featureCapacity = n;
-            hipStream_t s = nullptr;
-            hipCheck(hipStreamCreateWithFlags(&s, hipStreamNonBlocking), "hipStreamCreateWithFlags");
-            stream = s;
-            hipCheck(hipMalloc(&dev, kMatchesAt + (size_t)n * sizeof(cart_match)), "hipMalloc");
-            hipCheck(hipHostMalloc(&host, kMatchesAt, hipHostMallocDefault), "hipHostMalloc");
+            scratch.create();
+            scratch.reserve(kMatchesAt + (size_t)n * sizeof(cart_match), kMatchesAt);
         }
         if (n != featureCapacity) throw std::runtime_error("LoopClosureModule: the feature capacity changed between frames");
-        hipStream_t s = static_cast<hipStream_t>(stream);
-        uint8_t *d = static_cast<uint8_t *>(dev);
-        const uint8_t *h = static_cast<const uint8_t *>(host);
+        hipStream_t s = scratch.stream();
+        uint8_t *d = scratch.dev<uint8_t>();
+        const uint8_t *h = scratch.host<uint8_t>();
         cart_place_candidate *candidatesDev = reinterpret_cast<cart_place_candidate *>(d);
         int32_t *countsDev = reinterpret_cast<int32_t *>(d + kCountsAt);
         cart_ego_result *resultDev = reinterpret_cast<cart_ego_result *>(d + kResultAt);
@@ -107,13 +86,13 @@ system_data_t LoopClosureModule::runInternal(System &, SystemRunData &data) {
         // 1. the query, 2. the candidate list through the pinned buffer
         if (cart_place_query(db, &p, left.descriptors.ptr<uint8_t>(), left.descriptors.step, left.deviceCount(), data.id, nullptr, candidatesDev, countsDev, s) != 0)
             failAbi("cart_place_query");
-        hipCheck(hipMemcpyAsync(host, dev, kResultAt, hipMemcpyDeviceToHost, s), "hipMemcpyAsync of the candidates");
-        hipCheck(hipStreamSynchronize(s), "hipStreamSynchronize");
+        hipCheck(hipMemcpyAsync(scratch.host(), d, kResultAt, hipMemcpyDeviceToHost, s), "hipMemcpyAsync of the candidates");
+        scratch.wait();
         const int found = *reinterpret_cast<const int32_t *>(h + kCountsAt);
         if (found < 0 || found > options.maxCandidates) throw std::runtime_error("cart_place_query: candidate count out of range");
         std::vector<cart_place_candidate> candidates(reinterpret_cast<const cart_place_candidate *>(h), reinterpret_cast<const cart_place_candidate *>(h) + found);
         // 3. verification: a cross-checked match against the stored frame, then the relative pose between the two frames' landmarks
-        const cart_ego_camera cam{options.fx, options.fy, options.cx, options.cy, options.baseline};
+        const cart_ego_camera cam = cameraOf(options);
         const cart_ego_params ep{options.minDisparity, options.inlierThreshold, options.hypotheses, options.refineIterations};
         cart_match_params mp;
         cart_match_default_params(&mp);
@@ -133,9 +112,9 @@ system_data_t LoopClosureModule::runInternal(System &, SystemRunData &data) {
             if (cart_ego_estimate(ego, &cam, &ep, landmarks->landmarks.ptr<double>(), left.deviceKeypoints(), slotLandmarks, matchesDev, countsDev + 1, options.seed,
                                   data.id, resultDev, nullptr, s) != 0)
                 failAbi("cart_ego_estimate");
-            hipCheck(hipMemcpyAsync(static_cast<uint8_t *>(host) + kResultAt, resultDev, sizeof(cart_ego_result), hipMemcpyDeviceToHost, s),
+            hipCheck(hipMemcpyAsync(scratch.host<uint8_t>() + kResultAt, resultDev, sizeof(cart_ego_result), hipMemcpyDeviceToHost, s),
                      "hipMemcpyAsync of the loop's relative pose");
-            hipCheck(hipStreamSynchronize(s), "hipStreamSynchronize");
+            scratch.wait();
             cart_ego_result rel;
             std::memcpy(&rel, h + kResultAt, sizeof(rel));
             if (rel.status == 1 && rel.n_inliers >= options.minInliers) {
@@ -155,7 +134,7 @@ system_data_t LoopClosureModule::runInternal(System &, SystemRunData &data) {
         if (cart_place_insert(db, left.descriptors.ptr<uint8_t>(), left.descriptors.step, left.deviceKeypoints(), landmarks->landmarks.ptr<double>(), left.deviceCount(),
                               data.id, &slot, s) != 0)
             failAbi("cart_place_insert");
-        hipCheck(hipStreamSynchronize(s), "hipStreamSynchronize");   // the frame's buffers may be released once the module returns
+        scratch.wait();   // the frame's buffers may be released once the module returns
         keyframes[slot].id = data.id;
         std::memcpy(keyframes[slot].pose, pose->pose, sizeof(pose->pose));
     }

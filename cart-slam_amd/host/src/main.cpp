@@ -29,6 +29,19 @@
 #include "cartslam_amd/modules/planeseg.hpp"
 #include "cartslam_amd/modules/posegraph.hpp"
 
+namespace {
+// --dump: <dir>/<id>_<name>.bin gets `bytes` bytes; what a record has beyond its first part is appended to the returned file
+void append(std::ofstream &o, const void *p, size_t bytes) {
+    if (bytes) o.write(static_cast<const char *>(p), (std::streamsize)bytes);
+}
+std::ofstream writeBin(const std::string &dir, int id, const std::string &name, const void *p, size_t bytes) {
+    std::ofstream o(dir + "/" + std::to_string(id) + "_" + name + ".bin", std::ios::binary);
+    append(o, p, bytes);
+    return o;
+}
+void writeBin(const std::string &dir, int id, const std::string &name, const std::vector<uint8_t> &tight) { writeBin(dir, id, name, tight.data(), tight.size()); }
+}  // namespace
+
 int main(int argc, char **argv) {
     if (argc < 3) {
         std::cerr << "Usage: " << argv[0] << " <data source config file> <module config file> [--frames N] [--dump DIR]\n";
@@ -75,121 +88,101 @@ int main(int argc, char **argv) {
                 try { run = system->getRunById((uint32_t)id); } catch (const std::exception &) { continue; }  // evicted (retention ring)
                 if (run->hasData(CARTSLAM_KEY_SUPERPIXELS_MAX_LABEL)) {
                     const cart::contour::label_t mx = *run->getData<cart::contour::label_t>(CARTSLAM_KEY_SUPERPIXELS_MAX_LABEL);
-                    std::ofstream o(dump + "/" + std::to_string(id) + "_" + CARTSLAM_KEY_SUPERPIXELS_MAX_LABEL + ".bin", std::ios::binary);
-                    o.write(reinterpret_cast<const char *>(&mx), sizeof(mx));
+                    writeBin(dump, id, CARTSLAM_KEY_SUPERPIXELS_MAX_LABEL, &mx, sizeof(mx));
                 }
                 if (run->hasData(CARTSLAM_KEY_PLANES_EQ)) {   // planes f64 [N][4], assignments u64 [max_label + 1]
                     auto pf = run->getData<cart::plane_fit_data_t>(CARTSLAM_KEY_PLANES_EQ);
-                    std::ofstream p(dump + "/" + std::to_string(id) + "_" + CARTSLAM_KEY_PLANES_EQ + "_planes.bin", std::ios::binary);
-                    if (!pf->planes.empty()) p.write(reinterpret_cast<const char *>(pf->planes.data()), (std::streamsize)(pf->planes.size() * sizeof(cart::Vec4d)));
+                    writeBin(dump, id, CARTSLAM_KEY_PLANES_EQ "_planes", pf->planes.data(), pf->planes.size() * sizeof(cart::Vec4d));
                     std::vector<uint64_t> as(pf->planeAssignments.begin(), pf->planeAssignments.end());
-                    std::ofstream a(dump + "/" + std::to_string(id) + "_" + CARTSLAM_KEY_PLANES_EQ + "_assignments.bin", std::ios::binary);
-                    a.write(reinterpret_cast<const char *>(as.data()), (std::streamsize)(as.size() * sizeof(uint64_t)));
+                    writeBin(dump, id, CARTSLAM_KEY_PLANES_EQ "_assignments", as.data(), as.size() * sizeof(uint64_t));
                 }
                 if (run->hasData(CARTSLAM_KEY_FEATURES)) {   // keypoints: 28-byte cv::KeyPoint records; descriptors: n x 32 bytes
                     auto f = run->getData<std::pair<cart::ImageFeatures, cart::ImageFeatures>>(CARTSLAM_KEY_FEATURES);
                     const std::pair<const char *, const cart::ImageFeatures *> sides[] = {{"left", &f->first}, {"right", &f->second}};
                     for (const auto &side : sides) {
-                        const std::string base = dump + "/" + std::to_string(id) + "_" + CARTSLAM_KEY_FEATURES + "_" + side.first;
-                        std::ofstream k(base + "_keypoints.bin", std::ios::binary);
-                        k.write(reinterpret_cast<const char *>(side.second->keypoints.data()), (std::streamsize)(side.second->keypoints.size() * sizeof(cart::KeyPoint)));
+                        const std::string base = std::string(CARTSLAM_KEY_FEATURES) + "_" + side.first;
+                        writeBin(dump, id, base + "_keypoints", side.second->keypoints.data(), side.second->keypoints.size() * sizeof(cart::KeyPoint));
                         std::vector<uint8_t> d((size_t)side.second->descriptors.rows * CART_ORB_DESCRIPTOR_BYTES);
                         if (!d.empty()) side.second->descriptors.download(d.data(), CART_ORB_DESCRIPTOR_BYTES);
-                        std::ofstream o(base + "_descriptors.bin", std::ios::binary);
-                        o.write(reinterpret_cast<const char *>(d.data()), (std::streamsize)d.size());
+                        writeBin(dump, id, base + "_descriptors", d);
                     }
                 }
                 if (run->hasData(CARTSLAM_KEY_FEATURE_MATCHES)) {   // 16-byte cart_match records; an empty list gives an empty file
                     auto fm = run->getData<cart::FeatureMatches>(CARTSLAM_KEY_FEATURE_MATCHES);
                     const std::pair<const char *, const std::vector<cart::FeatureMatch> *> lists[] = {{"stereo", &fm->stereo}, {"temporal", &fm->temporal}};
-                    for (const auto &list : lists) {
-                        std::ofstream o(dump + "/" + std::to_string(id) + "_" + CARTSLAM_KEY_FEATURE_MATCHES + "_" + list.first + ".bin", std::ios::binary);
-                        o.write(reinterpret_cast<const char *>(list.second->data()), (std::streamsize)(list.second->size() * sizeof(cart::FeatureMatch)));
-                    }
+                    for (const auto &list : lists)
+                        writeBin(dump, id, std::string(CARTSLAM_KEY_FEATURE_MATCHES) + "_" + list.first, list.second->data(), list.second->size() * sizeof(cart::FeatureMatch));
                 }
                 if (run->hasData(CARTSLAM_KEY_EGO_MOTION)) {   // the 120-byte cart_ego_result, then the pose as 12 doubles
                     auto ego = run->getData<cart::EgoMotion>(CARTSLAM_KEY_EGO_MOTION);
-                    std::ofstream o(dump + "/" + std::to_string(id) + "_" + CARTSLAM_KEY_EGO_MOTION + ".bin", std::ios::binary);
-                    o.write(reinterpret_cast<const char *>(&ego->result), sizeof(ego->result));
-                    o.write(reinterpret_cast<const char *>(ego->pose), sizeof(ego->pose));
+                    std::ofstream o = writeBin(dump, id, CARTSLAM_KEY_EGO_MOTION, &ego->result, sizeof(ego->result));
+                    append(o, ego->pose, sizeof(ego->pose));
                 }
                 if (run->hasData(CARTSLAM_KEY_DENSE_EGO)) {   // the 136-byte cart_dense_ego_result, then the chained pose as 12 doubles
                     auto dense = run->getData<cart_dense_ego_result>(CARTSLAM_KEY_DENSE_EGO_RESULT);
                     auto chained = run->getData<cart::EgoMotion>(CARTSLAM_KEY_DENSE_EGO);
-                    std::ofstream o(dump + "/" + std::to_string(id) + "_" + CARTSLAM_KEY_DENSE_EGO + ".bin", std::ios::binary);
-                    o.write(reinterpret_cast<const char *>(dense.get()), sizeof(*dense));
-                    o.write(reinterpret_cast<const char *>(chained->pose), sizeof(chained->pose));
+                    std::ofstream o = writeBin(dump, id, CARTSLAM_KEY_DENSE_EGO, dense.get(), sizeof(*dense));
+                    append(o, chained->pose, sizeof(chained->pose));
                 }
                 if (run->hasData(CARTSLAM_KEY_LOOP_CLOSURE)) {   // the 336-byte LoopClosure record
                     auto loop = run->getData<cart::LoopClosure>(CARTSLAM_KEY_LOOP_CLOSURE);
-                    std::ofstream o(dump + "/" + std::to_string(id) + "_" + CARTSLAM_KEY_LOOP_CLOSURE + ".bin", std::ios::binary);
-                    o.write(reinterpret_cast<const char *>(loop.get()), sizeof(*loop));
+                    writeBin(dump, id, CARTSLAM_KEY_LOOP_CLOSURE, loop.get(), sizeof(*loop));
                 }
                 if (run->hasData(CARTSLAM_KEY_POSE_GRAPH)) {   // the 48-byte PoseGraphRecord, then the corrected pose as 12 doubles; every node's estimate on a frame that optimised
                     auto record = run->getData<cart::PoseGraphRecord>(CARTSLAM_KEY_POSE_GRAPH_RESULT);
                     auto corrected = run->getData<cart::EgoMotion>(CARTSLAM_KEY_POSE_GRAPH);
-                    std::ofstream o(dump + "/" + std::to_string(id) + "_" + CARTSLAM_KEY_POSE_GRAPH + ".bin", std::ios::binary);
-                    o.write(reinterpret_cast<const char *>(record.get()), sizeof(*record));
-                    o.write(reinterpret_cast<const char *>(corrected->pose), sizeof(corrected->pose));
+                    std::ofstream o = writeBin(dump, id, CARTSLAM_KEY_POSE_GRAPH, record.get(), sizeof(*record));
+                    append(o, corrected->pose, sizeof(corrected->pose));
                     auto nodes = run->getData<std::vector<double>>(CARTSLAM_KEY_POSE_GRAPH_NODES);
-                    if (!nodes->empty()) {
-                        std::ofstream n(dump + "/" + std::to_string(id) + "_" + CARTSLAM_KEY_POSE_GRAPH + "_nodes.bin", std::ios::binary);
-                        n.write(reinterpret_cast<const char *>(nodes->data()), (std::streamsize)(nodes->size() * sizeof(double)));
-                    }
+                    if (!nodes->empty()) writeBin(dump, id, CARTSLAM_KEY_POSE_GRAPH "_nodes", nodes->data(), nodes->size() * sizeof(double));
                 }
                 if (run->hasData(CARTSLAM_KEY_PLANE_MAP)) {   // int64 ox, oz; int32 Nx, Nz; double cell_size; the 16-byte cells; the u8 classes
                     auto pm = run->getData<cart::PlaneMap>(CARTSLAM_KEY_PLANE_MAP);
-                    std::ofstream o(dump + "/" + std::to_string(id) + "_" + CARTSLAM_KEY_PLANE_MAP + ".bin", std::ios::binary);
                     const int64_t origin[2] = {pm->originX, pm->originZ};
                     const int32_t shape[2] = {pm->cellsX, pm->cellsZ};
-                    o.write(reinterpret_cast<const char *>(origin), sizeof(origin));
-                    o.write(reinterpret_cast<const char *>(shape), sizeof(shape));
-                    o.write(reinterpret_cast<const char *>(&pm->cellSize), sizeof(pm->cellSize));
-                    o.write(reinterpret_cast<const char *>(pm->cells.data()), (std::streamsize)(pm->cells.size() * sizeof(cart_plane_map_cell)));
+                    std::ofstream o = writeBin(dump, id, CARTSLAM_KEY_PLANE_MAP, origin, sizeof(origin));
+                    append(o, shape, sizeof(shape));
+                    append(o, &pm->cellSize, sizeof(pm->cellSize));
+                    append(o, pm->cells.data(), pm->cells.size() * sizeof(cart_plane_map_cell));
                     const auto classes = pm->classes.downloadTight();
-                    o.write(reinterpret_cast<const char *>(classes.data()), (std::streamsize)classes.size());
+                    append(o, classes.data(), classes.size());
                 }
                 if (run->hasData(CARTSLAM_KEY_MOTION)) {   // int32 width, height; the filtered labels, the raw labels, the residual records
                     auto labels = run->getData<cart::image_t>(CARTSLAM_KEY_MOTION);
-                    std::ofstream o(dump + "/" + std::to_string(id) + "_" + CARTSLAM_KEY_MOTION + ".bin", std::ios::binary);
                     const int32_t shape[2] = {labels->cols, labels->rows};
-                    o.write(reinterpret_cast<const char *>(shape), sizeof(shape));
+                    std::ofstream o = writeBin(dump, id, CARTSLAM_KEY_MOTION, shape, sizeof(shape));
                     for (const char *k : {CARTSLAM_KEY_MOTION, CARTSLAM_KEY_MOTION_UNSMOOTHED, CARTSLAM_KEY_MOTION_RESIDUAL}) {
                         const auto bytes = run->getData<cart::image_t>(k)->downloadTight();
-                        o.write(reinterpret_cast<const char *>(bytes.data()), (std::streamsize)bytes.size());
+                        append(o, bytes.data(), bytes.size());
                     }
                 }
                 if (run->hasData(CARTSLAM_KEY_DISPARITY_FUSED)) {   // int32 width, height; fused (int16), age, source (u8); the five int32 counts
                     auto fused = run->getData<cart::image_t>(CARTSLAM_KEY_DISPARITY_FUSED);
-                    std::ofstream o(dump + "/" + std::to_string(id) + "_" + CARTSLAM_KEY_DISPARITY_FUSED + ".bin", std::ios::binary);
                     const int32_t shape[2] = {fused->cols, fused->rows};
-                    o.write(reinterpret_cast<const char *>(shape), sizeof(shape));
+                    std::ofstream o = writeBin(dump, id, CARTSLAM_KEY_DISPARITY_FUSED, shape, sizeof(shape));
                     for (const char *k : {CARTSLAM_KEY_DISPARITY_FUSED, CARTSLAM_KEY_DISPARITY_AGE, CARTSLAM_KEY_DISPARITY_SOURCE}) {
                         const auto bytes = run->getData<cart::image_t>(k)->downloadTight();
-                        o.write(reinterpret_cast<const char *>(bytes.data()), (std::streamsize)bytes.size());
+                        append(o, bytes.data(), bytes.size());
                     }
                     auto counts = run->getData<cart::FusionCounts>(CARTSLAM_KEY_DISPARITY_FUSION_COUNTS);
-                    o.write(reinterpret_cast<const char *>(counts->pixels), sizeof(counts->pixels));
+                    append(o, counts->pixels, sizeof(counts->pixels));
                 }
                 if (run->hasData(CARTSLAM_KEY_PLANES_EQ_LABEL_PLANES)) {   // f64 [max_label + 1][4]
                     auto lp = run->getData<std::vector<cart::Vec4d>>(CARTSLAM_KEY_PLANES_EQ_LABEL_PLANES);
-                    std::ofstream p(dump + "/" + std::to_string(id) + "_" + CARTSLAM_KEY_PLANES_EQ_LABEL_PLANES + ".bin", std::ios::binary);
-                    p.write(reinterpret_cast<const char *>(lp->data()), (std::streamsize)(lp->size() * sizeof(cart::Vec4d)));
+                    writeBin(dump, id, CARTSLAM_KEY_PLANES_EQ_LABEL_PLANES, lp->data(), lp->size() * sizeof(cart::Vec4d));
                 }
                 for (const char *k : keys) {
                     if (!run->hasData(k)) continue;
                     auto img = run->getData<cart::image_t>(k);
                     if (!img) continue;  // e.g. "optflow" of the first frame (optflow.cpp:126-128)
-                    auto bytes = img->downloadTight();
-                    std::ofstream o(dump + "/" + std::to_string(id) + "_" + k + ".bin", std::ios::binary);
-                    o.write(reinterpret_cast<const char *>(bytes.data()), (std::streamsize)bytes.size());
+                    writeBin(dump, id, k, img->downloadTight());
                 }
             }
         }
         if (!dump.empty()) {
             std::ofstream q(dump + "/Q.bin", std::ios::binary);
             const cart::CameraIntrinsics K = dataSource->getCameraIntrinsics();
-            q.write(reinterpret_cast<const char *>(K.Q), sizeof(K.Q));
+            append(q, K.Q, sizeof(K.Q));
         }
         std::cout << "frames " << frames << " failed " << failed;
         for (const auto &m : system->getModules())

@@ -1,8 +1,6 @@
 // motionseg.cpp -- MotionSegModule (cartslam_amd/modules/motionseg.hpp): motion segmentation from flow, disparity and ego-motion, spec DESIGN.md S25.
 #include "cartslam_amd/modules/motionseg.hpp"
 
-#include <hip/hip_runtime_api.h>
-
 #include <cmath>
 #include <cstring>
 #include <vector>
@@ -10,28 +8,16 @@
 #include "cartslam_amd/modules/disparity.hpp"
 #include "cartslam_amd/modules/egomotion.hpp"
 #include "cartslam_amd/modules/planeseg.hpp"
+#include "module_support.hpp"
 
 namespace cart {
-namespace {
-[[noreturn]] void failAbi(const char *what) { throw std::runtime_error(std::string(what) + ": " + cart_last_error(nullptr)); }
-void hipCheck(hipError_t e, const char *what) {
-    if (e != hipSuccess) throw std::runtime_error(std::string(what) + ": " + hipGetErrorString(e));
-}
-}  // namespace
-
 MotionSegModule::MotionSegModule(const MotionSegOptions &options) : SyncWrapperSystemModule("MotionSeg"), options(options) {
-    const auto positive = [](double v) { return v > 0 && std::isfinite(v); };
-    if (!positive(options.fx)) throw std::invalid_argument("fx must be a positive number (a source without calibration needs the camera keys)");
-    if (!positive(options.fy)) throw std::invalid_argument("fy must be a positive number");
-    if (!std::isfinite(options.cx)) throw std::invalid_argument("cx must be finite");
-    if (!std::isfinite(options.cy)) throw std::invalid_argument("cy must be finite");
-    if (!positive(options.baseline)) throw std::invalid_argument("baseline must be a positive number");
+    checkCamera(options);
     // the library's own checks, without a device: everything valid gets as far as the missing engine
-    const cart_ego_camera cam{options.fx, options.fy, options.cx, options.cy, options.baseline};
+    const cart_ego_camera cam = cameraOf(options);
     const cart_motion_params p{options.minDisparity, options.flowThreshold, options.disparityThreshold, options.radius, options.supportPercent};
-    static const double identity[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
-    (void)cart_motion_segment(nullptr, &cam, identity, &p, nullptr, 0, nullptr, 0, nullptr, 0, 1, 1, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, 0, nullptr);
-    if (std::strcmp(cart_last_error(nullptr), "bad arguments") != 0) throw std::invalid_argument(cart_last_error(nullptr));
+    (void)cart_motion_segment(nullptr, &cam, kIdentityPose, &p, nullptr, 0, nullptr, 0, nullptr, 0, 1, 1, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, 0, nullptr);
+    requireLibraryAccepts();
     this->requiresData.push_back(module_dependency_t(CARTSLAM_KEY_DISPARITY));
     this->requiresData.push_back(module_dependency_t(CARTSLAM_KEY_DISPARITY, -1));
     this->requiresData.push_back(module_dependency_t(CARTSLAM_KEY_OPTFLOW));
@@ -51,13 +37,12 @@ MotionSegModule::MotionSegModule(const MotionSegOptions &options) : SyncWrapperS
 MotionSegModule::~MotionSegModule() {
     unknown.reset();
     cart_engine_destroy(engine);
-    if (stream) (void)hipStreamDestroy(static_cast<hipStream_t>(stream));
 }
 
 void MotionSegModule::label(const Outputs &out) {   // the shapes disparity_planeseg publishes its own tables in
     static_assert(sizeof(cart_component) == 7 * sizeof(int32_t), "table rows are 7 x int32");
     if (cart_plane_ccl_table(engine, 1, out.labels->ptr<uint8_t>(), out.labels->step, 0, out.components->ptr<int32_t>(), out.components->step, 0,
-                             out.componentTable->ptr<cart_component>(), CARTSLAM_PLANE_COMPONENT_TABLE_ROWS, out.componentCount->ptr<int32_t>(), stream) != 0)
+                             out.componentTable->ptr<cart_component>(), CARTSLAM_PLANE_COMPONENT_TABLE_ROWS, out.componentCount->ptr<int32_t>(), scratch.stream()) != 0)
         failAbi("cart_plane_ccl_table");
 }
 
@@ -69,18 +54,15 @@ system_data_t MotionSegModule::runInternal(System &, SystemRunData &data) {
     std::shared_ptr<image_t> planes;
     if (options.planes) {
         planes = data.getData<image_t>(CARTSLAM_KEY_PLANES);
-        if (planes->empty() || planes->type() != CV_8UC1 || planes->rows != rows || planes->cols != cols)
-            throw std::runtime_error("MotionSegModule: planes must be a CV_8UC1 image of the disparity's size");
+        requireImage(planes, CV_8UC1, rows, cols, "MotionSegModule: planes must be a CV_8UC1 image of the disparity's size");
     }
     const bool estimate = data.id > 1 && ego->result.status != 0;
     std::shared_ptr<image_t> previous, flow;
     if (estimate) {
         previous = data.getRelativeRun(-1)->getData<image_t>(CARTSLAM_KEY_DISPARITY);
         flow = data.getData<image_t>(CARTSLAM_KEY_OPTFLOW);
-        if (!previous || previous->type() != CV_16SC1 || previous->rows != rows || previous->cols != cols)
-            throw std::runtime_error("MotionSegModule: the previous frame's disparity is missing or of another size");
-        if (!flow || flow->type() != CV_16SC2 || flow->rows != rows || flow->cols != cols)
-            throw std::runtime_error("MotionSegModule: optflow must be a CV_16SC2 image of the disparity's size");
+        requireImage(previous, CV_16SC1, rows, cols, "MotionSegModule: the previous frame's disparity is missing or of another size");
+        requireImage(flow, CV_16SC2, rows, cols, "MotionSegModule: optflow must be a CV_16SC2 image of the disparity's size");
     }
     const auto make = [&] {
         Outputs o;
@@ -98,13 +80,8 @@ system_data_t MotionSegModule::runInternal(System &, SystemRunData &data) {
     std::shared_ptr<image_t> planesStatic;
     std::unique_lock<std::mutex> lock(mutex);   // the lazy creation, the shared UNKNOWN images and the enqueue; not the wait
     if (!engine) {   // the geometry only: num_disparities = paths = 0 -> no SGM workspaces
-        cart_engine_params ep;
-        cart_engine_default_params(&ep);
-        ep.width = cols; ep.height = rows; ep.num_disparities = 0; ep.paths = 0; ep.max_inflight = 1;
-        if (cart_engine_create(&ep, &engine) != 0) failAbi("cart_engine_create");
-        hipStream_t s = nullptr;
-        hipCheck(hipStreamCreateWithFlags(&s, hipStreamNonBlocking), "hipStreamCreateWithFlags");
-        stream = s;
+        engine = createPostEngine(cols, rows);
+        scratch.create();
     }
     if (!estimate) {   // frame 1, or no pose: all UNKNOWN, zero components, planes_static = planes; one set of images serves every such frame
         if (!unknown || unknown->labels->rows != rows || unknown->labels->cols != cols) {
@@ -116,7 +93,7 @@ system_data_t MotionSegModule::runInternal(System &, SystemRunData &data) {
             u->residual->upload(record.data(), (size_t)cols * 4 * sizeof(int16_t));
             if (options.components) {
                 label(*u);
-                hipCheck(hipStreamSynchronize(static_cast<hipStream_t>(stream)), "hipStreamSynchronize");
+                scratch.wait();
             }
             unknown = u;
         }
@@ -125,31 +102,28 @@ system_data_t MotionSegModule::runInternal(System &, SystemRunData &data) {
     } else {
         out = make();
         if (options.planes) planesStatic = std::make_shared<image_t>(rows, cols, CV_8UC1);
-        const cart_ego_camera cam{options.fx, options.fy, options.cx, options.cy, options.baseline};
+        const cart_ego_camera cam = cameraOf(options);
         const cart_motion_params p{options.minDisparity, options.flowThreshold, options.disparityThreshold, options.radius, options.supportPercent};
         double rel[12];
-        for (int r = 0; r < 3; ++r) {
-            for (int c = 0; c < 3; ++c) rel[4 * r + c] = ego->result.R[3 * r + c];
-            rel[4 * r + 3] = ego->result.t[r];
-        }
+        pose12(ego->result, rel);
         if (cart_motion_segment(engine, &cam, rel, &p, disparity->ptr<int16_t>(), disparity->step, previous->ptr<int16_t>(), previous->step, flow->ptr<int16_t>(),
                                 flow->step, cols, rows, out.residual->ptr<int16_t>(), out.residual->step, out.raw->ptr<uint8_t>(), out.raw->step,
                                 out.labels->ptr<uint8_t>(), out.labels->step, planes ? planes->ptr<uint8_t>() : nullptr, planes ? planes->step : 0,
-                                planesStatic ? planesStatic->ptr<uint8_t>() : nullptr, planesStatic ? planesStatic->step : 0, stream) != 0)
+                                planesStatic ? planesStatic->ptr<uint8_t>() : nullptr, planesStatic ? planesStatic->step : 0, scratch.stream()) != 0)
             failAbi("cart_motion_segment");
         if (options.components) label(out);
         lock.unlock();   // the next frame may enqueue behind this one while this one waits
-        hipCheck(hipStreamSynchronize(static_cast<hipStream_t>(stream)), "hipStreamSynchronize");   // the frame's only blocking synchronisation
+        scratch.wait();   // the frame's only blocking synchronisation
     }
     system_data_t result;
-    result.push_back(std::make_pair(std::string(CARTSLAM_KEY_MOTION), std::shared_ptr<void>(out.labels)));
-    result.push_back(std::make_pair(std::string(CARTSLAM_KEY_MOTION_UNSMOOTHED), std::shared_ptr<void>(out.raw)));
-    result.push_back(std::make_pair(std::string(CARTSLAM_KEY_MOTION_RESIDUAL), std::shared_ptr<void>(out.residual)));
-    if (options.planes) result.push_back(std::make_pair(std::string(CARTSLAM_KEY_PLANES_STATIC), std::shared_ptr<void>(planesStatic)));
+    result.push_back(MODULE_PAIR(CARTSLAM_KEY_MOTION, out.labels));
+    result.push_back(MODULE_PAIR(CARTSLAM_KEY_MOTION_UNSMOOTHED, out.raw));
+    result.push_back(MODULE_PAIR(CARTSLAM_KEY_MOTION_RESIDUAL, out.residual));
+    if (options.planes) result.push_back(MODULE_PAIR(CARTSLAM_KEY_PLANES_STATIC, planesStatic));
     if (options.components) {
-        result.push_back(std::make_pair(std::string(CARTSLAM_KEY_MOTION_COMPONENTS), std::shared_ptr<void>(out.components)));
-        result.push_back(std::make_pair(std::string(CARTSLAM_KEY_MOTION_COMPONENT_TABLE), std::shared_ptr<void>(out.componentTable)));
-        result.push_back(std::make_pair(std::string(CARTSLAM_KEY_MOTION_COMPONENT_COUNT), std::shared_ptr<void>(out.componentCount)));
+        result.push_back(MODULE_PAIR(CARTSLAM_KEY_MOTION_COMPONENTS, out.components));
+        result.push_back(MODULE_PAIR(CARTSLAM_KEY_MOTION_COMPONENT_TABLE, out.componentTable));
+        result.push_back(MODULE_PAIR(CARTSLAM_KEY_MOTION_COMPONENT_COUNT, out.componentCount));
     }
     return result;
 }

@@ -1,21 +1,16 @@
 // posegraph.cpp -- PoseGraphModule (cartslam_amd/modules/posegraph.hpp): pose-graph optimisation over keyframes, spec DESIGN.md S29.
 #include "cartslam_amd/modules/posegraph.hpp"
 
-#include <hip/hip_runtime_api.h>
-
 #include <algorithm>
 #include <cmath>
 #include <cstring>
 
 #include "cartslam_amd/modules/denseego.hpp"
 #include "cartslam_amd/modules/loopclosure.hpp"
+#include "module_support.hpp"
 
 namespace cart {
 namespace {
-[[noreturn]] void failAbi(const char *what) { throw std::runtime_error(std::string(what) + ": " + cart_last_error(nullptr)); }
-void hipCheck(hipError_t e, const char *what) {
-    if (e != hipSuccess) throw std::runtime_error(std::string(what) + ": " + hipGetErrorString(e));
-}
 constexpr size_t kPosesAt = sizeof(cart_pose_graph_result);   // the module's buffers: the result record, then 12 doubles per node
 
 // (R | t) 3 x 4 in row order: inv = (R^T, -(R^T t)), and the product, every sum left to right
@@ -43,14 +38,13 @@ PoseGraphModule::PoseGraphModule(const PoseGraphOptions &options) : SyncWrapperS
     // the library's own checks, without a device: everything valid gets as far as the missing engine / object
     cart_pose_graph *none = nullptr;
     (void)cart_pose_graph_create(nullptr, options.maxNodes, options.maxLoops, &none);
-    if (std::strcmp(cart_last_error(nullptr), "bad arguments") != 0) throw std::invalid_argument(cart_last_error(nullptr));
+    requireLibraryAccepts();
     const cart_pose_graph_params p{options.iterations};
     (void)cart_pose_graph_optimize(nullptr, &p, nullptr, nullptr);
-    if (std::strcmp(cart_last_error(nullptr), "graph is NULL") != 0) throw std::invalid_argument(cart_last_error(nullptr));
-    const auto positive = [](double v) { return v > 0 && std::isfinite(v); };
-    if (!positive(options.weightRotation)) throw std::invalid_argument("weight_rotation must be a positive number");
-    if (!positive(options.weightTranslation)) throw std::invalid_argument("weight_translation must be a positive number");
-    if (!positive(options.loopWeight) || !positive(options.weightRotation * options.loopWeight) || !positive(options.weightTranslation * options.loopWeight))
+    requireLibraryAccepts("graph is NULL");
+    if (!positiveNumber(options.weightRotation)) throw std::invalid_argument("weight_rotation must be a positive number");
+    if (!positiveNumber(options.weightTranslation)) throw std::invalid_argument("weight_translation must be a positive number");
+    if (!positiveNumber(options.loopWeight) || !positiveNumber(options.weightRotation * options.loopWeight) || !positiveNumber(options.weightTranslation * options.loopWeight))
         throw std::invalid_argument("loop_weight must be a positive number that keeps both loop weights finite and above zero");
     if (options.keyframeInterval < 1) throw std::invalid_argument("keyframe_interval must be at least 1");
     if (options.loopClosureInterval > 0 && options.loopClosureInterval != options.keyframeInterval)
@@ -65,12 +59,7 @@ PoseGraphModule::PoseGraphModule(const PoseGraphOptions &options) : SyncWrapperS
     this->providesData.push_back(CARTSLAM_KEY_POSE_GRAPH_NODES);
 }
 
-PoseGraphModule::~PoseGraphModule() {
-    cart_pose_graph_destroy(graph);
-    if (dev) (void)hipFree(dev);
-    if (host) (void)hipHostFree(host);
-    if (stream) (void)hipStreamDestroy(static_cast<hipStream_t>(stream));
-}
+PoseGraphModule::~PoseGraphModule() { cart_pose_graph_destroy(graph); }
 
 system_data_t PoseGraphModule::runInternal(System &, SystemRunData &data) {
     auto source = data.getData<EgoMotion>(options.poseKey);
@@ -85,26 +74,17 @@ system_data_t PoseGraphModule::runInternal(System &, SystemRunData &data) {
     std::lock_guard<std::mutex> lock(mutex);
     if (data.id % (uint32_t)options.keyframeInterval == 0) {
         if (!graph) {   // the graph keeps the device of the engine it is made on, not the engine
-            cart_engine_params ep;
-            cart_engine_default_params(&ep);
-            ep.width = 64; ep.height = 32; ep.num_disparities = 0; ep.paths = 0; ep.max_inflight = 1;
-            cart_engine *engine = nullptr;
-            if (cart_engine_create(&ep, &engine) != 0) failAbi("cart_engine_create");
-            const int rc = cart_pose_graph_create(engine, options.maxNodes, options.maxLoops, &graph);
-            const std::string error = rc ? cart_last_error(nullptr) : "";
-            cart_engine_destroy(engine);
-            if (rc) throw std::runtime_error("cart_pose_graph_create: " + error);
-            hipStream_t s = nullptr;
-            hipCheck(hipStreamCreateWithFlags(&s, hipStreamNonBlocking), "hipStreamCreateWithFlags");
-            stream = s;
+            makeOnPostEngine(64, 32, [&](cart_engine *e) {
+                return cart_pose_graph_create(e, options.maxNodes, options.maxLoops, &graph) ? "cart_pose_graph_create" : nullptr;
+            });
+            scratch.create();
             const size_t bytes = kPosesAt + (size_t)options.maxNodes * 12 * sizeof(double);
-            hipCheck(hipMalloc(&dev, bytes), "hipMalloc");
-            hipCheck(hipHostMalloc(&host, bytes, hipHostMallocDefault), "hipHostMalloc");
+            scratch.reserve(bytes, bytes);
         }
         if ((int)nodeFrames.size() >= options.maxNodes) {
             full = 1;
         } else {
-            hipStream_t s = static_cast<hipStream_t>(stream);
+            hipStream_t s = scratch.stream();
             int32_t node = -1;
             if (cart_pose_graph_add_node(graph, source->pose, options.weightRotation, options.weightTranslation, &node, s) != 0) failAbi("cart_pose_graph_add_node");
             nodeFrames.push_back(data.id);
@@ -119,7 +99,7 @@ system_data_t PoseGraphModule::runInternal(System &, SystemRunData &data) {
                                                  options.weightTranslation * options.loopWeight, s) != 0)
                         failAbi("cart_pose_graph_add_loop");
                     const cart_pose_graph_params p{options.iterations};
-                    if (cart_pose_graph_optimize(graph, &p, static_cast<cart_pose_graph_result *>(dev), s) != 0) failAbi("cart_pose_graph_optimize");
+                    if (cart_pose_graph_optimize(graph, &p, scratch.dev<cart_pose_graph_result>(), s) != 0) failAbi("cart_pose_graph_optimize");
                     optimised = true;
                     record->loopAdded = 1;
                 } else {
@@ -128,11 +108,11 @@ system_data_t PoseGraphModule::runInternal(System &, SystemRunData &data) {
             }
             // this node's estimate, or after an optimise the result and every node's, through the pinned buffer: the frame's only synchronisation
             const int first = optimised ? 0 : node, count = optimised ? node + 1 : 1;
-            uint8_t *d = static_cast<uint8_t *>(dev), *h = static_cast<uint8_t *>(host);
+            uint8_t *d = scratch.dev<uint8_t>(), *h = scratch.host<uint8_t>();
             if (cart_pose_graph_poses(graph, first, count, reinterpret_cast<double *>(d + kPosesAt), s) != 0) failAbi("cart_pose_graph_poses");
             const size_t from = optimised ? 0 : kPosesAt, bytes = kPosesAt + (size_t)count * 12 * sizeof(double) - from;
             hipCheck(hipMemcpyAsync(h + from, d + from, bytes, hipMemcpyDeviceToHost, s), "hipMemcpyAsync of the pose graph's estimates");
-            hipCheck(hipStreamSynchronize(s), "hipStreamSynchronize");
+            scratch.wait();
             const double *estimates = reinterpret_cast<const double *>(h + kPosesAt);
             if (optimised) {
                 std::memcpy(&last, h, sizeof(last));
@@ -148,10 +128,6 @@ system_data_t PoseGraphModule::runInternal(System &, SystemRunData &data) {
     record->full = full;
     if (haveNode) carryPose(estNode, odomNode, source->pose, result->pose);
     else std::memcpy(result->pose, source->pose, sizeof(result->pose));
-    system_data_t out;
-    out.push_back(std::make_pair(std::string(CARTSLAM_KEY_POSE_GRAPH), std::shared_ptr<void>(result)));
-    out.push_back(std::make_pair(std::string(CARTSLAM_KEY_POSE_GRAPH_RESULT), std::shared_ptr<void>(record)));
-    out.push_back(std::make_pair(std::string(CARTSLAM_KEY_POSE_GRAPH_NODES), std::shared_ptr<void>(nodes)));
-    return out;
+    return MODULE_RETURN_ALL(MODULE_PAIR(CARTSLAM_KEY_POSE_GRAPH, result), MODULE_PAIR(CARTSLAM_KEY_POSE_GRAPH_RESULT, record), MODULE_PAIR(CARTSLAM_KEY_POSE_GRAPH_NODES, nodes));
 }
 }  // namespace cart

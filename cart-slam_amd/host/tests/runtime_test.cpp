@@ -11,6 +11,7 @@
 
 #include <cstring>
 
+#include "cartslam_amd/cartconfig.hpp"
 #include "cartslam_amd/cartslam.hpp"
 #include "cartslam_amd/coalescer.hpp"
 #include "cartslam_amd/modules/superpixels.hpp"
@@ -90,6 +91,25 @@ class ModuleOrdered : public SyncWrapperSystemModule {
     std::mutex m;
     std::vector<uint32_t> seen;
 };
+
+// what() of the std::invalid_argument that applying a module list to a System over a source without calibration throws;
+// "" when nothing is thrown (*count = modules constructed), "<other> ..." for any other exception
+std::string configError(const std::string &modules, size_t *count = nullptr) {
+    auto sys = std::make_shared<System>(std::make_shared<CountingSource>(0), CARTSLAM_RUN_RETENTION, 2);
+    try {
+        config::applyModuleConfigText("[" + modules + "]", sys);
+    } catch (const std::invalid_argument &e) {
+        return e.what();
+    } catch (const std::exception &e) {
+        return std::string("<other> ") + e.what();
+    }
+    if (count) *count = sys->getModules().size();
+    return "";
+}
+void checkConfigError(const std::string &modules, const std::string &expected) {
+    const std::string got = configError(modules);
+    if (got != expected) { std::printf("FAILED config [%s]: \"%s\" instead of \"%s\"\n", modules.c_str(), got.c_str(), expected.c_str()); ++failures; }
+}
 }  // namespace
 
 int main(int argc, char **argv) {
@@ -224,6 +244,43 @@ int main(int argc, char **argv) {
         for (size_t i = 1; i < ordered->seen.size(); ++i) ascending &= ordered->seen[i] == ordered->seen[i - 1] + 1;
         CHECK(ascending);
         if (hung) { std::printf("FAILED: frames behind a late id-ordered module never finished\n"); return 1; }
+    }
+    // 1e. the constructors' argument checks, without a device: every message below is what a configuration file's author reads.
+    //     The source has no calibration, so the camera comes from the keys alone.
+    {
+        const std::string fx = "\"fx\":700", fy = "\"fy\":700", cx = "\"cx\":600", cy = "\"cy\":180", baseline = "\"baseline\":0.5";
+        const auto camera = [](const std::string &a, const std::string &b, const std::string &c, const std::string &d, const std::string &e) {
+            return "," + a + "," + b + "," + c + "," + d + "," + e;
+        };
+        const std::string CAM = camera(fx, fy, cx, cy, baseline);
+        const auto module = [](const std::string &type, const std::string &keys) { return "{\"type\":\"" + type + "\"" + keys + "}"; };
+        const char *const noCamera = "fx must be a positive number (a source without calibration needs the camera keys)";
+        for (const char *type : {"ego_motion", "plane_map", "motion_seg", "dense_ego", "temporal_fusion", "loop_closure"}) {   // every copy of the camera check
+            checkConfigError(module(type, ""), noCamera);
+            checkConfigError(module(type, camera("\"fx\":1e999", fy, cx, cy, baseline)), noCamera);
+            checkConfigError(module(type, camera(fx, "\"fy\":1e999", cx, cy, baseline)), "fy must be a positive number");   // 1e999 reads as infinity
+            checkConfigError(module(type, camera(fx, fy, "\"cx\":1e999", cy, baseline)), "cx must be finite");
+            checkConfigError(module(type, camera(fx, fy, cx, "\"cy\":-1e999", baseline)), "cy must be finite");
+            checkConfigError(module(type, camera(fx, fy, cx, cy, "\"baseline\":-1")), "baseline must be a positive number");
+        }
+        checkConfigError(module("temporal_fusion", CAM + ",\"max_weight\":0"), "max_weight must be in [1, 255]");
+        checkConfigError(module("temporal_fusion", CAM + ",\"pose_key\":\"\""), "pose_key must name a blackboard pose");
+        checkConfigError(module("motion_seg", CAM + ",\"radius\":9"), "radius must be in [0, 4]");
+        checkConfigError(module("dense_ego", CAM + ",\"stride\":0"), "stride must be in [1, 16]");
+        checkConfigError(module("plane_map", CAM + ",\"cells_x\":0"), "cells_x must be a multiple of 16 in [32, 4096]");
+        checkConfigError(module("plane_map", CAM + ",\"obstacle_percent\":0"), "obstacle_percent must be in [1, 100]");
+        checkConfigError(module("loop_closure", CAM + ",\"verify\":17"), "verify must be in [0, 16]");
+        checkConfigError(module("loop_closure", CAM + ",\"capacity\":0"), "capacity must be in [1, 1024]");
+        checkConfigError(module("pose_graph", ",\"iterations\":99"), "iterations must be in [0, 16]");
+        checkConfigError(module("pose_graph", ",\"loop_weight\":0"), "loop_weight must be a positive number that keeps both loop weights finite and above zero");
+        checkConfigError(module("ego_motion", CAM + ",\"hypotheses\":0"), "hypotheses must be in [1, 1024]");
+        // all seven together: constructed and destroyed with nothing created on a device (the owners' empty state)
+        size_t count = 0;
+        const std::string all = module("ego_motion", CAM) + "," + module("plane_map", CAM) + "," + module("motion_seg", CAM) + "," + module("dense_ego", CAM) + "," +
+                                module("temporal_fusion", CAM) + "," + module("loop_closure", CAM) + "," + module("pose_graph", "");
+        const std::string got = configError(all, &count);
+        if (!got.empty()) std::printf("all seven modules: %s\n", got.c_str());
+        CHECK(got.empty() && count == 7);
     }
     // 2. the System: consumers listed before their providers, 12 frames in flight, retention 32
     const int frames = 400;
