@@ -243,6 +243,13 @@ PROTOTYPES = {
     "cart_plane_map_window": (_i, [_vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(_i)]),
     "cart_plane_map_read": (_i, [_vp, _vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _vp]),
     "cart_plane_map_classify": (_i, [_vp, _i, _i, _vp, _sz, _vp]),
+    "cart_plane_store_create": (_i, [_vp, _i, _i, _i, C.POINTER(_vp)]),
+    "cart_plane_store_destroy": (None, [_vp]),
+    "cart_plane_store_clear": (_i, [_vp]),
+    "cart_plane_store_size": (_i, [_vp, C.POINTER(_i), C.POINTER(_i)]),
+    "cart_plane_store_insert": (_i, [_vp, C.c_uint64, _vp, _sz, _vp, _sz, _i, _i, _vp]),
+    "cart_plane_store_contains": (_i, [_vp, C.c_uint64, C.POINTER(_i)]),
+    "cart_plane_map_rebuild": (_i, [_vp, _vp, C.POINTER(EgoCamera), C.POINTER(C.c_uint64), C.POINTER(C.c_double), _i, C.POINTER(C.c_double), C.POINTER(_i), _vp]),
     "cart_motion_default_params": (None, [C.POINTER(MotionParams)]),
     "cart_motion_segment": (_i, [_vp, C.POINTER(EgoCamera), C.POINTER(C.c_double), C.POINTER(MotionParams), _vp, _sz, _vp, _sz, _vp, _sz, _i, _i,
                                  _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp]),

@@ -984,6 +984,61 @@ class PlaneMap(_DeviceObject):
     def clear(self):
         self._check(self._lib.cart_plane_map_clear(self._h), "cart_plane_map_clear")
 
+    def rebuild(self, store, ids, poses, window_pose, raw=False):
+        """Spec S30: empties the window of `window_pose` (12 numbers, host) and votes every frame of the PlaneStore
+        `store` that `ids` names, entry k through poses[k] (12 numbers each, host).  Ids the store does not hold are skipped.  Ids and
+        poses are host data either way; `raw` is accepted for symmetry with update().  -> ((ox, oz), used)."""
+        if not isinstance(store, PlaneStore):
+            raise EngineError("store must be a PlaneStore")
+        ids = [int(i) for i in ids]
+        flat = np.ascontiguousarray(np.asarray(poses, np.float64).reshape(-1))
+        if len(flat) != 12 * len(ids):
+            raise EngineError("poses must hold 12 numbers for every id")
+        used = C.c_int(0)
+        self._check(self._lib.cart_plane_map_rebuild(self._h, store._h, C.byref(self.camera), (C.c_uint64 * max(len(ids), 1))(*ids),
+                                                     (C.c_double * max(len(flat), 1))(*flat.tolist()), len(ids), _pose12(window_pose), C.byref(used),
+                                                     _stream_ptr()), "cart_plane_map_rebuild")
+        return self.window()[:2], used.value
+
+
+class PlaneStore(_DeviceObject):
+    """Device-resident ring of keyframe images for PlaneMap.rebuild (cart_plane_store_* in the C ABI, spec S30 in DESIGN.md 7.12):
+    up to `capacity` frames of exactly width x height, the disparity (int16 x16) and the labels (uint8) copied verbatim."""
+    _name = "plane_store"
+
+    def __init__(self, engine, width, height, capacity):
+        self.width, self.height, self.capacity = int(width), int(height), int(capacity)
+        super().__init__(engine, self.width, self.height, self.capacity)
+
+    def insert(self, frame_id, disp, planes, raw=False):
+        """disp int16 [h, w] (x16) and planes uint8 [h, w] under frame_id; raw=True takes the two device tensors as they are (rows
+        may be pitched).  The oldest frame leaves a full store."""
+        import torch
+        if not raw:
+            disp, planes = _to_device(disp, torch.int16, via_host=True), _to_device(planes, torch.uint8, via_host=True)
+        if not isinstance(disp, torch.Tensor) or not isinstance(planes, torch.Tensor) or disp.dtype != torch.int16 or planes.dtype != torch.uint8:
+            raise EngineError("disp must be an int16 and planes a uint8 device tensor")
+        if disp.dim() != 2 or planes.shape != disp.shape:
+            raise EngineError("disp and planes must be [h, w] images of one size")
+        images = _pitched(disp, 1) + _pitched(planes, 1)
+        self._check(self._lib.cart_plane_store_insert(self._h, C.c_uint64(int(frame_id)), *images, int(disp.shape[1]), int(disp.shape[0]), _stream_ptr()),
+                    "cart_plane_store_insert")
+
+    def contains(self, frame_id):
+        """-> whether frame_id is held (host getter)."""
+        slot = C.c_int(-1)
+        self._check(self._lib.cart_plane_store_contains(self._h, C.c_uint64(int(frame_id)), C.byref(slot)), "cart_plane_store_contains")
+        return slot.value >= 0
+
+    def size(self):
+        """-> (frames held, capacity) (host getter)."""
+        frames, capacity = C.c_int(0), C.c_int(0)
+        self._check(self._lib.cart_plane_store_size(self._h, C.byref(frames), C.byref(capacity)), "cart_plane_store_size")
+        return frames.value, capacity.value
+
+    def clear(self):
+        self._check(self._lib.cart_plane_store_clear(self._h), "cart_plane_store_clear")
+
 
 def motion_params(**fields):
     """cart_motion_default_params (spec S25) with the given fields replaced."""

@@ -326,6 +326,20 @@ struct PlaneMapVoteArgs {
 // empties the window rectangle [rx0, rx0 + rw) x [rz0, rz0 + rh)
 void launch_plane_map_clear(const PlaneMapGrid &grid, int rx0, int rw, int rz0, int rh, hipStream_t s);
 void launch_plane_map_vote(const PlaneMapVoteArgs &a, hipStream_t s);
+// ---- rebuilding the map from stored keyframes (planemap_kernels.hip) ----
+constexpr int kRevoteStrip = 32;    // image rows one lane of the re-vote kernel walks with one open run: a multiple of kMapStrip
+constexpr int kRevoteMaxEntries = 4096;
+static_assert(kRevoteStrip % kMapStrip == 0, "the re-vote kernel loads kMapStrip rows at a time");
+struct PlaneRevoteRecord {             // one entry of a rebuild, written by the call into the store's device array
+    int32_t slot, pad;
+    double pose[12];
+};
+static_assert(sizeof(PlaneRevoteRecord) == 104, "PlaneRevoteRecord layout (DESIGN.md S30)");
+// pitched disparity + labels -> the packed planes of one store slot
+void launch_plane_store_insert(const int16_t *disp, size_t disp_step, const uint8_t *planes, size_t planes_step, int16_t *dst_disp, uint8_t *dst_planes, int w, int h,
+                               hipStream_t s);
+// a.disp / a.planes = the store's packed planes [slot][h][w] (the steps are not read), a.pose is not read: records[k] names entry k's slot and pose
+void launch_plane_map_revote(const PlaneMapVoteArgs &a, const PlaneRevoteRecord *records, int entries, hipStream_t s);
 // empty != 0: the map has no window, every class is UNKNOWN
 void launch_plane_map_classify(const PlaneMapGrid &grid, int empty, unsigned min_votes, unsigned percent, uint8_t *out, size_t out_step, hipStream_t s);
 // ---- motion segmentation (motion_kernels.hip) ----

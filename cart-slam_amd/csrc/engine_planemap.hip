@@ -1,5 +1,6 @@
 // engine_planemap.hip -- C ABI of the world-frame bird's-eye plane map (include/cart_engine.h): argument checks, the
-// window arithmetic (host, int64) and the cart_plane_map device object.
+// window arithmetic (host, int64) and the cart_plane_map device object; and of its rebuild from stored keyframes (S30): the
+// cart_plane_store ring of keyframe images and cart_plane_map_rebuild.
 
 #include "engine_host.h"
 
@@ -14,6 +15,28 @@ struct cart_plane_map : DeviceObject {
     cart_plane_map_cell *cells = nullptr;   // [nz][nx], toroidal (engine_internal.h, PlaneMapGrid)
     bool valid = false;                     // a window exists (guarded by mu)
     int64_t ox = 0, oz = 0;                 // its origin in absolute cells
+};
+
+// S30: a ring of `capacity` frames of exactly w x h.  The id table and the insertion count are host state (guarded by mu).
+struct cart_plane_store : DeviceObject {
+    using DeviceObject::DeviceObject;
+    int w = 0, h = 0, capacity = 0;
+    int16_t *disp = nullptr;             // [capacity][h][w], packed
+    uint8_t *planes = nullptr;           // [capacity][h][w], packed
+    PlaneRevoteRecord *records = nullptr;          // device [kRevoteMaxEntries]: the entries of the rebuild in flight
+    PlaneRevoteRecord *staging = nullptr;          // pinned host [kRevoteMaxEntries]: what the upload reads
+    hipEvent_t uploaded = nullptr;       // recorded after every upload: the next rebuild waits for it before it rewrites `staging`
+    bool staged = false;
+    std::vector<uint64_t> ids;           // [capacity]: the frame_id of every slot
+    uint64_t inserted = 0;               // since create / clear: insertion n went to slot n mod capacity
+    int find(uint64_t id) const {        // newest first, so a repeated id names its latest insertion; -1 = not stored
+        const uint64_t live = std::min<uint64_t>(inserted, (uint64_t)capacity);
+        for (uint64_t k = 1; k <= live; ++k) {
+            const int slot = (int)((inserted - k) % (uint64_t)capacity);
+            if (ids[slot] == id) return slot;
+        }
+        return -1;
+    }
 };
 
 void cart_plane_map_default_params(cart_plane_map_params *p) {
@@ -88,6 +111,132 @@ int cart_plane_map_update(cart_plane_map *m, const cart_ego_camera *cam, const d
     a.disp = disp; a.disp_step = disp_step; a.planes = planes; a.planes_step = planes_step; a.w = w; a.h = h;
     launch_plane_map_vote(a, stream);
     HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// ---- S30: the keyframe image store and the rebuild ----
+int cart_plane_store_create(cart_engine *e, int width, int height, int capacity, cart_plane_store **out) {
+    if (check_frame_size(width, height)) return -1;
+    if (capacity < 1 || capacity > 1024) return fail("capacity must be in [1, 1024]");
+    if (!e || !out) return fail("bad arguments");
+    HIP_TRY(hipSetDevice(e->params.device_id));
+    cart_plane_store *s = new (std::nothrow) cart_plane_store(e);
+    if (!s) return fail("out of host memory");
+    s->w = width; s->h = height; s->capacity = capacity;
+    const size_t plane = (size_t)width * height;
+    uint8_t *images = nullptr;   // one allocation: the int16 planes, then the u8 planes
+    if (s->alloc(&images, 3 * plane * (size_t)capacity) || s->alloc(&s->records, sizeof(PlaneRevoteRecord) * kRevoteMaxEntries) || s->create_event() ||
+        hipHostMalloc(reinterpret_cast<void **>(&s->staging), sizeof(PlaneRevoteRecord) * kRevoteMaxEntries, hipHostMallocDefault) != hipSuccess ||
+        hipEventCreateWithFlags(&s->uploaded, hipEventDisableTiming) != hipSuccess) {
+        cart_plane_store_destroy(s);
+        return fail("allocating the plane store failed");
+    }
+    s->disp = reinterpret_cast<int16_t *>(images);
+    s->planes = images + 2 * plane * (size_t)capacity;
+    s->ids.assign((size_t)capacity, 0);
+    *out = s;
+    return 0;
+}
+
+void cart_plane_store_destroy(cart_plane_store *s) {
+    if (!s) return;
+    (void)hipSetDevice(s->device_id);
+    (void)hipDeviceSynchronize();
+    if (s->staging) (void)hipHostFree(s->staging);
+    if (s->uploaded) (void)hipEventDestroy(s->uploaded);
+    destroy_object(s);
+}
+
+int cart_plane_store_clear(cart_plane_store *s) {
+    if (!s) return fail("store is NULL");
+    std::lock_guard<std::mutex> lk(s->mu);
+    s->inserted = 0;
+    return 0;
+}
+
+int cart_plane_store_size(cart_plane_store *s, int *frames, int *capacity) {
+    if (!s) return fail("store is NULL");
+    std::lock_guard<std::mutex> lk(s->mu);
+    if (frames) *frames = (int)std::min<uint64_t>(s->inserted, (uint64_t)s->capacity);
+    if (capacity) *capacity = s->capacity;
+    return 0;
+}
+
+int cart_plane_store_contains(cart_plane_store *s, uint64_t frame_id, int *slot) {
+    if (!s) return fail("store is NULL");
+    if (!slot) return fail("slot is NULL");
+    std::lock_guard<std::mutex> lk(s->mu);
+    *slot = s->find(frame_id);
+    return 0;
+}
+
+int cart_plane_store_insert(cart_plane_store *s, uint64_t frame_id, const int16_t *disp, size_t disp_step, const uint8_t *planes, size_t planes_step, int w, int h,
+                            void *stream_) {
+    if (check_frame_size(w, h)) return -1;
+    if (!s) return fail("store is NULL");
+    if (!disp || !planes) return fail("NULL pointer");
+    if ((reinterpret_cast<uintptr_t>(disp) & 1) || (disp_step & 1)) return fail("disparity and its step must be 2-byte aligned");
+    if (disp_step < (size_t)w * sizeof(int16_t)) return fail("disparity_step is below the row size");
+    if (check_pitched(Extent::image("planes", planes, planes_step, 1, w, h))) return -1;
+    if (w != s->w || h != s->h) return fail("width x height must equal the store's W x H");
+
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    ObjectCall call(*s, stream);
+    if (call.begin()) return -1;
+    const int slot = (int)(s->inserted % (uint64_t)s->capacity);
+    const size_t at = (size_t)slot * w * h;
+    launch_plane_store_insert(disp, disp_step, planes, planes_step, s->disp + at, s->planes + at, w, h, stream);
+    HIP_TRY(hipGetLastError());
+    s->ids[slot] = frame_id;
+    s->inserted += 1;
+    return 0;
+}
+
+int cart_plane_map_rebuild(cart_plane_map *m, cart_plane_store *s, const cart_ego_camera *cam, const uint64_t *ids, const double *poses, int count,
+                           const double *window_pose, int *used_out, void *stream_) {
+    if (count < 0 || count > kRevoteMaxEntries) return fail("count must be in [0, 4096]");
+    if (check_camera(cam) || check_pose("window_pose", window_pose)) return -1;
+    if (count > 0 && !ids) return fail("ids is NULL");
+    if (count > 0 && !poses) return fail("poses is NULL");
+    for (int k = 0; k < count; ++k)
+        if (check_pose(("poses[" + std::to_string(k) + "]").c_str(), poses + 12 * (size_t)k)) return -1;
+    if (!m) return fail("map is NULL");
+    if (!s) return fail("store is NULL");
+    if (m->device_id != s->device_id) return fail("map and store are on different devices");
+
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    ObjectCall map_call(*m, stream);   // the map first, then the store: insert takes the store alone, so the order cannot invert
+    if (map_call.begin()) return -1;
+    ObjectCall store_call(*s, stream);
+    if (store_call.begin()) return -1;
+    // the previous rebuild's upload may still be reading the pinned records: wait for that copy alone, not for the stream
+    if (s->staged) HIP_TRY(hipEventSynchronize(s->uploaded));
+    int used = 0;
+    for (int k = 0; k < count; ++k) {
+        const int slot = s->find(ids[k]);
+        if (slot < 0) continue;   // evicted or never inserted: skipped and counted
+        PlaneRevoteRecord &r = s->staging[used++];
+        r.slot = slot; r.pad = 0;
+        std::memcpy(r.pose, poses + 12 * (size_t)k, sizeof(r.pose));
+    }
+    if (used) {
+        HIP_TRY(hipMemcpyAsync(s->records, s->staging, sizeof(PlaneRevoteRecord) * (size_t)used, hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipEventRecord(s->uploaded, stream));
+        s->staged = true;
+    }
+    // the window (S24) of window_pose, emptied whole
+    const int64_t cx = (int64_t)std::floor(window_pose[3] / m->p.cell_size), cz = (int64_t)std::floor(window_pose[11] / m->p.cell_size);
+    m->ox = 16 * floor_div(cx - m->nx / 2, 16); m->oz = 16 * floor_div(cz - m->nz / 2, 16); m->valid = true;
+    const PlaneMapGrid grid = grid_of(m);
+    launch_plane_map_clear(grid, 0, m->nx, 0, m->nz, stream);
+    PlaneMapVoteArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.grid = grid; a.cam = *cam; a.p = m->p;
+    a.ox = (double)m->ox; a.oz = (double)m->oz;
+    a.disp = s->disp; a.disp_step = (size_t)s->w * sizeof(int16_t); a.planes = s->planes; a.planes_step = (size_t)s->w; a.w = s->w; a.h = s->h;
+    launch_plane_map_revote(a, s->records, used, stream);
+    HIP_TRY(hipGetLastError());
+    if (used_out) *used_out = used;
     return 0;
 }
 

@@ -177,6 +177,8 @@ void applyModuleConfig(const Value &modulesConfig, std::shared_ptr<System> syste
             o.planesKey = get<std::string>(moduleConfig, "planes_key", o.planesKey);   // "planes_static": the static world only (motion_seg)
             o.poseKey = get<std::string>(moduleConfig, "pose_key", o.poseKey);         // "dense_ego": the refined trajectory
             o.disparityKey = get<std::string>(moduleConfig, "disparity_key", o.disparityKey);   // "disparity_fused": the temporally fused image (temporal_fusion)
+            o.rebuild = get(moduleConfig, "rebuild", o.rebuild);   // S30: rebuild the grid from the stored keyframes when pose_graph optimised
+            o.storeCapacity = get(moduleConfig, "store_capacity", o.storeCapacity);
             system->addModule<PlaneMapModule>(o);
         } else if (moduleType == "motion_seg") {  // extension (spec S25): which pixels moved on their own, from disparity, optflow and ego_motion
             MotionSegOptions o;

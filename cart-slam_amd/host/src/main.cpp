@@ -146,6 +146,11 @@ int main(int argc, char **argv) {
                     append(o, pm->cells.data(), pm->cells.size() * sizeof(cart_plane_map_cell));
                     const auto classes = pm->classes.downloadTight();
                     append(o, classes.data(), classes.size());
+                    if (pm->rebuilt > 0) {   // a frame that rebuilt the grid (S30): int32 count, used; the ids as uint64
+                        const int32_t counts[2] = {pm->rebuilt, pm->rebuildUsed};
+                        std::ofstream r = writeBin(dump, id, CARTSLAM_KEY_PLANE_MAP "_rebuild", counts, sizeof(counts));
+                        append(r, pm->rebuildIds.data(), pm->rebuildIds.size() * sizeof(uint64_t));
+                    }
                 }
                 if (run->hasData(CARTSLAM_KEY_MOTION)) {   // int32 width, height; the filtered labels, the raw labels, the residual records
                     auto labels = run->getData<cart::image_t>(CARTSLAM_KEY_MOTION);

@@ -600,6 +600,49 @@ int cart_plane_map_read(cart_plane_map *map, cart_plane_map_cell *host_cells, in
  * (1..100) * n -> 1 (VERTICAL = obstacle), else 0 (HORIZONTAL = free).  No host synchronisation. */
 int cart_plane_map_classify(cart_plane_map *map, int min_votes, int obstacle_percent, uint8_t *classes, size_t classes_step, void *stream);
 
+/* ---- Rebuilding the plane map after a pose correction (spec S30) ------------------------------------------------
+ * An extension.  A store keeps the disparity and label images of keyframes on the device; cart_plane_map_rebuild empties the map's
+ * window and votes every stored frame that is named again, each through a NEW pose, in one launch sequence.  S24's votes are integer
+ * sums, minima and maxima, so the rebuilt cells equal, byte for byte, an empty window at that origin plus each used entry's S24 votes
+ * in any order; restated in tests/np_planemap_rebuild.py.
+ *   Store: a ring of `capacity` frames of exactly width x height, each the int16 x16 disparity image and the u8 label image, tightly
+ *   packed and copied verbatim: no gate is applied at insertion, so a store is independent of any map, camera or parameter set.
+ *   Insertion number n (counted from 0 since create / clear) goes to slot n mod capacity and evicts what was there.  Every slot
+ *   remembers the caller's frame_id; the id table is host state.  Ids are looked up newest first, so a repeated id names its latest
+ *   insertion.
+ *   Rebuild: the window origin is S24's, taken from window_pose (t_x = P[3], t_z = P[11]); every cell of the window is emptied; every
+ *   entry (frame_id, pose) whose id is in the store votes by S24's Vote rule into that fixed window through its own pose, with the
+ *   map's own params; votes outside the window are dropped.  Entries whose id is not in the store (evicted or never inserted) are
+ *   skipped and counted: used = count - skipped.  An id may appear more than once and then votes once per appearance.  count = 0
+ *   leaves an empty window at the new origin.  Afterwards the map is valid with that origin and cart_plane_map_update continues on it
+ *   as after any update. */
+typedef struct cart_plane_store cart_plane_store;
+/* Extension (S30).  width, height in 1..16384, capacity in 1..1024, all checked before the engine.  Device footprint:
+ * 3 * width * height * capacity bytes for the images plus 4096 records of 104 bytes for the entries of a rebuild:
+ * 1242 x 375 x 256 is about 358 MB. */
+int cart_plane_store_create(cart_engine *engine, int width, int height, int capacity, cart_plane_store **out);
+/* Extension (S30).  Keeps the device it was created on, so it may be destroyed after its engine. */
+void cart_plane_store_destroy(cart_plane_store *store);
+/* Extension (S30).  Forgets every frame; the next insertion is number 0 again.  HOST only, no device work. */
+int cart_plane_store_clear(cart_plane_store *store);
+/* Extension (S30).  HOST getter: the number of frames held (at most capacity) and the capacity; either pointer may be NULL. */
+int cart_plane_store_size(cart_plane_store *store, int *frames, int *capacity);
+/* Extension (S30).  One frame into the ring under frame_id: disparity = device int16 x16 (2-byte aligned, step a multiple of 2),
+ * planes = device u8 labels, steps in bytes, both width x height, which must equal the store's.  The sizes are checked before the
+ * store and the images.  One copy kernel; no host synchronisation. */
+int cart_plane_store_insert(cart_plane_store *store, uint64_t frame_id, const int16_t *disparity, size_t disparity_step,
+                            const uint8_t *planes, size_t planes_step, int width, int height, void *stream);
+/* Extension (S30).  HOST getter: the slot that holds frame_id's latest insertion, or -1. */
+int cart_plane_store_contains(cart_plane_store *store, uint64_t frame_id, int *slot_or_minus_1);
+/* Extension (S30).  ids = HOST uint64 [count], poses = HOST double [count][12] (3 x 4 camera-to-world, as cart_plane_map_update's),
+ * count in 0..4096, window_pose = HOST double [12]; used_out (HOST, may be NULL) receives the number of entries that voted.  count,
+ * the camera, window_pose and every poses[k] are checked before the map and the store, so a configuration can be validated without
+ * a device; map and store must be on one device.  The entries travel through a pinned buffer of the store: a rebuild that follows
+ * another waits on the host for that earlier upload alone (not for its kernels) before it rewrites the buffer.  No other host
+ * synchronisation.  Holds the map, then the store. */
+int cart_plane_map_rebuild(cart_plane_map *map, cart_plane_store *store, const cart_ego_camera *camera, const uint64_t *ids,
+                           const double *poses, int count, const double *window_pose, int *used_out, void *stream);
+
 /* ---- Motion segmentation from flow, disparity and ego-motion (spec S25) ------------------------------------------
  * An extension: the reference has no such stage.  A pixel moves on its own if the point seen there in frame t-1 (through the flow and
  * the previous disparity), carried through the relative pose and projected back, does not land where the image and the disparity of
