@@ -159,6 +159,28 @@ class PoseGraphResult(C.Structure):
 POSE_GRAPH_MAX_NODES, POSE_GRAPH_MAX_LOOPS, POSE_GRAPH_MAX_ITERATIONS = 4096, 64, 16   # CART_POSE_GRAPH_MAX_*
 
 
+class ObjectParams(C.Structure):
+    # mirrors cart_object_params (include/cart_engine.h, spec S31); the defaults are cart_object_default_params' (build-owned, untuned)
+    _fields_ = [(n, C.c_double) for n in ("min_disparity", "disparity_band", "max_speed", "gate")] + \
+               [(n, C.c_int32) for n in ("min_area", "min_points", "gain_percent", "max_missed", "min_age")]
+
+
+class Object(C.Structure):
+    # mirrors cart_object (include/cart_engine.h, spec S31)
+    _fields_ = [(n, C.c_int32) for n in ("component", "area", "x0", "y0", "x1", "y1", "median_bin", "n_hist", "n_points", "n_flow")] + \
+               [("lo", C.c_int32 * 3), ("hi", C.c_int32 * 3), ("sum", C.c_int64 * 3), ("flow_sum", C.c_int64 * 3), ("centroid", C.c_double * 3),
+                ("velocity", C.c_double * 3), ("extent", C.c_double * 3), ("valid", C.c_int32), ("has_velocity", C.c_int32)]
+
+
+class Track(C.Structure):
+    # mirrors cart_track (include/cart_engine.h, spec S31)
+    _fields_ = [("id", C.c_uint32)] + [(n, C.c_int32) for n in ("state", "age", "missed", "object", "component")] + \
+               [("position", C.c_double * 3), ("velocity", C.c_double * 3), ("extent", C.c_double * 3)]
+
+
+OBJECT_BINS, OBJECT_MAX_OBJECTS, OBJECT_MAX_TRACKS = 512, 256, 256   # CART_OBJECT_*
+
+
 FUSION_NONE, FUSION_MEASURED, FUSION_AGREED, FUSION_REPLACED, FUSION_PREDICTED = range(5)   # CART_FUSION_*
 
 
@@ -280,6 +302,12 @@ PROTOTYPES = {
     "cart_pose_graph_optimize": (_i, [_vp, C.POINTER(PoseGraphParams), _vp, _vp]),
     "cart_pose_graph_poses": (_i, [_vp, _i, _i, _vp, _vp]),
     "cart_pose_graph_read": (_i, [_vp, _i, _i, C.POINTER(C.c_double)]),
+    "cart_object_default_params": (None, [C.POINTER(ObjectParams)]),
+    "cart_object_tracker_create": (_i, [_vp, _i, _i, _i, _i, C.POINTER(_vp)]),
+    "cart_object_tracker_destroy": (None, [_vp]),
+    "cart_object_tracker_reset": (_i, [_vp, _vp]),
+    "cart_object_tracker_update": (_i, [_vp, C.POINTER(EgoCamera), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(ObjectParams), _vp, _sz, _vp, _i, _vp,
+                                        _vp, _sz, _vp, _sz, _vp, _sz, _i, _i, _vp, _vp, _vp, _vp]),
     "cart_optical_flow": (_i, [_vp, _vp, _sz, _vp, _sz, _i, _i, _i, _vp, _sz, _vp]),
     "cart_flow_default_params": (None, [C.POINTER(FlowParams)]),
     "cart_flow_pyramid_levels": (_i, [_i, _i, _i, C.POINTER(_i), C.POINTER(_i)]),

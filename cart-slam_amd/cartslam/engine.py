@@ -10,7 +10,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import DenseEgoParams, EgoCamera, EgoParams, EngineParams, FusionParams, MatchParams, MotionParams, PlaceParams, PlaneMapParams, PlaneParams, PoseGraphParams, SuperpixelParams
+from ._lib import DenseEgoParams, EgoCamera, EgoParams, EngineParams, FusionParams, MatchParams, MotionParams, ObjectParams, PlaceParams, PlaneMapParams, PlaneParams, PoseGraphParams, SuperpixelParams
 
 INVALID = -32768  # CARTSLAM_DISPARITY_INVALID, reference include/modules/disparity.hpp:17
 
@@ -1327,6 +1327,76 @@ class DisparityFusion(_DeviceObject):
         if stream is not None:
             stream.synchronize()
         return tuple(t.cpu().numpy() if t is not None else None for t in out)
+
+
+OBJECT_DTYPE = np.dtype([("component", "<i4"), ("area", "<i4"), ("x0", "<i4"), ("y0", "<i4"), ("x1", "<i4"), ("y1", "<i4"), ("median_bin", "<i4"), ("n_hist", "<i4"),
+                         ("n_points", "<i4"), ("n_flow", "<i4"), ("lo", "<i4", 3), ("hi", "<i4", 3), ("sum", "<i8", 3), ("flow_sum", "<i8", 3),
+                         ("centroid", "<f8", 3), ("velocity", "<f8", 3), ("extent", "<f8", 3), ("valid", "<i4"), ("has_velocity", "<i4")])   # cart_object
+TRACK_DTYPE = np.dtype([("id", "<u4"), ("state", "<i4"), ("age", "<i4"), ("missed", "<i4"), ("object", "<i4"), ("component", "<i4"),
+                        ("position", "<f8", 3), ("velocity", "<f8", 3), ("extent", "<f8", 3)])   # cart_track
+
+
+def object_params(**fields):
+    """cart_object_default_params (spec S31; the defaults are build-owned and untuned) with the given fields replaced."""
+    return _default_params(ObjectParams, "object", fields)
+
+
+ObjectTracks = collections.namedtuple("ObjectTracks", "objects tracks counts")
+
+
+class ObjectTracker(_DeviceObject):
+    """Moving objects and their tracks from the motion components (cart_object_tracker_* in the C ABI, spec S31 in DESIGN.md 7.13): every
+    MOVING component of plane_ccl_table(motion labels) that is large enough, measured in metres and followed from frame to frame, for
+    frames of up to max_width x max_height.  A context manager; close() destroys the device object."""
+    _name = "object_tracker"
+
+    def __init__(self, engine, max_width, max_height, max_objects=64, max_tracks=64):
+        self.max_width, self.max_height, self.max_objects, self.max_tracks = int(max_width), int(max_height), int(max_objects), int(max_tracks)
+        super().__init__(engine, self.max_width, self.max_height, self.max_objects, self.max_tracks)
+
+    def reset(self, stream=None):
+        """Frees every track; the next new track gets id 1."""
+        sp = C.c_void_p(stream.cuda_stream) if stream is not None else _stream_ptr()
+        self._check(self._lib.cart_object_tracker_reset(self._h, sp), "cart_object_tracker_reset")
+
+    def update(self, camera, rel, pose, ids, table, n_components, disp_cur, disp_prev, flow, params=None, raw=False, stream=None):
+        """camera = EgoCamera or (fx, fy, cx, cy, baseline); rel = 12 numbers, the 3 x 4 (R | t) with p_cur = R p_prev + t, pose = 12 numbers,
+        this frame's camera-to-world (both host); ids int32 [h, w], table int32 [max_components, 7] and n_components int32 [1] (or an int)
+        as Engine.plane_ccl_table gives them for one frame of motion labels; disp_cur / disp_prev int16 [h, w] (x16), flow int16 [h, w, 2]
+        (S10.5).  Device tensors are taken as they are (rows may be pitched), host arrays go up.  stream = a torch stream (default: the
+        current one).  -> ObjectTracks(objects OBJECT_DTYPE [max_objects], tracks TRACK_DTYPE [max_tracks], counts int32 [8]) as numpy
+        arrays; raw=True returns the device tensors (float64 views of the records) with no host round trip."""
+        import torch
+        cam = _camera(camera)
+        p = params if params is not None else object_params()
+        with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):   # uploads and allocations on the call's stream
+            if isinstance(n_components, (int, np.integer)):
+                n_components = np.array([n_components], np.int32)
+            idt, tb, nc = _to_device(ids, torch.int32), _to_device(table, torch.int32), _to_device(n_components, torch.int32)
+            dc, dp, fl = _to_device(disp_cur, torch.int16), _to_device(disp_prev, torch.int16), _to_device(flow, torch.int16)
+            if not isinstance(dc, torch.Tensor) or dc.dim() != 2:
+                raise EngineError("disp_cur must be an int16 [h, w] image")
+            objects = torch.empty(self.max_objects * OBJECT_DTYPE.itemsize // 8, dtype=torch.float64, device=dc.device)   # every byte is written by the call
+            tracks = torch.empty(self.max_tracks * TRACK_DTYPE.itemsize // 8, dtype=torch.float64, device=dc.device)
+            counts = torch.empty(8, dtype=torch.int32, device=dc.device)
+        for t, dtype, what, channels in ((dc, torch.int16, "disp_cur", None), (idt, torch.int32, "ids", None), (dp, torch.int16, "disp_prev", None), (fl, torch.int16, "flow", 2)):
+            _check_frame_image(t, dtype, what, dc, channels)
+        if not isinstance(tb, torch.Tensor) or tb.dtype != torch.int32 or not tb.is_cuda or not tb.is_contiguous() or tb.numel() < 7 or tb.numel() % 7:
+            raise EngineError("table must be a contiguous device tensor of int32 rows of 7")
+        if not isinstance(nc, torch.Tensor) or nc.dtype != torch.int32 or not nc.is_cuda or nc.numel() < 1:
+            raise EngineError("n_components must be an int or a device tensor of int32")
+        h, w = int(dc.shape[0]), int(dc.shape[1])
+        sp = C.c_void_p(stream.cuda_stream) if stream is not None else _stream_ptr()
+        self._check(self._lib.cart_object_tracker_update(self._h, C.byref(cam), _pose12(rel), _pose12(pose), C.byref(p), *_pitched(idt, 1), C.c_void_p(tb.data_ptr()),
+                                                         tb.numel() // 7, C.c_void_p(nc.data_ptr()), *_pitched(dc, 1), *_pitched(dp, 1), *_pitched(fl, 2), w, h,
+                                                         C.c_void_p(objects.data_ptr()), C.c_void_p(tracks.data_ptr()), C.c_void_p(counts.data_ptr()), sp),
+                    "cart_object_tracker_update")
+        out = ObjectTracks(objects, tracks, counts)
+        if raw:
+            return out
+        if stream is not None:
+            stream.synchronize()
+        return ObjectTracks(objects.cpu().numpy().view(OBJECT_DTYPE), tracks.cpu().numpy().view(TRACK_DTYPE), counts.cpu().numpy())
 
 
 def plane_cluster(planes, offsets, neighbours):

@@ -490,6 +490,47 @@ struct PoseGraphArgs {
 void launch_pose_graph_add_node(const PoseGraphNodeArgs &a, hipStream_t s);
 void launch_pose_graph_add_loop(const PoseGraphLoopArgs &a, hipStream_t s);
 void launch_pose_graph_optimize(const PoseGraphArgs &a, hipStream_t s);   // one launch whatever the counts
+// ---- moving-object tracks from the motion components (object_kernels.hip) ----
+constexpr int kObjectHistStrip = 8;     // image rows one lane of the histogram kernel walks with one open run
+constexpr int kObjectPointStrip = 4;    // image rows one lane of the point kernel walks with one open run
+constexpr int kObjectMaxObjects = CART_OBJECT_MAX_OBJECTS, kObjectMaxTracks = CART_OBJECT_MAX_TRACKS;   // both = threads of object_tracks
+struct ObjectAcc {                      // 96 bytes per object, all integers: what pass 2 accumulates
+    uint32_t n_points, n_flow;
+    int32_t lo[3], hi[3];
+    int32_t x0, y0, x1, y1;
+    unsigned long long sum[3], flow_sum[3];   // int64 sums, added as unsigned (two's complement)
+};
+static_assert(sizeof(ObjectAcc) == 96, "ObjectAcc layout (DESIGN.md S31)");
+struct ObjectState {                    // the tracker's device words beside the tracks
+    uint32_t next_id;
+    int32_t n_seen, n_selected, n_objects;   // of the call in flight, written by object_select
+};
+struct ObjectArgs {
+    cart_ego_camera cam;
+    cart_object_params p;
+    double rel[12], pose[12];
+    const int32_t *ids; size_t ids_step;
+    const cart_component *table; int max_components;
+    const int32_t *n_components;
+    const int16_t *disp_cur; size_t disp_cur_step;
+    const int16_t *disp_prev; size_t disp_prev_step;
+    const int16_t *flow; size_t flow_step;
+    int w, h, max_objects, max_tracks;
+    // the tracker's own memory
+    int32_t *slot_of;                   // [max_width * max_height] by component id: the object index, -1 everywhere between calls
+    int32_t *hist;                      // [max_objects][CART_OBJECT_BINS]
+    int32_t *median;                    // [max_objects][2]: B_j, n_hist
+    ObjectAcc *acc;                     // [max_objects]
+    cart_object *objects;               // [max_objects]: the selection's fields, then the whole record
+    cart_track *tracks;                 // [max_tracks]
+    ObjectState *state;
+    // the caller's outputs
+    cart_object *objects_out;           // may be NULL
+    cart_track *tracks_out;
+    int32_t *counts_out;
+};
+void launch_object_reset(cart_track *tracks, int max_tracks, ObjectState *state, hipStream_t s);
+void launch_object_update(const ObjectArgs &a, hipStream_t s);   // the five launches of one call
 void launch_narrow_copy(const void *src, void *dst, size_t bytes, int blocks, hipStream_t s);
 int kernel_count();
 

@@ -18,6 +18,7 @@
 #include "cartslam_amd/modules/matches.hpp"
 #include "cartslam_amd/modules/denseego.hpp"
 #include "cartslam_amd/modules/fusion.hpp"
+#include "cartslam_amd/modules/objects.hpp"
 #include "cartslam_amd/modules/loopclosure.hpp"
 #include "cartslam_amd/modules/motionseg.hpp"
 #include "cartslam_amd/modules/planefit.hpp"
@@ -214,6 +215,22 @@ void applyModuleConfig(const Value &modulesConfig, std::shared_ptr<System> syste
             o.useMotion = get(moduleConfig, "use_motion", o.useMotion);
             o.poseKey = get<std::string>(moduleConfig, "pose_key", o.poseKey);   // "dense_ego": the refined relative pose
             system->addModule<TemporalFusionModule>(o);
+        } else if (moduleType == "moving_objects") {  // extension (spec S31): motion_seg's MOVING components as objects in metres and their tracks
+            MovingObjectsOptions o;
+            readCamera(moduleConfig, *dataSource, o);
+            o.minDisparity = get(moduleConfig, "min_disparity", o.minDisparity);
+            o.disparityBand = get(moduleConfig, "disparity_band", o.disparityBand);
+            o.maxSpeed = get(moduleConfig, "max_speed", o.maxSpeed);
+            o.gate = get(moduleConfig, "gate", o.gate);
+            o.minArea = get(moduleConfig, "min_area", o.minArea);
+            o.minPoints = get(moduleConfig, "min_points", o.minPoints);
+            o.gainPercent = get(moduleConfig, "gain_percent", o.gainPercent);
+            o.maxMissed = get(moduleConfig, "max_missed", o.maxMissed);
+            o.minAge = get(moduleConfig, "min_age", o.minAge);
+            o.maxObjects = get(moduleConfig, "max_objects", o.maxObjects);
+            o.maxTracks = get(moduleConfig, "max_tracks", o.maxTracks);
+            o.poseKey = get<std::string>(moduleConfig, "pose_key", o.poseKey);   // "dense_ego": the refined poses; "pose_graph" is refused
+            system->addModule<MovingObjectsModule>(o);
         } else if (moduleType == "loop_closure") {  // extension (spec S27): keyframes recognised in a device-resident ring and verified by a relative pose
             LoopClosureOptions o;
             readCamera(moduleConfig, *dataSource, o);

@@ -23,6 +23,7 @@
 #include "cartslam_amd/modules/fusion.hpp"
 #include "cartslam_amd/modules/loopclosure.hpp"
 #include "cartslam_amd/modules/motionseg.hpp"
+#include "cartslam_amd/modules/objects.hpp"
 #include "cartslam_amd/timing.hpp"
 #include "cartslam_amd/modules/planefit.hpp"
 #include "cartslam_amd/modules/planemap.hpp"
@@ -171,6 +172,12 @@ int main(int argc, char **argv) {
                     }
                     auto counts = run->getData<cart::FusionCounts>(CARTSLAM_KEY_DISPARITY_FUSION_COUNTS);
                     append(o, counts->pixels, sizeof(counts->pixels));
+                }
+                if (run->hasData(CARTSLAM_KEY_MOVING_OBJECTS)) {   // int32 counts [8]; the n_objects 192-byte cart_object records; the live 96-byte cart_track records
+                    auto mo = run->getData<cart::MovingObjects>(CARTSLAM_KEY_MOVING_OBJECTS);
+                    std::ofstream o = writeBin(dump, id, CARTSLAM_KEY_MOVING_OBJECTS, mo->counts, sizeof(mo->counts));
+                    append(o, mo->objects.data(), mo->objects.size() * sizeof(cart_object));
+                    append(o, mo->tracks.data(), mo->tracks.size() * sizeof(cart_track));
                 }
                 if (run->hasData(CARTSLAM_KEY_PLANES_EQ_LABEL_PLANES)) {   // f64 [max_label + 1][4]
                     auto lp = run->getData<std::vector<cart::Vec4d>>(CARTSLAM_KEY_PLANES_EQ_LABEL_PLANES);

@@ -906,6 +906,96 @@ int cart_pose_graph_poses(cart_pose_graph *pg, int first, int count, double *out
 /* Extension.  The same into HOST memory, after every call queued on the object so far; synchronises.  For tests and dumps. */
 int cart_pose_graph_read(cart_pose_graph *pg, int first, int count, double *out_host);
 
+/* ---- Moving-object tracks from the motion components (spec S31) ----------------------------------------------------
+ * An extension: the reference has no such stage.  Every MOVING component of cart_plane_ccl_table (run on the labels of
+ * cart_motion_segment) that is large enough becomes an object: where its surface is in metres, how large, which way and how fast it
+ * moves beyond the camera's own motion, and, through a small tracker in the world frame, that it is the object of the last frame.
+ * fp64 with + - * / floor only, every expression in the written order, the only atomics are integer additions, minima and maxima:
+ * restated in tests/np_objects.py, byte for byte.
+ *   Selection: table entries k = 0 .. min(n_components, max_components) - 1 in table order; entry k is selected iff label == 1 and
+ *   area >= min_area; the j-th selected entry is object j, objects j >= max_objects are dropped (n_selected keeps the true count).
+ *   Pass 1: a pixel whose id is object j's contributes iff s_c = disp_cur != -32768 and s_c / 16.0 >= min_disparity; it adds one to bin
+ *   min(s_c >> 4, 511) of the object's histogram (CART_OBJECT_BINS bins).  n_hist = the total, B_j = the smallest bin whose cumulative
+ *   count is >= (n_hist + 1) >> 1, -1 at n_hist = 0.
+ *   Pass 2: with band16 = (int)floor(disparity_band 16.0), a pixel of object j that passes pass 1's gate is a point iff
+ *   |s_c - (16 B_j + 8)| <= band16.  A point: P = back-projection of (x, y, s_c / 16.0) as S25's; n_points += 1, sum[i] += Qp(P_i),
+ *   lo[i] / hi[i] = min / max of Qp(P_i), the pixel box x0..y1 grows; Qp(v) = (int64) clamp(floor(v 1024.0 + 0.5), -2147483647,
+ *   2147483647), a NaN gives the lower bound.  The point carries flow iff S25's gates 2-4 pass ((xp, yp) = p - (flow >> 5) inside the
+ *   image, disp_prev there valid and >= min_disparity, q = rel applied to the previous point with q.z > 0) and f = P - q has
+ *   (f.x f.x + f.y f.y) + f.z f.z <= max_speed max_speed; then n_flow += 1, flow_sum[i] += Qp(f_i).
+ *   Derive: valid = n_points >= min_points; c_i = ((double)sum[i] / 1024.0) / (double)n_points, centroid = pose applied to c,
+ *   extent_i = (double)(hi[i] - lo[i]) / 1024.0 (camera axes); has_velocity = valid and n_flow >= min_points, v_i = ((double)flow_sum[i]
+ *   / 1024.0) / (double)n_flow, velocity[r] = (pose[4r] v.x + pose[4r+1] v.y) + pose[4r+2] v.z (world, metres per frame).  The three
+ *   of an invalid object, and the velocity of one without, are +0.0.
+ *   Tracks (max_tracks slots, state 0 = free, a device next_id that starts at 1), per frame over the valid objects and live tracks:
+ *   pred = position + velocity; d2 = (dx dx + dy dy) + dz dz between centroid and pred (d = centroid - pred), admissible iff d2 <=
+ *   gate gate; greedy: the admissible pair with both ends free and the smallest d2 is matched, ties to the smaller slot, then the
+ *   smaller object, until none is left.  Matched: m = has_velocity ? the object's velocity : centroid - position (the old one),
+ *   velocity += g (m - velocity) with g = gain_percent / 100.0, position = centroid, extent = the object's, age += 1, missed = 0,
+ *   object / component set, state = age >= min_age ? 2 : 1.  Unmatched: position = pred, missed += 1, object = component = -1, freed
+ *   when missed > max_missed.  Then every unmatched valid object in ascending index takes the lowest free slot (those just freed
+ *   included): id = next_id++, age 1, missed 0, state = min_age <= 1 ? 2 : 1, velocity the object's (or 0); without a free slot it is
+ *   dropped and counted. */
+#define CART_OBJECT_BINS 512
+#define CART_OBJECT_MAX_OBJECTS 256
+#define CART_OBJECT_MAX_TRACKS 256
+typedef struct cart_object_params {
+    double min_disparity;                     /* pixels, finite, > 0 */
+    double disparity_band;                    /* pixels, finite, 0.5..64 */
+    double max_speed;                         /* metres per frame, finite, > 0 */
+    double gate;                              /* metres, finite, > 0 */
+    int32_t min_area;                         /* pixels of a component, 1..2^30 */
+    int32_t min_points;                       /* 1..2^30 */
+    int32_t gain_percent;                     /* 0..100 */
+    int32_t max_missed;                       /* 0..255 */
+    int32_t min_age;                          /* 1..255 */
+} cart_object_params;
+/* Extension (S31): 1.0, 2.0, 5.0, 2.0, 64, 16, 50, 3, 3 (build-owned, no data set has tuned them). */
+void cart_object_default_params(cart_object_params *p);
+typedef struct cart_object {                  /* S31; 192 bytes, 8-byte aligned */
+    int32_t component, area;                  /* the table entry's id and area */
+    int32_t x0, y0, x1, y1;                   /* the pixel box of the object's POINTS, inclusive (not the table's box, which holds the
+                                                 occlusion rim as well); 0, 0, -1, -1 without a point */
+    int32_t median_bin, n_hist, n_points, n_flow;
+    int32_t lo[3], hi[3];                     /* of Qp(P_i); all 0 without a point */
+    int64_t sum[3], flow_sum[3];
+    double centroid[3], velocity[3], extent[3];   /* world, world per frame, camera axes */
+    int32_t valid, has_velocity;
+} cart_object;
+typedef struct cart_track {                   /* S31; 96 bytes, 8-byte aligned */
+    uint32_t id;                              /* 0 in a free slot; never repeats */
+    int32_t state;                            /* 0 free, 1 tentative, 2 confirmed */
+    int32_t age, missed;
+    int32_t object, component;                /* this frame's object index and its component id, -1 when unmatched or free */
+    double position[3], velocity[3], extent[3];
+} cart_track;
+
+typedef struct cart_object_tracker cart_object_tracker;
+/* Extension (S31).  The histograms, the accumulators, the id -> object scratch image (4 bytes per pixel) and the tracks for frames of up
+ * to max_width x max_height (1..16384 each), max_objects and max_tracks in 1..256; no call allocates.  The sizes are checked before the
+ * engine. */
+int cart_object_tracker_create(cart_engine *engine, int max_width, int max_height, int max_objects, int max_tracks, cart_object_tracker **out);
+/* Extension (S31).  Keeps the device it was created on, so it may be destroyed after its engine. */
+void cart_object_tracker_destroy(cart_object_tracker *obj);
+/* Extension (S31).  Frees every track and sets next_id = 1; ordered on `stream` like every other call. */
+int cart_object_tracker_reset(cart_object_tracker *obj, void *stream);
+/* Extension (S31).  One frame, width x height (1..16384 each and within the object's maxima), every image the caller's device memory
+ * followed by its step in bytes: ids = the int32 image and table = the DEVICE cart_component [max_components] of cart_plane_ccl_table
+ * run on cart_motion_segment's labels, n_components = its DEVICE int32 count (it may exceed max_components; max_components >= 1);
+ * disp_cur / disp_prev int16 x16, flow int16 x2 in S10.5 as cart_motion_segment's.  rel = HOST double [12] as cart_motion_segment's,
+ * pose = HOST double [12], camera-to-world of this frame as cart_plane_map_update's.  Outputs: objects_out = DEVICE cart_object
+ * [max_objects] (rows past the frame's objects all zero; may be NULL), tracks_out = DEVICE cart_track [max_tracks], every slot,
+ * counts_out = DEVICE int32 [8]: {table entries walked, n_selected, n_objects, n_valid, n_matched, n_born, n_dropped, n_live}.  The
+ * records are 8-byte aligned, counts_out and the int32 inputs 4-byte.  No output may overlap another output or an input: each such pair
+ * is refused by name.  Checked in this order, all before any device call: params, camera, rel, pose, sizes, object (and the sizes
+ * against it), then pointers, alignment, steps and overlaps; a refused call launches nothing and touches no output or track.  Five
+ * plain launches on `stream`, no host synchronisation. */
+int cart_object_tracker_update(cart_object_tracker *obj, const cart_ego_camera *camera, const double *rel, const double *pose,
+                               const cart_object_params *params, const int32_t *ids, size_t ids_step, const cart_component *table,
+                               int max_components, const int32_t *n_components, const int16_t *disp_cur, size_t disp_cur_step,
+                               const int16_t *disp_prev, size_t disp_prev_step, const int16_t *flow, size_t flow_step, int width, int height,
+                               cart_object *objects_out, cart_track *tracks_out, int32_t *counts_out, void *stream);
+
 /* Stand-in for ImageOpticalFlowModule's device work (src/modules/optflow.cpp:96-140: cvtColor x2 +
  * cv::cuda::NvidiaOpticalFlow_2_0::calc(current, previous), NVIDIA fixed-function hardware): dense census block
  * matching (oracle S15).  cur / prev = the reference images of frame id and id-1 (1-channel gray or 3-channel BGR),
