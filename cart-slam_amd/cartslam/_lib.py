@@ -159,6 +159,20 @@ class PoseGraphResult(C.Structure):
 POSE_GRAPH_MAX_NODES, POSE_GRAPH_MAX_LOOPS, POSE_GRAPH_MAX_ITERATIONS = 4096, 64, 16   # CART_POSE_GRAPH_MAX_*
 
 
+class LocalBAParams(C.Structure):
+    # mirrors cart_local_ba_params (include/cart_engine.h, spec S32); the defaults are cart_local_ba_default_params' (build-owned, untuned)
+    _fields_ = [(n, C.c_double) for n in ("min_disparity", "huber", "damping")] + [(n, C.c_int32) for n in ("iterations", "min_observations", "min_frame_observations")]
+
+
+class LocalBAResult(C.Structure):
+    # mirrors cart_local_ba_result (include/cart_engine.h, spec S32)
+    _fields_ = [(n, C.c_int32) for n in ("status", "n_frames", "n_points_active", "n_observations", "n_held", "iterations")] + \
+               [("cost_before", C.c_double), ("cost_after", C.c_double)]
+
+
+LOCAL_BA_MAX_WINDOW, LOCAL_BA_MAX_POINTS, LOCAL_BA_MAX_ITERATIONS = 16, 65536, 16   # CART_LOCAL_BA_MAX_*
+
+
 class ObjectParams(C.Structure):
     # mirrors cart_object_params (include/cart_engine.h, spec S31); the defaults are cart_object_default_params' (build-owned, untuned)
     _fields_ = [(n, C.c_double) for n in ("min_disparity", "disparity_band", "max_speed", "gate")] + \
@@ -308,6 +322,16 @@ PROTOTYPES = {
     "cart_object_tracker_reset": (_i, [_vp, _vp]),
     "cart_object_tracker_update": (_i, [_vp, C.POINTER(EgoCamera), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(ObjectParams), _vp, _sz, _vp, _i, _vp,
                                         _vp, _sz, _vp, _sz, _vp, _sz, _i, _i, _vp, _vp, _vp, _vp]),
+    "cart_local_ba_default_params": (None, [C.POINTER(LocalBAParams)]),
+    "cart_local_ba_create": (_i, [_vp, _i, _i, _i, C.POINTER(_vp)]),
+    "cart_local_ba_destroy": (None, [_vp]),
+    "cart_local_ba_clear": (_i, [_vp, _vp]),
+    "cart_local_ba_size": (_i, [_vp, C.POINTER(_i), C.POINTER(_i)]),
+    "cart_local_ba_push": (_i, [_vp, C.POINTER(EgoCamera), C.POINTER(LocalBAParams), C.c_uint64, C.POINTER(C.c_double), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "cart_local_ba_optimize": (_i, [_vp, C.POINTER(EgoCamera), C.POINTER(LocalBAParams), _vp, _vp]),
+    "cart_local_ba_poses": (_i, [_vp, _vp, _vp, _vp]),
+    "cart_local_ba_points": (_i, [_vp, _vp, _vp]),
+    "cart_local_ba_track_of": (_i, [_vp, _vp, _vp]),
     "cart_optical_flow": (_i, [_vp, _vp, _sz, _vp, _sz, _i, _i, _i, _vp, _sz, _vp]),
     "cart_flow_default_params": (None, [C.POINTER(FlowParams)]),
     "cart_flow_pyramid_levels": (_i, [_i, _i, _i, C.POINTER(_i), C.POINTER(_i)]),

@@ -10,7 +10,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import DenseEgoParams, EgoCamera, EgoParams, EngineParams, FusionParams, MatchParams, MotionParams, ObjectParams, PlaceParams, PlaneMapParams, PlaneParams, PoseGraphParams, SuperpixelParams
+from ._lib import DenseEgoParams, EgoCamera, EgoParams, EngineParams, FusionParams, LocalBAParams, MatchParams, MotionParams, ObjectParams, PlaceParams, PlaneMapParams, PlaneParams, PoseGraphParams, SuperpixelParams
 
 INVALID = -32768  # CARTSLAM_DISPARITY_INVALID, reference include/modules/disparity.hpp:17
 
@@ -1230,6 +1230,89 @@ class PoseGraph(_DeviceObject):
 
     def clear(self):
         self._check(self._lib.cart_pose_graph_clear(self._h, _stream_ptr()), "cart_pose_graph_clear")
+
+
+LOCAL_BA_RESULT_DTYPE = np.dtype([("status", "<i4"), ("n_frames", "<i4"), ("n_points_active", "<i4"), ("n_observations", "<i4"), ("n_held", "<i4"),
+                                  ("iterations", "<i4"), ("cost_before", "<f8"), ("cost_after", "<f8")])   # cart_local_ba_result
+
+
+def local_ba_params(**fields):
+    """cart_local_ba_default_params (spec S32; build-owned, untuned) with the given fields replaced."""
+    return _default_params(LocalBAParams, "local_ba", fields)
+
+
+class LocalBA(_DeviceObject):
+    """Windowed bundle adjustment over the last frames (cart_local_ba_* in the C ABI, spec S32 in DESIGN.md 7.14): push() builds feature
+    tracks from a frame's keypoints and match lists, optimize() refines the poses of the window and the points they share on the device.
+    Stateful in call order.  A context manager; close() destroys the device object."""
+    _name = "local_ba"
+
+    def __init__(self, engine, max_features=_lib.ORB_DEFAULT_FEATURES, window=8, max_points=8192):
+        self.max_features, self.window, self.max_points = int(max_features), int(window), int(max_points)
+        super().__init__(engine, self.max_features, self.window, self.max_points)
+
+    _rows, _count = EgoMotion._rows, EgoMotion._count   # the same lists, padded to max_features, and their device counts
+
+    def push(self, camera, frame_id, pose, kp_left, kp_right, stereo_matches, temporal_matches, left_count=None, stereo_count=None, temporal_count=None,
+             params=None, raw=False):
+        """One frame: camera = EgoCamera or (fx, fy, cx, cy, baseline); pose = 12 numbers (3 x 4 camera-to-world, host); keypoints as KEYPOINT_DTYPE arrays or float32 device [max_features, 7]
+        records, matches as MATCH_DTYPE arrays or int32 device [max_features, 4] tensors, counts as ints, device int32 or None (= the rows
+        of a host array).  -> the int32 [8] counts (host, synchronises), or with raw=True the device tensor with no host round trip."""
+        import torch
+        p = params if params is not None else local_ba_params()
+        kl, nl = self._rows(kp_left, torch.float32, 7, "keypoints")
+        kr, _ = self._rows(kp_right, torch.float32, 7, "keypoints")
+        sm, ns = self._rows(stereo_matches, torch.int32, 4, "matches")
+        tm, nt = self._rows(temporal_matches, torch.int32, 4, "matches")
+        lc = self._count(left_count, nl, isinstance(kp_left, torch.Tensor))
+        sc = self._count(stereo_count, ns, isinstance(stereo_matches, torch.Tensor))
+        tc = self._count(temporal_count, nt, isinstance(temporal_matches, torch.Tensor))
+        counts = torch.zeros(8, dtype=torch.int32, device="cuda")
+        ptr = lambda t: C.c_void_p(t.data_ptr())   # noqa: E731
+        self._check(self._lib.cart_local_ba_push(self._h, C.byref(_camera(camera)), C.byref(p), C.c_uint64(int(frame_id)), _pose12(pose), ptr(kl), ptr(kr), ptr(lc),
+                                                 ptr(sm), ptr(sc), ptr(tm), ptr(tc), ptr(counts), _stream_ptr()), "cart_local_ba_push")
+        return counts if raw else counts.cpu().numpy()
+
+    def optimize(self, camera, params=None, raw=False, **fields):
+        """Gauss-Newton over the window with camera = EgoCamera or (fx, fy, cx, cy, baseline) (local_ba_params(**fields) unless params is given) -> the LOCAL_BA_RESULT_DTYPE record [1]
+        (synchronises); raw=True: the device tensor of 5 doubles that holds it, no host synchronisation."""
+        import torch
+        p = params if params is not None else local_ba_params(**fields)
+        out = torch.zeros(LOCAL_BA_RESULT_DTYPE.itemsize // 8, dtype=torch.float64, device="cuda")
+        self._check(self._lib.cart_local_ba_optimize(self._h, C.byref(_camera(camera)), C.byref(p), C.c_void_p(out.data_ptr()), _stream_ptr()), "cart_local_ba_optimize")
+        return out if raw else out.cpu().numpy().view(LOCAL_BA_RESULT_DTYPE)
+
+    def poses(self, raw=False):
+        """-> (float64 [window, 12] estimates in age order, oldest first, rows past the frames in the window zero; uint64 [window] frame
+        ids); raw=True: the device tensors (the ids as int64), no host synchronisation."""
+        import torch
+        out = torch.zeros((self.window, 12), dtype=torch.float64, device="cuda")
+        ids = torch.zeros(self.window, dtype=torch.int64, device="cuda")
+        self._check(self._lib.cart_local_ba_poses(self._h, C.c_void_p(out.data_ptr()), C.c_void_p(ids.data_ptr()), _stream_ptr()), "cart_local_ba_poses")
+        return (out, ids) if raw else (out.cpu().numpy(), ids.cpu().numpy().view(np.uint64))
+
+    def points(self, raw=False):
+        """-> float64 [max_points, 4] = (X, Y, Z, n_obs) of every point slot, zeros in a free one."""
+        import torch
+        out = torch.zeros((self.max_points, 4), dtype=torch.float64, device="cuda")
+        self._check(self._lib.cart_local_ba_points(self._h, C.c_void_p(out.data_ptr()), _stream_ptr()), "cart_local_ba_points")
+        return out if raw else out.cpu().numpy()
+
+    def track_of(self, raw=False):
+        """-> int32 [max_features]: the point slot of every left index of the newest frame, -1 without."""
+        import torch
+        out = torch.zeros(self.max_features, dtype=torch.int32, device="cuda")
+        self._check(self._lib.cart_local_ba_track_of(self._h, C.c_void_p(out.data_ptr()), _stream_ptr()), "cart_local_ba_track_of")
+        return out if raw else out.cpu().numpy()
+
+    def size(self):
+        """-> (frames in the window, max_points); host only."""
+        frames, cap = C.c_int(0), C.c_int(0)
+        self._check(self._lib.cart_local_ba_size(self._h, C.byref(frames), C.byref(cap)), "cart_local_ba_size")
+        return frames.value, cap.value
+
+    def clear(self):
+        self._check(self._lib.cart_local_ba_clear(self._h, _stream_ptr()), "cart_local_ba_clear")
 
 
 DENSE_EGO_RESULT_DTYPE = np.dtype([("R", "<f8", 9), ("t", "<f8", 3), ("rms_initial", "<f8"), ("rms", "<f8"), ("status", "<i4"), ("n_candidates", "<i4"),

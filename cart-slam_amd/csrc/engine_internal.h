@@ -531,6 +531,68 @@ struct ObjectArgs {
 };
 void launch_object_reset(cart_track *tracks, int max_tracks, ObjectState *state, hipStream_t s);
 void launch_object_update(const ObjectArgs &a, hipStream_t s);   // the five launches of one call
+// ---- windowed bundle adjustment over the last frames (localba_kernels.hip) ----
+constexpr int kLbaMaxWindow = CART_LOCAL_BA_MAX_WINDOW, kLbaMaxIterations = CART_LOCAL_BA_MAX_ITERATIONS;
+constexpr int kLbaLanes = 256;          // threads of the reducing workgroups = virtual lanes of the S23 sums
+constexpr int kLbaPointRows = 12;       // SoA rows of the per-point blocks of a step: V^-1 [9] in row order, g_p [3]
+constexpr int kLbaInBit = 31;           // bit of LbaStore::used: the point takes part in the step; bit a < 16: its observation in age a does
+struct LbaObs { float u, v, ur; int32_t valid; };   // one observation
+static_assert(sizeof(LbaObs) == 16, "LbaObs layout (DESIGN.md S32)");
+struct LbaControl {                     // the optimiser's device words
+    int32_t fail, skip, n_active, n_observations, n_held;
+    int32_t count[2][kLbaMaxWindow];    // usable observations per age, of the even and of the odd steps
+    int32_t pad;
+    double cost_before;
+};
+struct LbaStore {
+    // the frame ring, [window] by ring slot
+    double *odom, *est, *lin_est, *snap_est;   // [window][12]: as handed in, the estimate, the estimate a step linearises at, the call's snapshot
+    uint64_t *frame_id;
+    // the point table and the dense observation table
+    double *X, *snap_X;                 // [max_points][3]
+    int32_t *n_obs, *state;             // [max_points]; state 0 = free
+    LbaObs *obs;                        // [max_points][window]
+    // push
+    LbaObs *sobs;                       // [max_features]: the stereo observation of every left index
+    int32_t *tmatch;                    // [max_features]: the train index of the left index's temporal match, -1 without
+    int32_t *claim;                     // [max_points]: the smallest left index that continues the point
+    int32_t *free_list;                 // [max_points]: the free slots in ascending order
+    int32_t *track[2];                  // [max_features] each: track_of of the newest frame and of the one before, swapped per push
+    int32_t *counts;                    // [8] of the last push, then [1]: points freed by the push in flight
+    // optimise
+    double *blocks;                     // [kLbaPointRows][max_points]
+    int32_t *used;                      // [max_points]
+    LbaControl *ctl;
+    double *S;                          // [6 (window - 1) + 1][6 (window - 1)]: the reduced system's lower entries, the last row its right-hand side
+    double *delta;                      // [6 (window - 1)]
+    int max_features, window, max_points;
+};
+struct LbaPushArgs {
+    LbaStore g;
+    cart_ego_camera cam;
+    double min_disparity;
+    double pose[12];
+    uint64_t frame_id;
+    int slot, prev_slot;                // the new frame's ring slot; the previous frame's, -1 for the first push after a clear
+    int evict;                          // the ring is full: the frame in `slot` leaves
+    int cur;                            // which of g.track the new frame writes
+    int frames;                         // frames in the window after the push
+    const cart_keypoint *kpL, *kpR; const int32_t *left_count;
+    const cart_match *stereo; const int32_t *stereo_count;
+    const cart_match *temporal; const int32_t *temporal_count;
+    int32_t *counts_out;                // may be NULL
+};
+struct LbaOptArgs {
+    LbaStore g;
+    cart_ego_camera cam;
+    cart_local_ba_params p;
+    int frames, first_slot;             // age a lives in ring slot (first_slot + a) mod window
+    cart_local_ba_result *result;       // may be NULL
+};
+void launch_local_ba_push(const LbaPushArgs &a, hipStream_t s);        // 4 launches
+void launch_local_ba_optimize(const LbaOptArgs &a, hipStream_t s);     // 2 + 5 iterations launches
+void launch_local_ba_poses(const LbaStore &g, int frames, int first_slot, double *out, uint64_t *ids_out, hipStream_t s);
+void launch_local_ba_points(const LbaStore &g, double *out, hipStream_t s);
 void launch_narrow_copy(const void *src, void *dst, size_t bytes, int blocks, hipStream_t s);
 int kernel_count();
 

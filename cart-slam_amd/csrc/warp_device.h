@@ -7,7 +7,7 @@
 //   back-project  Z = fxb / d,  X = ((u - cx) * Z) / fx,  Y = ((v - cy) * Z) / fy          (fxb = fx * baseline, d = disparity in pixels)
 //   carry         q_r = ((P[4r] * X + P[4r + 1] * Y) + P[4r + 2] * Z) + P[4r + 3]          (r = 0, 1, 2)
 //   project       u = (fx * q_x) / q_z + cx,  v = (fy * q_y) / q_z + cy
-// Device only; included by planemap_kernels.hip, motion_kernels.hip, dense_ego_kernels.hip and fusion_kernels.hip.
+// Device only; included by planemap_kernels.hip, motion_kernels.hip, dense_ego_kernels.hip, fusion_kernels.hip and localba_kernels.hip.
 #pragma once
 
 #include "engine_internal.h"
@@ -31,6 +31,12 @@ __device__ __forceinline__ double back_project_y(const cart_ego_camera &cam, int
 __device__ __forceinline__ WarpPoint back_project(const cart_ego_camera &cam, double fxb, int u, int v, double d) {
     const double Z = fxb / d;
     return WarpPoint{back_project_x(cam, u, Z), back_project_y(cam, v, Z), Z};
+}
+
+// The same for a position between pixels (a keypoint of spec S32): the operations and their order are the ones above.
+__device__ __forceinline__ WarpPoint back_project(const cart_ego_camera &cam, double fxb, double u, double v, double d) {
+    const double Z = fxb / d;
+    return WarpPoint{((u - cam.cx) * Z) / cam.fx, ((v - cam.cy) * Z) / cam.fy, Z};
 }
 
 // Row r of the 3 x 4 row-major pose P applied to p, and all three.

@@ -24,6 +24,7 @@
 #include "cartslam_amd/modules/planefit.hpp"
 #include "cartslam_amd/modules/planemap.hpp"
 #include "cartslam_amd/modules/planeseg.hpp"
+#include "cartslam_amd/modules/localba.hpp"
 #include "cartslam_amd/modules/posegraph.hpp"
 #include "cartslam_amd/modules/superpixels.hpp"
 
@@ -263,6 +264,20 @@ void applyModuleConfig(const Value &modulesConfig, std::shared_ptr<System> syste
             o.loopWeight = get(moduleConfig, "loop_weight", o.loopWeight);
             o.poseKey = get<std::string>(moduleConfig, "pose_key", o.poseKey);   // "dense_ego": the refined trajectory is the odometry
             system->addModule<PoseGraphModule>(o);
+        } else if (moduleType == "local_ba") {  // extension (spec S32): feature tracks over the last frames and a windowed bundle adjustment of their poses
+            LocalBAOptions o;
+            readCamera(moduleConfig, *dataSource, o);
+            o.minDisparity = get(moduleConfig, "min_disparity", o.minDisparity);
+            o.huber = get(moduleConfig, "huber", o.huber);
+            o.damping = get(moduleConfig, "damping", o.damping);
+            o.iterations = get(moduleConfig, "iterations", o.iterations);
+            o.minObservations = get(moduleConfig, "min_observations", o.minObservations);
+            o.minFrameObservations = get(moduleConfig, "min_frame_observations", o.minFrameObservations);
+            o.window = get(moduleConfig, "window", o.window);
+            o.maxPoints = get(moduleConfig, "max_points", o.maxPoints);
+            o.interval = get(moduleConfig, "interval", o.interval);
+            o.poseKey = get<std::string>(moduleConfig, "pose_key", o.poseKey);   // "dense_ego": the refined trajectory is the odometry
+            system->addModule<LocalBAModule>(o);
         } else if (endsWith(moduleType, "_visualization")) {
             std::cerr << "[cartconfig] skipping GUI module type " << moduleType << " (out of scope)\n";
         } else {

@@ -21,6 +21,7 @@
 #include "cartslam_amd/modules/matches.hpp"
 #include "cartslam_amd/modules/denseego.hpp"
 #include "cartslam_amd/modules/fusion.hpp"
+#include "cartslam_amd/modules/localba.hpp"
 #include "cartslam_amd/modules/loopclosure.hpp"
 #include "cartslam_amd/modules/motionseg.hpp"
 #include "cartslam_amd/modules/objects.hpp"
@@ -136,6 +137,17 @@ int main(int argc, char **argv) {
                     append(o, corrected->pose, sizeof(corrected->pose));
                     auto nodes = run->getData<std::vector<double>>(CARTSLAM_KEY_POSE_GRAPH_NODES);
                     if (!nodes->empty()) writeBin(dump, id, CARTSLAM_KEY_POSE_GRAPH "_nodes", nodes->data(), nodes->size() * sizeof(double));
+                }
+                if (run->hasData(CARTSLAM_KEY_LOCAL_BA)) {   // the 80-byte LocalBARecord, the refined pose as 12 doubles, the window's ids (uint64) and poses, then the published R and t
+                    auto record = run->getData<cart::LocalBARecord>(CARTSLAM_KEY_LOCAL_BA_RESULT);
+                    auto refined = run->getData<cart::EgoMotion>(CARTSLAM_KEY_LOCAL_BA);
+                    auto window = run->getData<cart::LocalBAWindow>(CARTSLAM_KEY_LOCAL_BA_WINDOW);
+                    std::ofstream o = writeBin(dump, id, CARTSLAM_KEY_LOCAL_BA, record.get(), sizeof(*record));
+                    append(o, refined->pose, sizeof(refined->pose));
+                    append(o, window->ids.data(), window->ids.size() * sizeof(uint64_t));
+                    append(o, window->poses.data(), window->poses.size() * sizeof(double));
+                    append(o, refined->result.R, sizeof(refined->result.R));
+                    append(o, refined->result.t, sizeof(refined->result.t));
                 }
                 if (run->hasData(CARTSLAM_KEY_PLANE_MAP)) {   // int64 ox, oz; int32 Nx, Nz; double cell_size; the 16-byte cells; the u8 classes
                     auto pm = run->getData<cart::PlaneMap>(CARTSLAM_KEY_PLANE_MAP);

@@ -996,6 +996,85 @@ int cart_object_tracker_update(cart_object_tracker *obj, const cart_ego_camera *
                                const int16_t *disp_prev, size_t disp_prev_step, const int16_t *flow, size_t flow_step, int width, int height,
                                cart_object *objects_out, cart_track *tracks_out, int32_t *counts_out, void *stream);
 
+/* ---- Windowed bundle adjustment over the last frames (spec S32) -------------------------------------------------
+ * An extension: the reference refines no trajectory.  The object keeps the last `window` frames (their camera-to-world poses as handed
+ * in and as estimated), the points those frames share and one stereo observation (u, v, u_right) per point and frame.  push() builds
+ * the tracks from the frame's keypoints and match lists (integer logic and one back-projection per new point); optimize() runs
+ * Gauss-Newton with a Huber weight over the poses of all frames but the oldest and over every point with enough observations: the
+ * points are eliminated (Schur complement), the reduced system of order 6 (frames - 1) <= 90 is solved by an unpivoted Cholesky.  fp64
+ * with + - * / sqrt only, every sum in one written order (S23's 256 virtual lanes over the point slots), no floating-point atomics:
+ * restated in tests/np_localba.py, byte for byte.
+ *   Ring: push number n (from 0 after a clear) goes to slot n mod window; a full ring drops the frame in that slot (no marginalisation)
+ *   and frees every point that loses its last observation.  est_new = est_prev (odom_prev^-1 odom_new) with S29's products.
+ *   Observation of left index i with stereo match (i, j): u = kpL[i].x, v = kpL[i].y, ur = kpR[j].x, valid iff (double)u - (double)ur >=
+ *   min_disparity.  i continues point p iff it has a valid observation, a temporal match (i, j) and track_of_prev[j] = p is alive; of
+ *   several i that name one p the smallest wins.  Every other valid i is a new point: ascending i take the free slots in ascending
+ *   order, X = est_new applied to the back-projection of (u, v, u - ur); without a free slot the keypoint is dropped.
+ *   Residual of X in a frame with est = (R, t): q = R^T (X - t), skipped unless q.z > 0; eu = ((fx q.x) / q.z + cx) - u, ev likewise,
+ *   er = ((fx (q.x - baseline)) / q.z + cx) - ur; n2 = (eu eu + ev ev) + er er; w = 1 where n2 <= huber^2, else huber / sqrt(n2).
+ *   Update: R <- R Rq(omega), t <- t + R upsilon (S29's), X <- X + dX.  The Jacobians, the elimination, the held frames and every
+ *   operation order: DESIGN.md 7.14.  A pivot of the reduced system that is not > 0 ends the call with status 0 and everything as it was. */
+typedef struct cart_local_ba_params {
+    double min_disparity;                     /* pixels, finite, > 0: S23's test of a stereo observation */
+    double huber;                             /* pixels, finite, > 0 */
+    double damping;                           /* finite, >= 0: added to every diagonal entry of the pose and the point blocks */
+    int32_t iterations;                       /* 0..16 Gauss-Newton steps, no early exit */
+    int32_t min_observations;                 /* 1..16: a point with fewer observations in the window neither contributes nor moves */
+    int32_t min_frame_observations;           /* 0..65536: a free frame with fewer usable observations in a step is held for that step */
+} cart_local_ba_params;
+/* Extension (S32): 1.0, 2.0, 0.0, 4, 2, 6 (build-owned, no data set has tuned them). */
+void cart_local_ba_default_params(cart_local_ba_params *p);
+#define CART_LOCAL_BA_MAX_WINDOW 16
+#define CART_LOCAL_BA_MAX_POINTS 65536
+#define CART_LOCAL_BA_MAX_ITERATIONS 16
+typedef struct cart_local_ba_result {         /* S32; 40 bytes, 8-byte aligned */
+    int32_t status;                           /* 1 = optimised (or nothing to do), 0 = a pivot was not > 0: nothing moved */
+    int32_t n_frames, n_points_active;        /* frames in the window; points with >= min_observations observations */
+    int32_t n_observations;                   /* observations of those points with q.z > 0, before the first step */
+    int32_t n_held;                           /* held frames, added up over the steps */
+    int32_t iterations;
+    double cost_before, cost_after;           /* sum of the Huber costs; cost_after = cost_before with status 0 or nothing to do */
+} cart_local_ba_result;
+
+typedef struct cart_local_ba cart_local_ba;
+/* Extension (S32).  Everything for keypoint lists of up to max_features (1..65536), window in 2..16 frames and max_points in 64..65536
+ * is allocated here: per point 16 window bytes of observations, 48 for the position and its snapshot, 96 for the blocks of a step and
+ * 20 of bookkeeping (2.4 MB at 8 / 8192, 28 MB at 16 / 65536), 28 bytes per feature, 392 per frame and the reduced system of at most
+ * 91 x 90 doubles.  No call allocates.  The sizes are checked before the engine. */
+int cart_local_ba_create(cart_engine *engine, int max_features, int window, int max_points, cart_local_ba **out);
+/* Extension (S32).  Keeps the device it was created on, so it may be destroyed after its engine. */
+void cart_local_ba_destroy(cart_local_ba *ba);
+/* Extension (S32).  Forgets every frame and point; ordered on `stream` like every other call.  The object is stateful in call order. */
+int cart_local_ba_clear(cart_local_ba *ba, void *stream);
+/* Extension (S32).  HOST getter, no device work: the frames in the window and max_points (either pointer may be NULL). */
+int cart_local_ba_size(cart_local_ba *ba, int *frames, int *points_capacity);
+/* Extension (S32).  One frame: pose = HOST double [12], camera-to-world (all finite, |R entries| <= 2, |t entries| <= 1e6); kpL / kpR
+ * = the cart_keypoint records of the left and right image, left_count = the number of left keypoints, stereo_matches with query =
+ * left, train = right, temporal_matches with query = this frame's left, train = the previously pushed frame's left, both with
+ * distinct queries (what cart_matcher_match writes); all DEVICE memory, 4-byte aligned, the counts DEVICE int32 clamped to [0,
+ * max_features]; a match with an index outside [0, left_count) x [0, max_features) is ignored.  The first push after a clear ignores
+ * the temporal list.  counts_out = DEVICE int32 [8] or NULL: {left keypoints, stereo-valid, continued, born, dropped, freed, live
+ * points, frames in window}; it may overlap no input.  Of params only min_disparity is used, all are checked.  Checked in this order,
+ * all before any device call: params, camera, pose, object, then pointers, alignment and overlaps; a refused call launches nothing and
+ * touches no state.  Four launches on `stream`, no host synchronisation. */
+int cart_local_ba_push(cart_local_ba *ba, const cart_ego_camera *camera, const cart_local_ba_params *params, uint64_t frame_id,
+                       const double *pose, const cart_keypoint *kpL, const cart_keypoint *kpR, const int32_t *left_count,
+                       const cart_match *stereo_matches, const int32_t *stereo_count, const cart_match *temporal_matches,
+                       const int32_t *temporal_count, int32_t *counts_out, void *stream);
+/* Extension (S32).  params->iterations Gauss-Newton steps over the window as it stands.  result = DEVICE record (8-byte aligned) or
+ * NULL.  2 + 5 iterations launches on `stream` whatever the counts, no host synchronisation.  Checked in this order: params, camera,
+ * object, then the pointer. */
+int cart_local_ba_optimize(cart_local_ba *ba, const cart_ego_camera *camera, const cart_local_ba_params *params,
+                           cart_local_ba_result *result, void *stream);
+/* Extension (S32).  The window in age order, oldest first: out = DEVICE double [window][12] (8-byte aligned), ids_out = DEVICE uint64
+ * [window] (8-byte aligned, may be NULL); rows past the frames in the window are zero.  The two may not overlap. */
+int cart_local_ba_poses(cart_local_ba *ba, double *out, uint64_t *ids_out, void *stream);
+/* Extension (S32).  Every point slot: out = DEVICE double [max_points][4] (8-byte aligned) = (X, Y, Z, n_obs), zeros in a free slot. */
+int cart_local_ba_points(cart_local_ba *ba, double *out, void *stream);
+/* Extension (S32).  The point slot of every left index of the newest frame, -1 without: out = DEVICE int32 [max_features] (4-byte
+ * aligned). */
+int cart_local_ba_track_of(cart_local_ba *ba, int32_t *out, void *stream);
+
 /* Stand-in for ImageOpticalFlowModule's device work (src/modules/optflow.cpp:96-140: cvtColor x2 +
  * cv::cuda::NvidiaOpticalFlow_2_0::calc(current, previous), NVIDIA fixed-function hardware): dense census block
  * matching (oracle S15).  cur / prev = the reference images of frame id and id-1 (1-channel gray or 3-channel BGR),
