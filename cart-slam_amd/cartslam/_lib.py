@@ -195,6 +195,20 @@ class Track(C.Structure):
 OBJECT_BINS, OBJECT_MAX_OBJECTS, OBJECT_MAX_TRACKS = 512, 256, 256   # CART_OBJECT_*
 
 
+class VoxelMapParams(C.Structure):
+    # mirrors cart_voxel_map_params (include/cart_engine.h, spec S33); the defaults are cart_voxel_map_default_params' (build-owned, untuned)
+    _fields_ = [(n, C.c_double) for n in ("voxel_size", "min_disparity", "min_depth", "max_depth", "truncation", "disparity_sigma", "lookahead", "march_step")] + \
+               [(n, C.c_int32) for n in ("max_weight", "min_weight")]
+
+
+class Voxel(C.Structure):
+    # mirrors cart_voxel (include/cart_engine.h, spec S33)
+    _fields_ = [("tsdf", C.c_int16), ("weight", C.c_uint16)]
+
+
+VOXEL_RAY_NONE, VOXEL_RAY_HIT, VOXEL_RAY_INSIDE = range(3)   # CART_VOXEL_RAY_*
+
+
 FUSION_NONE, FUSION_MEASURED, FUSION_AGREED, FUSION_REPLACED, FUSION_PREDICTED = range(5)   # CART_FUSION_*
 
 
@@ -332,6 +346,14 @@ PROTOTYPES = {
     "cart_local_ba_poses": (_i, [_vp, _vp, _vp, _vp]),
     "cart_local_ba_points": (_i, [_vp, _vp, _vp]),
     "cart_local_ba_track_of": (_i, [_vp, _vp, _vp]),
+    "cart_voxel_map_default_params": (None, [C.POINTER(VoxelMapParams)]),
+    "cart_voxel_map_create": (_i, [_vp, _i, _i, _i, C.POINTER(VoxelMapParams), C.POINTER(_vp)]),
+    "cart_voxel_map_destroy": (None, [_vp]),
+    "cart_voxel_map_clear": (_i, [_vp]),
+    "cart_voxel_map_window": (_i, [_vp, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(_i)]),
+    "cart_voxel_map_integrate": (_i, [_vp, C.POINTER(EgoCamera), C.POINTER(C.c_double), _vp, _sz, _i, _i, _vp, _sz, _vp, _vp]),
+    "cart_voxel_map_raycast": (_i, [_vp, C.POINTER(EgoCamera), C.POINTER(C.c_double), _i, _i, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp]),
+    "cart_voxel_map_read": (_i, [_vp, _vp, C.POINTER(C.c_int64), _vp]),
     "cart_optical_flow": (_i, [_vp, _vp, _sz, _vp, _sz, _i, _i, _i, _vp, _sz, _vp]),
     "cart_flow_default_params": (None, [C.POINTER(FlowParams)]),
     "cart_flow_pyramid_levels": (_i, [_i, _i, _i, C.POINTER(_i), C.POINTER(_i)]),

@@ -10,7 +10,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import DenseEgoParams, EgoCamera, EgoParams, EngineParams, FusionParams, LocalBAParams, MatchParams, MotionParams, ObjectParams, PlaceParams, PlaneMapParams, PlaneParams, PoseGraphParams, SuperpixelParams
+from ._lib import DenseEgoParams, EgoCamera, EgoParams, EngineParams, FusionParams, LocalBAParams, MatchParams, MotionParams, ObjectParams, PlaceParams, PlaneMapParams, PlaneParams, PoseGraphParams, SuperpixelParams, VoxelMapParams
 
 INVALID = -32768  # CARTSLAM_DISPARITY_INVALID, reference include/modules/disparity.hpp:17
 
@@ -1410,6 +1410,93 @@ class DisparityFusion(_DeviceObject):
         if stream is not None:
             stream.synchronize()
         return tuple(t.cpu().numpy() if t is not None else None for t in out)
+
+
+VOXEL_DTYPE = np.dtype([("tsdf", "<i2"), ("weight", "<u2")])   # cart_voxel
+
+
+def voxel_map_params(**fields):
+    """cart_voxel_map_default_params (spec S33; the defaults are build-owned and untuned) with the given fields replaced."""
+    return _default_params(VoxelMapParams, "voxel_map", fields)
+
+
+class VoxelMap(_DeviceObject):
+    """Rolling TSDF voxel map with model raycast (cart_voxel_map_* in the C ABI, spec S33 in DESIGN.md 7.15): a window of cells_x x cells_y x
+    cells_z voxels in the world frame that every frame's disparity is averaged into through the frame's camera-to-world pose, and a
+    raycast of it from any pose in the format of the disparity image.  Stateful: integrate calls must come in frame order.  A context
+    manager; close() destroys the device object."""
+    _name = "voxel_map"
+
+    def __init__(self, engine, cells_x, cells_y, cells_z, params=None):
+        """params = VoxelMapParams (default: voxel_map_params()); fixed for the object's life."""
+        self.cells_x, self.cells_y, self.cells_z = int(cells_x), int(cells_y), int(cells_z)
+        self.params = params if params is not None else voxel_map_params()
+        super().__init__(engine, self.cells_x, self.cells_y, self.cells_z, C.byref(self.params))
+
+    def integrate(self, camera, pose, disp, mask=None, counts=True, raw=False, stream=None):
+        """camera = EgoCamera or (fx, fy, cx, cy, baseline); pose = 12 numbers (3 x 4 camera-to-world, KITTI row order, host); disp int16
+        [h, w] (x16); mask uint8 [h, w] (motion_segment's labels) or None.  Device tensors are taken as they are (rows may be pitched), host
+        arrays go up.  stream = a torch stream (default: the current one).  -> counts int32 [2] (voxels updated, of them with f < 1) as a
+        numpy array, or None when counts is false; raw=True returns the device tensor with no host round trip."""
+        import torch
+        cam = _camera(camera)
+        with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):   # uploads and allocations on the call's stream
+            d, m = _to_device(disp, torch.int16), _to_device(mask, torch.uint8)
+            if not isinstance(d, torch.Tensor) or d.dtype != torch.int16 or d.dim() != 2:
+                raise EngineError("disp must be an int16 [h, w] image")
+            if m is not None:
+                _check_frame_image(m, torch.uint8, "mask", d)
+            n = torch.empty(2, dtype=torch.int32, device=d.device) if counts else None
+        sp = C.c_void_p(stream.cuda_stream) if stream is not None else _stream_ptr()
+        self._check(self._lib.cart_voxel_map_integrate(self._h, C.byref(cam), _pose12(pose), *_pitched(d, 1), int(d.shape[1]), int(d.shape[0]), *_pitched(m, 1),
+                                                       C.c_void_p(n.data_ptr()) if counts else None, sp), "cart_voxel_map_integrate")
+        if raw or n is None:
+            return n
+        if stream is not None:
+            stream.synchronize()
+        return n.cpu().numpy()
+
+    def raycast(self, camera, pose, width, height, weight=True, status=True, counts=True, raw=False, stream=None):
+        """The model seen from `pose` at width x height.  -> (disp_model int16 [h, w], weight uint16 [h, w], status uint8 [h, w], counts
+        int32 [3] = rays NONE, HIT, INSIDE) as numpy arrays, None for an output that was not asked for; raw=True returns the device tensors
+        (weight as int16: the same bits)."""
+        import torch
+        cam = _camera(camera)
+        w, h = int(width), int(height)
+        with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
+            dm = torch.empty((max(h, 0), max(w, 0)), dtype=torch.int16, device="cuda")
+            wm = torch.empty((max(h, 0), max(w, 0)), dtype=torch.int16, device="cuda") if weight else None
+            st = torch.empty((max(h, 0), max(w, 0)), dtype=torch.uint8, device="cuda") if status else None
+            n = torch.empty(3, dtype=torch.int32, device="cuda") if counts else None
+        sp = C.c_void_p(stream.cuda_stream) if stream is not None else _stream_ptr()
+        images = [C.c_void_p(dm.data_ptr()), 2 * max(w, 0)] + ([C.c_void_p(wm.data_ptr()), 2 * max(w, 0)] if weight else [None, 0]) + \
+                 ([C.c_void_p(st.data_ptr()), max(w, 0)] if status else [None, 0])
+        self._check(self._lib.cart_voxel_map_raycast(self._h, C.byref(cam), _pose12(pose), w, h, *images, C.c_void_p(n.data_ptr()) if counts else None, sp),
+                    "cart_voxel_map_raycast")
+        out = (dm, wm, st, n)
+        if raw:
+            return out
+        if stream is not None:
+            stream.synchronize()
+        dm, wm, st, n = (t.cpu().numpy() if t is not None else None for t in out)
+        return dm, (wm.view(np.uint16) if wm is not None else None), st, n
+
+    def window(self):
+        """-> ((ox, oy, oz), (cells_x, cells_y, cells_z), valid): the window origin in absolute voxels; valid is False after create / clear
+        (host getter)."""
+        o, n, valid = (C.c_int64 * 3)(), (C.c_int32 * 3)(), C.c_int(0)
+        self._check(self._lib.cart_voxel_map_window(self._h, o, n, C.byref(valid)), "cart_voxel_map_window")
+        return tuple(o), tuple(n), bool(valid.value)
+
+    def read(self):
+        """-> (voxels VOXEL_DTYPE [cells_z, cells_y, cells_x] in window order, (ox, oy, oz)); synchronises."""
+        voxels = np.empty((self.cells_z, self.cells_y, self.cells_x), VOXEL_DTYPE)
+        o = (C.c_int64 * 3)()
+        self._check(self._lib.cart_voxel_map_read(self._h, C.c_void_p(voxels.ctypes.data), o, _stream_ptr()), "cart_voxel_map_read")
+        return voxels, tuple(o)
+
+    def clear(self):
+        self._check(self._lib.cart_voxel_map_clear(self._h), "cart_voxel_map_clear")
 
 
 OBJECT_DTYPE = np.dtype([("component", "<i4"), ("area", "<i4"), ("x0", "<i4"), ("y0", "<i4"), ("x1", "<i4"), ("y1", "<i4"), ("median_bin", "<i4"), ("n_hist", "<i4"),

@@ -593,6 +593,52 @@ void launch_local_ba_push(const LbaPushArgs &a, hipStream_t s);        // 4 laun
 void launch_local_ba_optimize(const LbaOptArgs &a, hipStream_t s);     // 2 + 5 iterations launches
 void launch_local_ba_poses(const LbaStore &g, int frames, int first_slot, double *out, uint64_t *ids_out, hipStream_t s);
 void launch_local_ba_points(const LbaStore &g, double *out, hipStream_t s);
+// ---- rolling TSDF voxel map with model raycast (voxelmap_kernels.hip) ----
+// Global voxel g lives at (gx mod nx, gy mod ny, gz mod nz), x fastest; window voxel r = g - o therefore lives at (r + m) mod n per axis
+// with m = o mod n.  o and n are multiples of 8, so eight window voxels along x are 32 contiguous, 32-byte aligned bytes.
+#ifndef CART_VOXEL_CULL
+#define CART_VOXEL_CULL 0               // the A/B of DESIGN.md 7.15 builds the library a second time with 1 (groups of slices outside the frustum are skipped): no faster
+#endif
+constexpr int kVoxelSlices = 4;         // z slices one lane of the integrate kernel handles at a time (nz is a multiple of 8)
+#ifndef CART_VOXEL_DEPTH
+#define CART_VOXEL_DEPTH 16             // the A/B of DESIGN.md 7.15 also builds 4: one group of slices per workgroup, four times the workgroups and tickets
+#endif
+constexpr int kVoxelDepth = CART_VOXEL_DEPTH;   // z slices per workgroup of the integrate kernel: a multiple of kVoxelSlices
+constexpr int kVoxelCounters = 8;       // int32 words of the object's counter block, read as four uint64: integrate {updated | near << 32, ticket},
+                                        // raycast {NONE | HIT << 32, INSIDE | ticket << 32}; all zero between calls
+struct VoxelGrid {
+    uint32_t *voxels;                   // [nz][ny][nx] words: tsdf in the low half, weight in the high half
+    int nx, ny, nz, mx, my, mz;
+    double ox, oy, oz;                  // the window origin (|o| < 2^28: exact)
+};
+struct VoxelIntegrateArgs {
+    VoxelGrid grid;
+    cart_ego_camera cam;
+    cart_voxel_map_params p;
+    double pose[12];
+    const int16_t *disp; size_t disp_step;
+    const uint8_t *mask; size_t mask_step;              // may be NULL
+    int32_t *counts;                                    // may be NULL
+    int32_t *counters;
+    int w, h;
+};
+struct VoxelRaycastArgs {
+    VoxelGrid grid;
+    cart_ego_camera cam;
+    cart_voxel_map_params p;
+    double pose[12];
+    int16_t *disp; size_t disp_step;
+    uint16_t *weight; size_t weight_step;               // may be NULL
+    uint8_t *status; size_t status_step;                // may be NULL
+    int32_t *counts;                                    // may be NULL
+    int32_t *counters;
+    int w, h, steps;                                    // steps = K of the spec
+    int empty;                                          // the map has no window: every sample is unknown
+};
+// empties the window box [rx0, rx0 + rw) x [ry0, ry0 + rh) x [rz0, rz0 + rd); rx0 and rw are multiples of 8
+void launch_voxel_clear(const VoxelGrid &grid, int rx0, int rw, int ry0, int rh, int rz0, int rd, hipStream_t s);
+void launch_voxel_integrate(const VoxelIntegrateArgs &a, hipStream_t s);
+void launch_voxel_raycast(const VoxelRaycastArgs &a, hipStream_t s);
 void launch_narrow_copy(const void *src, void *dst, size_t bytes, int blocks, hipStream_t s);
 int kernel_count();
 

@@ -1,0 +1,56 @@
+// modules/voxelmap.hpp -- an extension module (the reference keeps no three-dimensional model): the rolling TSDF voxel map with model
+// raycast through cart_voxel_map_* (include/cart_engine.h), spec DESIGN.md S33.  Every frame's disparity is integrated into one rolling
+// volume through the frame's camera-to-world pose, and the volume is raycast from that pose into "disparity_model", an image in the
+// format of "disparity".  Factory type "voxel_map".
+#pragma once
+#include <array>
+#include <mutex>
+#include <string>
+#include <vector>
+
+#include "../cartslam.hpp"
+#include "cart_engine.h"
+
+#define CARTSLAM_KEY_VOXEL_MAP "voxel_map"                                // VoxelMap
+#define CARTSLAM_KEY_DISPARITY_MODEL "disparity_model"                    // CV_16SC1, the format of "disparity"; empty without "raycast"
+#define CARTSLAM_KEY_DISPARITY_MODEL_STATUS "disparity_model_status"      // CV_8UC1: CART_VOXEL_RAY_*
+#define CARTSLAM_KEY_DISPARITY_MODEL_COUNTS "disparity_model_counts"      // VoxelRayCounts
+
+namespace cart {
+struct VoxelMap {
+    int64_t origin[3] = {0, 0, 0};      // the window's first voxel in absolute voxels
+    int32_t cells[3] = {0, 0, 0};       // cells_x, cells_y, cells_z
+    double voxelSize = 0;
+    int32_t counts[2] = {0, 0};         // of this frame's integrate: voxels updated, of them with f < 1
+    std::vector<cart_voxel> voxels;     // the voxels in window order; filled only when CARTSLAM_VOXEL_MAP_SNAPSHOT is set
+};
+struct VoxelRayCounts {
+    int32_t rays[3] = {0, 0, 0};        // CART_VOXEL_RAY_NONE, _HIT, _INSIDE
+};
+
+// Every default is a build-owned choice that no data set has tuned.
+struct VoxelMapOptions : CameraOptions {   // the factory fills the camera from the data source's Q
+    int cellsX = 256, cellsY = 64, cellsZ = 256;
+    double voxelSize = 0.125, minDisparity = 1.0, minDepth = 0.5, maxDepth = 16.0, truncation = 0.25, disparitySigma = 0.5, lookahead = 8.0,
+           marchStep = 0.125;             // cart_voxel_map_default_params
+    int maxWeight = 64, minWeight = 1;
+    std::string disparityKey = "disparity";   // the blackboard CV_16SC1 image that is integrated; "disparity_fused" = temporal_fusion's
+    std::string poseKey = "ego_motion";       // the blackboard EgoMotion whose accumulated pose the map takes; "dense_ego", "local_ba", "pose_graph"
+    bool useMotion = false;                   // "motion" of this frame masks the integration
+    bool raycast = true;                      // publish the model image of every frame
+};
+
+class VoxelMapModule : public SyncWrapperSystemModule {
+   public:
+    explicit VoxelMapModule(const VoxelMapOptions &options);   // throws std::invalid_argument naming the key that is out of range
+    ~VoxelMapModule();
+    system_data_t runInternal(System &system, SystemRunData &data) override;
+
+   private:
+    const VoxelMapOptions options;
+    const bool snapshot;
+    std::mutex mutex;                 // the frames arrive one at a time (the -1 dependency); this guards the lazy creation
+    cart_voxel_map *map = nullptr;
+    DeviceScratch scratch;            // the one stream; the five counts on the device and the pinned buffer they are downloaded through
+};
+}  // namespace cart

@@ -27,6 +27,7 @@
 #include "cartslam_amd/modules/localba.hpp"
 #include "cartslam_amd/modules/posegraph.hpp"
 #include "cartslam_amd/modules/superpixels.hpp"
+#include "cartslam_amd/modules/voxelmap.hpp"
 
 #define CART_CONFIG_KEY_DATA_SOURCE "data_source"
 #define CART_CONFIG_KEY_MODULES "modules"
@@ -278,6 +279,27 @@ void applyModuleConfig(const Value &modulesConfig, std::shared_ptr<System> syste
             o.interval = get(moduleConfig, "interval", o.interval);
             o.poseKey = get<std::string>(moduleConfig, "pose_key", o.poseKey);   // "dense_ego": the refined trajectory is the odometry
             system->addModule<LocalBAModule>(o);
+        } else if (moduleType == "voxel_map") {  // extension (spec S33): disparity averaged into a rolling TSDF volume through the frame's pose, and its raycast
+            VoxelMapOptions o;
+            readCamera(moduleConfig, *dataSource, o);
+            o.cellsX = get(moduleConfig, "cells_x", o.cellsX);
+            o.cellsY = get(moduleConfig, "cells_y", o.cellsY);
+            o.cellsZ = get(moduleConfig, "cells_z", o.cellsZ);
+            o.voxelSize = get(moduleConfig, "voxel_size", o.voxelSize);
+            o.minDisparity = get(moduleConfig, "min_disparity", o.minDisparity);
+            o.minDepth = get(moduleConfig, "min_depth", o.minDepth);
+            o.maxDepth = get(moduleConfig, "max_depth", o.maxDepth);
+            o.truncation = get(moduleConfig, "truncation", o.truncation);
+            o.disparitySigma = get(moduleConfig, "disparity_sigma", o.disparitySigma);
+            o.lookahead = get(moduleConfig, "lookahead", o.lookahead);
+            o.marchStep = get(moduleConfig, "march_step", o.marchStep);
+            o.maxWeight = get(moduleConfig, "max_weight", o.maxWeight);
+            o.minWeight = get(moduleConfig, "min_weight", o.minWeight);
+            o.disparityKey = get<std::string>(moduleConfig, "disparity_key", o.disparityKey);   // "disparity_fused": the temporally fused image (temporal_fusion)
+            o.poseKey = get<std::string>(moduleConfig, "pose_key", o.poseKey);                 // "dense_ego", "local_ba", "pose_graph": the refined trajectory
+            o.useMotion = get(moduleConfig, "use_motion", o.useMotion);
+            o.raycast = get(moduleConfig, "raycast", o.raycast);
+            system->addModule<VoxelMapModule>(o);
         } else if (endsWith(moduleType, "_visualization")) {
             std::cerr << "[cartconfig] skipping GUI module type " << moduleType << " (out of scope)\n";
         } else {

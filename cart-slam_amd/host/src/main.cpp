@@ -30,6 +30,7 @@
 #include "cartslam_amd/modules/planemap.hpp"
 #include "cartslam_amd/modules/planeseg.hpp"
 #include "cartslam_amd/modules/posegraph.hpp"
+#include "cartslam_amd/modules/voxelmap.hpp"
 
 namespace {
 // --dump: <dir>/<id>_<name>.bin gets `bytes` bytes; what a record has beyond its first part is appended to the returned file
@@ -164,6 +165,26 @@ int main(int argc, char **argv) {
                         std::ofstream r = writeBin(dump, id, CARTSLAM_KEY_PLANE_MAP "_rebuild", counts, sizeof(counts));
                         append(r, pm->rebuildIds.data(), pm->rebuildIds.size() * sizeof(uint64_t));
                     }
+                }
+                if (run->hasData(CARTSLAM_KEY_VOXEL_MAP)) {   // int64 origin [3]; int32 cells [3]; double voxel_size; int32 integrate counts [2], ray counts [3], width, height; the model (int16) and status (u8) images
+                    auto vm = run->getData<cart::VoxelMap>(CARTSLAM_KEY_VOXEL_MAP);
+                    auto rays = run->getData<cart::VoxelRayCounts>(CARTSLAM_KEY_DISPARITY_MODEL_COUNTS);
+                    auto model = run->getData<cart::image_t>(CARTSLAM_KEY_DISPARITY_MODEL);
+                    const int32_t shape[2] = {model->cols, model->rows};   // 0 x 0 without "raycast"
+                    std::ofstream o = writeBin(dump, id, CARTSLAM_KEY_VOXEL_MAP, vm->origin, sizeof(vm->origin));
+                    append(o, vm->cells, sizeof(vm->cells));
+                    append(o, &vm->voxelSize, sizeof(vm->voxelSize));
+                    append(o, vm->counts, sizeof(vm->counts));
+                    append(o, rays->rays, sizeof(rays->rays));
+                    append(o, shape, sizeof(shape));
+                    if (!model->empty()) {
+                        for (const char *k : {CARTSLAM_KEY_DISPARITY_MODEL, CARTSLAM_KEY_DISPARITY_MODEL_STATUS}) {
+                            const auto bytes = run->getData<cart::image_t>(k)->downloadTight();
+                            append(o, bytes.data(), bytes.size());
+                        }
+                    }
+                    if (!vm->voxels.empty())   // with CARTSLAM_VOXEL_MAP_SNAPSHOT: the 4-byte voxels in window order
+                        writeBin(dump, id, CARTSLAM_KEY_VOXEL_MAP "_voxels", vm->voxels.data(), vm->voxels.size() * sizeof(cart_voxel));
                 }
                 if (run->hasData(CARTSLAM_KEY_MOTION)) {   // int32 width, height; the filtered labels, the raw labels, the residual records
                     auto labels = run->getData<cart::image_t>(CARTSLAM_KEY_MOTION);

@@ -1075,6 +1075,92 @@ int cart_local_ba_points(cart_local_ba *ba, double *out, void *stream);
  * aligned). */
 int cart_local_ba_track_of(cart_local_ba *ba, int32_t *out, void *stream);
 
+/* ---- Rolling TSDF voxel map with model raycast (spec S33) ----------------------------------------------------------
+ * An extension: the reference keeps no three-dimensional model.  A rolling window of Nx x Ny x Nz voxels in the world frame; every
+ * frame's disparity is averaged into it as a truncated signed distance through the frame's camera-to-world pose, and a raycast from any
+ * pose gives a model disparity in the format of the disparity image.  fp64 with + - * / floor only, every expression in the written
+ * order, integers after the projection, no floating-point atomic and no atomic on the volume (one lane owns a voxel for a whole call):
+ * restated in tests/np_voxelmap.py, byte for byte.
+ *   Voxel: {int16 tsdf (units of 1 / 32767 of the truncation distance), uint16 weight}, empty = (0, 0).  Global voxel g is stored at
+ *   (gx mod Nx, gy mod Ny, gz mod Nz) (floor modulo), x fastest, whatever the window: a window move copies nothing.
+ *   Window (host, int64, floor division): c_a = floor((t_a + lookahead P[4a + 2]) / voxel_size) per axis a (t_a = P[4a + 3]; the third
+ *   column of R is the optical axis), o_a = 8 floor_div(c_a - N_a / 2, 8).  The first integrate after create / clear starts at o with every
+ *   voxel empty; afterwards the voxels that enter are emptied before the frame is integrated and those that leave are forgotten; a move
+ *   of >= N_a on an axis empties everything.
+ *   Integrate, for every voxel g of the new window, the gates in this order:
+ *     1. p_a = ((double)g_a + 0.5) voxel_size, d = p - t, q_c = (P[c] d_0 + P[4 + c] d_1) + P[8 + c] d_2; q_z >= min_depth
+ *     2. u = (fx q_x) / q_z + cx, v = (fy q_y) / q_z + cy, x = floor(u + 0.5), y = floor(v + 0.5), both inside the image (compared as
+ *        doubles before the conversion; a NaN fails)
+ *     3. s = disp[y][x] != -32768, d = s / 16.0 >= min_disparity, Z = (fx baseline) / d <= max_depth, mask absent or mask[y][x] != 1
+ *     4. tr = truncation + disparity_sigma ((Z Z) / (fx baseline)), sdf = Z - q_z >= -tr
+ *     5. f = sdf / tr, 1.0 where it is larger; obs = (int)floor(f 32767.0 + 0.5)
+ *     6. with the stored (t, w), in int64: t' = floor_div(2 (w t + obs) + (w + 1), 2 (w + 1)), w' = min(w + 1, max_weight)
+ *   A voxel that fails a gate is neither read nor written.
+ *   Raycast of pixel (x, y): K = (int)floor((max_depth - min_depth) / march_step); for k = 0..K, z_k = min_depth + (double)k march_step,
+ *   X = ((x - cx) z_k) / fx, Y = ((y - cy) z_k) / fy, p_w[r] = ((P[4r] X + P[4r+1] Y) + P[4r+2] z_k) + P[4r+3]; per axis a = p_w /
+ *   voxel_size - 0.5, i0 = floor(a), fr = a - i0.  The sample is known iff a window exists, all eight corners i0 + {0,1}^3 lie in it
+ *   (compared as doubles) and each has weight >= min_weight.  F = trilinear in fp64 of the eight tsdf integers: along x
+ *   c = t0 + fr_x (t1 - t0) (the difference in integers), then e0 = c[0][0] + fr_y (c[1][0] - c[0][0]), e1 = c[0][1] + fr_y (c[1][1] -
+ *   c[0][1]) with c[dy][dz], then F = e0 + fr_z (e1 - e0).  An unknown sample forgets the previous one; a known F <= 0 after a known
+ *   previous F_p > 0 is a hit at z* = z_p + (march_step F_p) / (F_p - F) and ends the ray; a known F <= 0 otherwise ends it as INSIDE;
+ *   a known F > 0 becomes the previous sample.  A hit with sw = floor(((fx baseline) / z*) 16.0 + 0.5) in 1..32767 writes sw, status
+ *   HIT and the minimum weight of the eight corners of the sample that closed it; an INSIDE ray writes -32768, weight 0, status INSIDE;
+ *   every other ray -32768, weight 0, status NONE. */
+typedef struct cart_voxel {
+    int16_t tsdf;
+    uint16_t weight;
+} cart_voxel;                                 /* the empty voxel is (0, 0) */
+typedef struct cart_voxel_map_params {
+    double voxel_size;                        /* metres, finite, >= 0.01 */
+    double min_disparity;                     /* pixels, finite, > 0 */
+    double min_depth;                         /* metres, finite, > 0 */
+    double max_depth;                         /* metres, finite, > min_depth */
+    double truncation;                        /* metres, finite, > 0 */
+    double disparity_sigma;                   /* pixels, finite, >= 0: the truncation grows by sigma Z^2 / (fx baseline) */
+    double lookahead;                         /* metres, finite, |.| <= 1000: the window's centre lies this far along the optical axis */
+    double march_step;                        /* metres, finite, 0 < march_step <= truncation, at most 8192 steps */
+    int32_t max_weight;                       /* 1..65535 */
+    int32_t min_weight;                       /* 1..65535 */
+} cart_voxel_map_params;
+/* extension: 0.125, 1.0, 0.5, 16.0, 0.25, 0.5, 8.0, 0.125, 64, 1 (build-owned, untuned) */
+void cart_voxel_map_default_params(cart_voxel_map_params *p);
+#define CART_VOXEL_RAY_NONE 0
+#define CART_VOXEL_RAY_HIT 1
+#define CART_VOXEL_RAY_INSIDE 2
+
+typedef struct cart_voxel_map cart_voxel_map;
+/* Extension.  cells_x, cells_y, cells_z: multiples of 8 in 16..1024 with a product of at most 2^26 (4 bytes per voxel).  The parameters
+ * are fixed for the object's life.  Stateful: calls on one object must be issued in frame order.  The sizes and params are checked
+ * before the engine, so a configuration can be validated without a device. */
+int cart_voxel_map_create(cart_engine *engine, int cells_x, int cells_y, int cells_z, const cart_voxel_map_params *params,
+                          cart_voxel_map **out);
+/* Extension.  Keeps the device it was created on, so it may be destroyed after its engine. */
+void cart_voxel_map_destroy(cart_voxel_map *map);
+/* Extension.  Forgets the window: the next integrate starts an empty one.  No device work. */
+int cart_voxel_map_clear(cart_voxel_map *map);
+/* Extension.  HOST getter: origin3 = int64 [3] (absolute voxels, zeros without a window), shape3 = int32 [3] (cells_x, cells_y,
+ * cells_z), *valid = 0 after create / clear. */
+int cart_voxel_map_window(cart_voxel_map *map, int64_t *origin3, int32_t *shape3, int *valid);
+/* Extension.  One frame: pose = HOST double [12] (3 x 4 camera-to-world as cart_plane_map_update's); disp = device int16 x16, mask =
+ * device u8 labels of cart_motion_segment or NULL, both width x height (1..16384 each), steps in bytes; counts = DEVICE int32 [2]
+ * (4-byte aligned, may be NULL: then no counter is touched) = voxels updated, of them with f < 1.  Moves the window, empties what
+ * entered it (at most one launch per axis that moved, or one for the whole grid), integrates (one launch).  Checked in this order, all
+ * before any device call: camera, pose, sizes, the object, then pointers, alignment, steps and overlaps (counts against disp and mask); a
+ * refused call launches nothing and leaves the window where it was.  No host synchronisation. */
+int cart_voxel_map_integrate(cart_voxel_map *map, const cart_ego_camera *camera, const double *pose, const int16_t *disp,
+                             size_t disp_step, int width, int height, const uint8_t *mask, size_t mask_step, int32_t *counts,
+                             void *stream);
+/* Extension.  The model seen from `pose` at width x height: disp_model = device int16 x16; weight_model = device uint16, status =
+ * device u8 (CART_VOXEL_RAY_*), counts = DEVICE int32 [3] = rays NONE, HIT, INSIDE; the last three may be NULL.  Reads the volume only:
+ * the window does not move.  No output may overlap another: each pair is refused by name.  Checked in the order of
+ * cart_voxel_map_integrate.  One launch, no host synchronisation. */
+int cart_voxel_map_raycast(cart_voxel_map *map, const cart_ego_camera *camera, const double *pose, int width, int height,
+                           int16_t *disp_model, size_t disp_model_step, uint16_t *weight_model, size_t weight_model_step,
+                           uint8_t *status, size_t status_step, int32_t *counts, void *stream);
+/* Extension.  Test / dump access: synchronises `stream` and copies the window's voxels in window order [cells_z][cells_y][cells_x]
+ * into host_voxels (HOST); without a window every voxel is empty and the origin is (0, 0, 0).  origin3 = int64 [3]. */
+int cart_voxel_map_read(cart_voxel_map *map, cart_voxel *host_voxels, int64_t *origin3, void *stream);
+
 /* Stand-in for ImageOpticalFlowModule's device work (src/modules/optflow.cpp:96-140: cvtColor x2 +
  * cv::cuda::NvidiaOpticalFlow_2_0::calc(current, previous), NVIDIA fixed-function hardware): dense census block
  * matching (oracle S15).  cur / prev = the reference images of frame id and id-1 (1-channel gray or 3-channel BGR),
