@@ -203,7 +203,8 @@ struct PfFitArgs {
     const uint16_t *labels; size_t lstep;
     int w, h, L1;
     uint64_t seed, frame;
-    const int32_t *cnt, *npts, *start, *err;
+    const int32_t *cnt, *npts, *start;
+    const int32_t *err;       // the label_planes call's own flag (cart_planefit.lp_err): non-zero -> n_planes = -1
     const float4 *pts;
     const double *planes17;   // [L1][4]
     PfFitState *state;
@@ -215,7 +216,8 @@ struct PfFitArgs {
 };
 int pf_tiles(int w, int h);   // 1024-pixel raster tiles of the point sort
 void launch_pf_points(const uint16_t *labels, size_t lstep, const float *xyz, size_t xstep, int w, int h, int L1, int pred,
-                      int32_t *cursor, int ntiles, int32_t *cnt, int32_t *npts, int32_t *start, float4 *pts, int32_t *err, hipStream_t s);
+                      int32_t *cursor, int ntiles, int32_t *cnt, int32_t *npts, int32_t *start, float4 *pts, int32_t *err, int32_t *lp_err,
+                      hipStream_t s);   // a label >= L1 sets bit 0 of *err and of *lp_err
 void launch_pf_ransac(const float4 *pts, const int32_t *start, const int32_t *npts, int L1, double thr, uint64_t seed, uint64_t frame,
                       double *planes, hipStream_t s);
 void launch_pf_adjacency(const uint16_t *labels, size_t lstep, int w, int h, int L1, uint32_t *bits, int32_t *cnt, int32_t *off,

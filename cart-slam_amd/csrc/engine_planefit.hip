@@ -16,7 +16,9 @@ struct cart_planefit : DeviceObject {
     int32_t *cnt = nullptr;       // [cap_L1][2]
     int32_t *npts = nullptr;      // [cap_L1]
     int32_t *start = nullptr;     // [cap_L1 + 1]
-    int32_t *err = nullptr;       // label out of range (bit 0), adjacency capacity (bit 1)
+    int32_t *err = nullptr;       // [2] words.  [0], cleared by label_planes and by adjacency (cart_planefit_status): label out of range
+                                  // (bit 0), adjacency capacity (bit 1)
+    int32_t *lp_err = nullptr;    // = err + 1, cleared by label_planes alone: label out of range in the call cart_planefit_fit rests on
     float4 *pts = nullptr;        // [w*h]
     double *planes17 = nullptr;   // [cap_L1][4]
     uint32_t *bits = nullptr;     // [cap_L1][words] adjacency bitmap (allocated by the first adjacency call)
@@ -32,6 +34,9 @@ int pf_grid_slots(int w, int h) {   // selectRandomSuperpixels(4, 3) positions (
     const int ys = h / 5, xs = w / 6;
     return (ys > 0 && xs > 0) ? ((h - 1) / ys) * ((w - 1) / xs) : 0;
 }
+Extent pf_xyz_extent(const float *xyz, size_t step, const Geometry &g) {   // CV_32FC3: 12-byte pixels, pointer and step on 4 bytes
+    return Extent{"xyz", xyz, step, 4, (size_t)g.w * 12, g.h};
+}
 }  // namespace
 
 int cart_planefit_create(cart_engine *e, int max_label_capacity, cart_planefit **out) {
@@ -45,13 +50,14 @@ int cart_planefit_create(cart_engine *e, int max_label_capacity, cart_planefit *
     pf->cap_L1 = max_label_capacity + 1; pf->ntiles = pf_tiles(g.w, g.h);
     const size_t L1 = (size_t)pf->cap_L1;
     if (pf->alloc(&pf->cursor, (size_t)pf->ntiles * L1 * 4) || pf->alloc(&pf->cnt, L1 * 8) || pf->alloc(&pf->npts, L1 * 4) ||
-        pf->alloc(&pf->start, (L1 + 1) * 4) || pf->alloc(&pf->err, 4) || pf->alloc(&pf->pts, g.npx * sizeof(float4)) ||
+        pf->alloc(&pf->start, (L1 + 1) * 4) || pf->alloc(&pf->err, 8) || pf->alloc(&pf->pts, g.npx * sizeof(float4)) ||
         pf->alloc(&pf->planes17, L1 * 32) || pf->alloc(&pf->adj_cnt, L1 * 4) || pf->alloc(&pf->state, sizeof(PfFitState)) ||
-        pf->alloc(&pf->local, (size_t)kPfMaxLocal * 32) || pf->alloc(&pf->accept, L1 * 8) || hipMemset(pf->err, 0, 4) != hipSuccess ||
+        pf->alloc(&pf->local, (size_t)kPfMaxLocal * 32) || pf->alloc(&pf->accept, L1 * 8) || hipMemset(pf->err, 0, 8) != hipSuccess ||
         pf->create_event()) {
         destroy_object(pf);
         return fail("allocating the planefit workspaces failed");
     }
+    pf->lp_err = pf->err + 1;
     *out = pf;
     return 0;
 }
@@ -67,16 +73,16 @@ int cart_planefit_label_planes(cart_planefit *pf, const uint16_t *labels, size_t
     if (predicate != CART_PLANE_PREDICATE_PLANEFIT && predicate != CART_PLANE_PREDICATE_PLANECLUSTER) return fail("unknown predicate");
     if (!(thr > 0)) return fail("thr must be positive");
     const Geometry &g = pf->g;
-    if (labels_step < (size_t)g.w * 2 || (labels_step & 1) || xyz_step < (size_t)g.w * 12 || (xyz_step & 3)) return fail("bad step");
+    if (check_pitched(Extent::image("labels", labels, labels_step, 2, g.w, g.h)) || check_pitched(pf_xyz_extent(xyz, xyz_step, g))) return -1;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     ObjectCall call(*pf, stream);
     if (call.begin()) return -1;
     const int L1 = max_label + 1;
     HIP_TRY(hipMemsetAsync(pf->cursor, 0, (size_t)pf->ntiles * L1 * 4, stream));
     HIP_TRY(hipMemsetAsync(pf->cnt, 0, (size_t)L1 * 8, stream));
-    HIP_TRY(hipMemsetAsync(pf->err, 0, 4, stream));
+    HIP_TRY(hipMemsetAsync(pf->err, 0, 8, stream));   // both words: the status flag and this call's own
     launch_pf_points(labels, labels_step, xyz, xyz_step, g.w, g.h, L1, predicate, pf->cursor, pf->ntiles, pf->cnt, pf->npts, pf->start,
-                     pf->pts, pf->err, stream);
+                     pf->pts, pf->err, pf->lp_err, stream);
     launch_pf_ransac(pf->pts, pf->start, pf->npts, L1, thr, seed, frame_id, pf->planes17, stream);
     HIP_TRY(hipGetLastError());
     if (planes) HIP_TRY(hipMemcpyAsync(planes, pf->planes17, (size_t)L1 * 32, hipMemcpyDeviceToDevice, stream));
@@ -109,7 +115,7 @@ int cart_planefit_adjacency(cart_planefit *pf, const uint16_t *labels, size_t la
     if (!labels || !offsets || !neighbours) return fail("NULL pointer");
     if (max_label < 0 || max_label + 1 > pf->cap_L1) return fail("max_label must be in [0, max_label_capacity]");
     const Geometry &g = pf->g;
-    if (labels_step < (size_t)g.w * 2 || (labels_step & 1)) return fail("bad step");
+    if (check_pitched(Extent::image("labels", labels, labels_step, 2, g.w, g.h))) return -1;
     const size_t L1 = (size_t)max_label + 1;
     if (capacity < std::min(8 * g.npx, L1 * (L1 - 1))) return fail("capacity must be >= min(8 * width * height, (max_label + 1) * max_label)");
     hipStream_t stream = static_cast<hipStream_t>(stream_);
@@ -119,7 +125,7 @@ int cart_planefit_adjacency(cart_planefit *pf, const uint16_t *labels, size_t la
     if (!pf->bits && pf->alloc(&pf->bits, (size_t)pf->cap_L1 * words * 4)) return -1;
     const size_t used_words = (L1 + 31) / 32;
     HIP_TRY(hipMemsetAsync(pf->bits, 0, L1 * used_words * 4, stream));
-    HIP_TRY(hipMemsetAsync(pf->err, 0, 4, stream));
+    HIP_TRY(hipMemsetAsync(pf->err, 0, 4, stream));   // the status flag only: lp_err stays with the label_planes call that fit uses
     launch_pf_adjacency(labels, labels_step, g.w, g.h, (int)L1, pf->bits, pf->adj_cnt, offsets, neighbours, capacity, pf->err, stream);
     HIP_TRY(hipGetLastError());
     return 0;
@@ -132,14 +138,14 @@ int cart_planefit_fit(cart_planefit *pf, const uint16_t *labels, size_t labels_s
     if (pf->last_L1 == 0 || pf->last_pred != CART_PLANE_PREDICATE_PLANEFIT)
         return fail("cart_planefit_fit needs a preceding label_planes call with CART_PLANE_PREDICATE_PLANEFIT");
     const Geometry &g = pf->g;
-    if (labels_step < (size_t)g.w * 2 || (labels_step & 1)) return fail("bad step");
+    if (check_pitched(Extent::image("labels", labels, labels_step, 2, g.w, g.h))) return -1;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     ObjectCall call(*pf, stream);
     if (call.begin()) return -1;
     PfFitArgs a;
     std::memset(&a, 0, sizeof(a));
     a.labels = labels; a.lstep = labels_step; a.w = g.w; a.h = g.h; a.L1 = pf->last_L1; a.seed = seed; a.frame = frame_id;
-    a.cnt = pf->cnt; a.npts = pf->npts; a.start = pf->start; a.err = pf->err; a.pts = pf->pts; a.planes17 = pf->planes17;
+    a.cnt = pf->cnt; a.npts = pf->npts; a.start = pf->start; a.err = pf->lp_err; a.pts = pf->pts; a.planes17 = pf->planes17;
     a.state = pf->state; a.local = pf->local; a.accept = pf->accept; a.planes_out = planes; a.assign = assignments; a.nplanes_out = n_planes;
     const int n = launch_pf_fit(a, stream);
     HIP_TRY(hipGetLastError());

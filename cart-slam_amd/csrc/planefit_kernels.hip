@@ -78,7 +78,7 @@ struct TileArgs {
     int32_t *cnt;        // [L1][2] all, invalid
     const int32_t *start;
     float4 *pts;
-    int32_t *err;
+    int32_t *err, *lp_err;   // label out of range: the status word and the word cart_planefit_fit reads
 };
 
 // One wave walks tile t chunk by chunk and handles the chunk label run by label run (ballot of the lanes that share the
@@ -106,7 +106,7 @@ __global__ __launch_bounds__(256) void pf_tile_kernel(TileArgs a) {
 #pragma unroll
     for (int c = 0; c < kChunks; ++c) {
         bool act = lab[c] >= 0;
-        if (act && lab[c] >= a.L1) { act = false; if (!kScatter) atomicOr(a.err, 1); }
+        if (act && lab[c] >= a.L1) { act = false; if (!kScatter) { atomicOr(a.err, 1); atomicOr(a.lp_err, 1); } }
         const bool val = act && pf_valid(z[c], a.pred);
         uint64_t pending = __ballot(act);
         const uint64_t vmask = __ballot(val);
@@ -464,8 +464,9 @@ __global__ __launch_bounds__(256) void pf_fit_inliers_kernel(PfFitArgs a) {
 static_assert(kPfMaxLocal <= 64, "accept masks are 64-bit");
 
 void launch_pf_points(const uint16_t *labels, size_t lstep, const float *xyz, size_t xstep, int w, int h, int L1, int pred,
-                      int32_t *cursor, int ntiles, int32_t *cnt, int32_t *npts, int32_t *start, float4 *pts, int32_t *err, hipStream_t s) {
-    TileArgs a{labels, lstep, xyz, xstep, w, h, L1, pred, ntiles, cursor, cnt, start, pts, err};
+                      int32_t *cursor, int ntiles, int32_t *cnt, int32_t *npts, int32_t *start, float4 *pts, int32_t *err, int32_t *lp_err,
+                      hipStream_t s) {
+    TileArgs a{labels, lstep, xyz, xstep, w, h, L1, pred, ntiles, cursor, cnt, start, pts, err, lp_err};
     const dim3 tg((ntiles + 3) / 4);
     hipLaunchKernelGGL(pf_tile_kernel<false>, tg, dim3(256), 0, s, a);
     hipLaunchKernelGGL(pf_colscan_kernel, dim3((L1 + 255) / 256), dim3(256), 0, s, cursor, ntiles, L1, npts);

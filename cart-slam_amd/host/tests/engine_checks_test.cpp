@@ -32,6 +32,12 @@ int main() {
     assert(check_pitched(big) == 0 && big.end() > big.begin());
     assert(failed_with(check_pitched(Extent::image("odd", at(0x1001), 64, 2, 16, 4)), "odd and its step must be 2-byte aligned"));
     assert(failed_with(check_pitched(Extent::image("odd", at(0x1000), 63, 2, 16, 4)), "odd and its step must be 2-byte aligned"));
+    // 12-byte pixels on 4-byte alignment (CV_32FC3, built by hand as cart_planefit_label_planes does): the row is 12 * w, the alignment 4
+    const auto xyz = [&](uintptr_t a, size_t step) { return Extent{"xyz", at(a), step, 4, (size_t)67 * 12, 9}; };
+    assert(check_pitched(xyz(0x1004, 804)) == 0 && check_pitched(xyz(0x1000, 808)) == 0 && xyz(0x1004, 808).end() == 0x1004 + 8 * 808 + 804);
+    assert(failed_with(check_pitched(xyz(0x1000, 800)), "xyz_step is below the row size"));
+    assert(failed_with(check_pitched(xyz(0x1002, 804)), "xyz and its step must be 4-byte aligned"));
+    assert(failed_with(check_pitched(xyz(0x1000, 806)), "xyz and its step must be 4-byte aligned"));
     // an output that ends exactly where an input begins does not overlap it; one byte further it does
     const Extent in = Extent::image("in", at(0x2000), 64, 1, 64, 4), none = Extent::image("none", nullptr, 0, 1, 64, 4);
     const Extent before = Extent::image("out", at(0x2000 - 4 * 64), 64, 1, 64, 4), into = Extent::image("out", at(0x2000 - 4 * 64 + 1), 64, 1, 64, 4);

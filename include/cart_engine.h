@@ -376,7 +376,9 @@ int cart_planefit_create(cart_engine *engine, int max_label_capacity, cart_plane
 /* Keeps the device and image size it was created with, so it may be destroyed after its engine (as the plane schedule may). */
 void cart_planefit_destroy(cart_planefit *pf);
 /* S17 for every label 0..max_label (replaces planefit.cu:366-384 + plane.cpp:102-180, planecluster.cpp:31-67).  labels =
- * CV_16UC1, xyz = CV_32FC3 "depth" (device, steps in bytes).  Keeps the per-label statistics, point lists and planes in the
+ * CV_16UC1, xyz = CV_32FC3 "depth" (device, steps in bytes; labels and its step on 2 bytes, xyz and its step on 4, each step
+ * at least a row: "<name> and its step must be N-byte aligned", "<name>_step is below the row size"; the same for the labels
+ * of cart_planefit_adjacency and cart_planefit_fit).  Keeps the per-label statistics, point lists and planes in the
  * object for cart_planefit_fit / cart_planefit_points.  Optional device outputs (NULL = not written): planes [max_label+1][4]
  * f64, npoints [max_label+1] (points passing the predicate), counts [max_label+1][2] (all pixels, pixels failing the
  * predicate; planefit.cu:39-77).  Labels > max_label are not counted and are reported by cart_planefit_status. */
@@ -395,11 +397,14 @@ int cart_planefit_adjacency(cart_planefit *pf, const uint16_t *labels, size_t la
 /* S19 on the device (replaces planefit.cu:386-445 incl. attemptAssignment and selectRandomSuperpixels): uses the last
  * label_planes call, which must have used CART_PLANE_PREDICATE_PLANEFIT.  Device outputs: planes [100][4] f64 (the first
  * *n_planes rows are set), assignments [max_label+1] u64 (1 + plane index, 0 = none), n_planes (int32; -1 when the label
- * image held a label > max_label).  *launches (host, may be NULL) = kernel launches queued.  No host synchronisation. */
+ * image of that label_planes call held a label > max_label: then assignments are all 0 and planes is not written.  The flag
+ * belongs to the label_planes call and only the next label_planes call clears it; a cart_planefit_adjacency call in between
+ * does not).  *launches (host, may be NULL) = kernel launches queued.  No host synchronisation. */
 int cart_planefit_fit(cart_planefit *pf, const uint16_t *labels, size_t labels_step, uint64_t seed, uint64_t frame_id,
                       double *planes, uint64_t *assignments, int32_t *n_planes, int *launches, void *stream);
-/* Synchronises the object's last stream; *bad_labels = 1 if a label image given since the last label_planes / adjacency
- * call held a label above its max_label (those pixels were left out). */
+/* Synchronises the object's last stream; *bad_labels = 1 if the label image of the last label_planes / adjacency call held a
+ * label above its max_label (those pixels were left out).  Each of the two calls clears this flag when it starts, so it speaks
+ * of the most recent of them; what cart_planefit_fit reports through n_planes is kept apart (see there). */
 int cart_planefit_status(cart_planefit *pf, int *bad_labels);
 /* S18 on the HOST (replaces planecluster.cpp:44-177): planes = [max_label+1][4] S17 planes (CART_PLANE_PREDICATE_PLANECLUSTER),
  * offsets / neighbours = the adjacency CSR (host copies).  Outputs: planes_out [max_label+1][4] (the first *n_planes rows),

@@ -52,11 +52,14 @@ def valid_mask(z, predicate):
 
 
 def label_points(labels, xyz, max_label, predicate):
-    """-> (counts [L+1,2] int64 (all, invalid), offsets [L+2], points [n,3] float32 in label-major raster order)."""
+    """-> (counts [L+1,2] int64 (all, invalid), offsets [L+2], points [n,3] float32 in label-major raster order).
+    Pixels whose label is above max_label are left out of everything (the device reports them through its status)."""
     lab = np.asarray(labels).astype(np.int64).ravel()
     pts = np.asarray(xyz, dtype=np.float32).reshape(-1, 3)
-    ok = valid_mask(pts[:, 2], predicate)
     L1 = max_label + 1
+    keep = lab < L1
+    lab, pts = lab[keep], pts[keep]
+    ok = valid_mask(pts[:, 2], predicate)
     counts = np.zeros((L1, 2), np.int64)
     counts[:, 0] = np.bincount(lab, minlength=L1)[:L1]
     counts[:, 1] = np.bincount(lab[~ok], minlength=L1)[:L1]
@@ -193,7 +196,8 @@ def label_planes(labels, xyz, max_label, predicate, seed, frame_id, thr=THR17):
 
 # ---- adjacency --------------------------------------------------------------------------------------------------------
 def adjacency(labels, max_label):
-    """8-neighbour label sets (planecluster.cpp:72-96) as CSR (offsets [L+2], ascending neighbours)."""
+    """8-neighbour label sets (planecluster.cpp:72-96) as CSR (offsets [L+2], ascending neighbours).  A pair with a label above
+    max_label on either side is dropped."""
     lab = np.asarray(labels).astype(np.int64)
     h, w = lab.shape
     L1 = max_label + 1
@@ -201,7 +205,7 @@ def adjacency(labels, max_label):
     for dy, dx in ((0, 1), (1, -1), (1, 0), (1, 1)):
         a = lab[0:h - dy, max(0, -dx):w - max(0, dx)]
         b = lab[dy:h, max(0, dx):w - max(0, -dx)]
-        m = a != b
+        m = (a != b) & (a < L1) & (b < L1)
         key = np.unique(a[m] * L1 + b[m])
         pairs.update(key.tolist())
         key = np.unique(b[m] * L1 + a[m])
@@ -302,8 +306,10 @@ def fit_distance(pl, P):
         return np.abs(a * P[:, 0] + b * P[:, 1] + c * P[:, 2] + d) / np.float64(math.sqrt(a * a + b * b + c * c))
 
 
-def planefit(labels, xyz, max_label, seed, frame_id, planes17=None):
-    """S19 -> (planes [k,4], assignments [L+1] uint64, iterations run)."""
+def planefit(labels, xyz, max_label, seed, frame_id, planes17=None, trace=None):
+    """S19 -> (planes [k,4], assignments [L+1] uint64, iterations run).  trace: a list that receives one dict per iteration:
+    "labels" (the sampled labels that gave the local planes, in order), "local" (their number), "votes" (accepting labels of
+    the winner; None when <= 3 local planes skipped the iteration), "accepted"."""
     lab = np.asarray(labels)
     h, w = lab.shape
     counts, offsets, pts = label_points(lab, xyz, max_label, PRED_PLANEFIT)
@@ -322,12 +328,16 @@ def planefit(labels, xyz, max_label, seed, frame_id, planes17=None):
     while assigned / float(L1) < 0.9 and it < 100:
         i = it
         it += 1
-        local = []
+        local, sampled = [], []
         for (x, y) in sample_positions(w, h, seed, frame_id, i):
             l = int(lab[y, x])
             if assign[l] != 0 or not valid[l] or npts[l] < MIN_POINTS:
                 continue
             local.append(tuple(float(v) for v in planes17[l]))
+            sampled.append(l)
+        step = {"labels": sampled, "local": len(local), "votes": None, "accepted": False}
+        if trace is not None:
+            trace.append(step)
         if len(local) <= 3:
             continue
         acc = np.zeros(len(local), np.int64)
@@ -345,8 +355,10 @@ def planefit(labels, xyz, max_label, seed, frame_id, planes17=None):
         for k in range(len(local)):
             if acc[k] > bc:
                 best, bc = k, acc[k]
+        step["votes"] = len(accepting[best])
         if len(accepting[best]) < 16:
             continue
+        step["accepted"] = True
         planes.append(local[best])
         for l in accepting[best]:
             assign[l] = len(planes)

@@ -159,6 +159,37 @@ def test_cluster_rejects_null_and_bad_tables():
         plane_cluster(np.zeros((4, 4)), np.array([-1, 1, 3, 5, 6], np.int32), nb)
 
 
+def test_cluster_refusals_by_message_write_nothing():
+    """Every refusal of cart_plane_cluster by its words; the outputs keep their sentinel."""
+    from cartslam import _lib
+    lib = _lib.load()
+    off, nb = _chain_graph(4)
+    planes = np.zeros((4, 4))
+    out, assign, n = np.full((4, 4), -7777.25), np.full(4, 0x5A5B5C5D5E5F6061, np.uint64), C.c_int(-77)
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p)
+
+    def call(max_label=3, planes=planes, off=off, nb=nb, out=out, assign=assign, n=n):
+        return lib.cart_plane_cluster(ptr(planes) if planes is not None else None, max_label, ptr(off) if off is not None else None,
+                                      ptr(nb) if nb is not None else None, ptr(out) if out is not None else None,
+                                      ptr(assign) if assign is not None else None, C.byref(n) if n is not None else None)
+
+    def refused(rc, words):
+        err = lib.cart_last_error(None).decode()
+        assert rc != 0 and words in err, (rc, words, err)
+        assert (out == -7777.25).all() and (assign == 0x5A5B5C5D5E5F6061).all() and n.value == -77
+
+    for name in ("planes", "off", "nb", "out", "assign", "n"):
+        refused(call(**{name: None}), "NULL pointer")
+    for bad in (-1, 16384):
+        refused(call(max_label=bad), "max_label must be in [0, 16383]")
+    refused(call(off=np.array([1, 1, 3, 5, 6], np.int32)), "offsets[0] must be 0")
+    refused(call(off=np.array([-1, 1, 3, 5, 6], np.int32)), "offsets[0] must be 0")
+    refused(call(off=np.array([0, 3, 1, 5, 6], np.int32)), "offsets are not ascending")
+    refused(call(nb=np.array([1, 0, 2, 1, 4, 2], np.int32)), "neighbour label out of range")
+    refused(call(nb=np.array([1, 0, 2, 1, -1, 2], np.int32)), "neighbour label out of range")
+    assert call() == 0 and n.value == 0 and (assign == 0).all() and (out == -7777.25).all()      # zero planes: no group, no plane row written
+
+
 # ---- S19 ---------------------------------------------------------------------------------------------------------
 def _scene(w, h, bs, invalid_frac, rng):
     lab = ((np.arange(h)[:, None] // bs) * ((w + bs - 1) // bs) + np.arange(w)[None, :] // bs).astype(np.uint16)
