@@ -209,6 +209,20 @@ class Voxel(C.Structure):
 VOXEL_RAY_NONE, VOXEL_RAY_HIT, VOXEL_RAY_INSIDE = range(3)   # CART_VOXEL_RAY_*
 
 
+class ModelTrackParams(C.Structure):
+    # mirrors cart_model_track_params (include/cart_engine.h, spec S34); the defaults are cart_model_track_default_params' (build-owned, untuned)
+    _fields_ = [(n, C.c_double) for n in ("residual_gate", "damping")] + [(n, C.c_int32) for n in ("iterations", "stride", "min_inliers")]
+
+
+class ModelTrackResult(C.Structure):
+    # mirrors cart_model_track_result (include/cart_engine.h, spec S34): the layout of cart_dense_ego_result
+    _fields_ = [("R", C.c_double * 9), ("t", C.c_double * 3), ("rms_initial", C.c_double), ("rms", C.c_double)] + \
+               [(n, C.c_int32) for n in ("status", "n_candidates", "n_initial", "n_inliers", "steps", "reserved")]
+
+
+MODEL_TRACK_MAX_ITERATIONS = 16   # CART_MODEL_TRACK_MAX_ITERATIONS
+
+
 FUSION_NONE, FUSION_MEASURED, FUSION_AGREED, FUSION_REPLACED, FUSION_PREDICTED = range(5)   # CART_FUSION_*
 
 
@@ -354,6 +368,10 @@ PROTOTYPES = {
     "cart_voxel_map_integrate": (_i, [_vp, C.POINTER(EgoCamera), C.POINTER(C.c_double), _vp, _sz, _i, _i, _vp, _sz, _vp, _vp]),
     "cart_voxel_map_raycast": (_i, [_vp, C.POINTER(EgoCamera), C.POINTER(C.c_double), _i, _i, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp]),
     "cart_voxel_map_read": (_i, [_vp, _vp, C.POINTER(C.c_int64), _vp]),
+    "cart_model_track_default_params": (None, [C.POINTER(ModelTrackParams)]),
+    "cart_model_track_create": (_i, [_vp, _i, _i, C.POINTER(_vp)]),
+    "cart_model_track_destroy": (None, [_vp]),
+    "cart_model_track_refine": (_i, [_vp, _vp, C.POINTER(EgoCamera), C.POINTER(C.c_double), C.POINTER(ModelTrackParams), _vp, _sz, _vp, _sz, _i, _i, _vp, _vp]),
     "cart_optical_flow": (_i, [_vp, _vp, _sz, _vp, _sz, _i, _i, _i, _vp, _sz, _vp]),
     "cart_flow_default_params": (None, [C.POINTER(FlowParams)]),
     "cart_flow_pyramid_levels": (_i, [_i, _i, _i, C.POINTER(_i), C.POINTER(_i)]),

@@ -10,7 +10,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import DenseEgoParams, EgoCamera, EgoParams, EngineParams, FusionParams, LocalBAParams, MatchParams, MotionParams, ObjectParams, PlaceParams, PlaneMapParams, PlaneParams, PoseGraphParams, SuperpixelParams, VoxelMapParams
+from ._lib import DenseEgoParams, ModelTrackParams, EgoCamera, EgoParams, EngineParams, FusionParams, LocalBAParams, MatchParams, MotionParams, ObjectParams, PlaceParams, PlaneMapParams, PlaneParams, PoseGraphParams, SuperpixelParams, VoxelMapParams
 
 INVALID = -32768  # CARTSLAM_DISPARITY_INVALID, reference include/modules/disparity.hpp:17
 
@@ -1497,6 +1497,52 @@ class VoxelMap(_DeviceObject):
 
     def clear(self):
         self._check(self._lib.cart_voxel_map_clear(self._h), "cart_voxel_map_clear")
+
+
+MODEL_TRACK_RESULT_DTYPE = np.dtype([("R", "<f8", 9), ("t", "<f8", 3), ("rms_initial", "<f8"), ("rms", "<f8"), ("status", "<i4"), ("n_candidates", "<i4"),
+                                     ("n_initial", "<i4"), ("n_inliers", "<i4"), ("steps", "<i4"), ("reserved", "<i4")])   # cart_model_track_result
+
+
+def model_track_params(**fields):
+    """cart_model_track_default_params (spec S34; the defaults are build-owned and untuned) with the given fields replaced."""
+    return _default_params(ModelTrackParams, "model_track", fields)
+
+
+class ModelTrack(_DeviceObject):
+    """Frame-to-model pose tracking against a VoxelMap (cart_model_track_* in the C ABI, spec S34 in DESIGN.md 7.16): Gauss-Newton on the
+    camera-to-world pose over the frame's back-projected pixels, which should lie on the volume's zero level set, for frames of up to
+    max_width x max_height.  Reads the volume only.  A context manager; close() destroys the device object."""
+    _name = "model_track"
+
+    def __init__(self, engine, max_width, max_height):
+        self.max_width, self.max_height = int(max_width), int(max_height)
+        super().__init__(engine, self.max_width, self.max_height)
+
+    def refine(self, voxel_map, camera, pose0, disp, params=None, mask=None, stream=None, raw=False):
+        """voxel_map = the VoxelMap to track against; camera = EgoCamera or (fx, fy, cx, cy, baseline); pose0 = 12 numbers, the 3 x 4
+        camera-to-world pose to refine (host); disp int16 [h, w] (x16), mask uint8 [h, w] (motion_segment's labels) or None: device tensors
+        are taken as they are (rows may be pitched), host arrays go up.  stream = a torch stream (default: the current one).  -> the result
+        as a MODEL_TRACK_RESULT_DTYPE array of one record (host); raw=True returns the device tensor (136 bytes as float64) with no host
+        round trip."""
+        import torch
+        cam = _camera(camera)
+        p = params if params is not None else model_track_params()
+        with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):   # uploads and the result's allocation on the call's stream
+            d, mk = _to_device(disp, torch.int16), _to_device(mask, torch.uint8)
+            if not isinstance(d, torch.Tensor) or d.dtype != torch.int16 or d.dim() != 2:
+                raise EngineError("disp must be an int16 [h, w] image")
+            if mk is not None:
+                _check_frame_image(mk, torch.uint8, "mask", d)
+            res = torch.empty(MODEL_TRACK_RESULT_DTYPE.itemsize // 8, dtype=torch.float64, device=d.device)   # every byte is written by the call
+        h, w = int(d.shape[0]), int(d.shape[1])
+        sp = C.c_void_p(stream.cuda_stream) if stream is not None else _stream_ptr()
+        self._check(self._lib.cart_model_track_refine(self._h, voxel_map._h, C.byref(cam), _pose12(pose0), C.byref(p), *_pitched(d, 1), *_pitched(mk, 1), w, h,
+                                                      C.c_void_p(res.data_ptr()), sp), "cart_model_track_refine")
+        if raw:
+            return res
+        if stream is not None:
+            stream.synchronize()
+        return res.cpu().numpy().view(MODEL_TRACK_RESULT_DTYPE).reshape(-1)
 
 
 OBJECT_DTYPE = np.dtype([("component", "<i4"), ("area", "<i4"), ("x0", "<i4"), ("y0", "<i4"), ("x1", "<i4"), ("y1", "<i4"), ("median_bin", "<i4"), ("n_hist", "<i4"),

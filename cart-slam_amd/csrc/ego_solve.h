@@ -1,5 +1,5 @@
 // ego_solve.h -- the Gauss-Newton step of the pose refinements (spec S23, shared by S26): the unpivoted Cholesky solve of the 6 x 6
-// normal equations and the quaternion pose update.  Included by ego_kernels.hip and dense_ego_kernels.hip; IEEE double in the spec's
+// normal equations and the quaternion pose update.  Included by ego_kernels.hip, dense_ego_kernels.hip and modeltrack_kernels.hip; IEEE double in the spec's
 // operation order, no FMA contraction.
 #pragma once
 

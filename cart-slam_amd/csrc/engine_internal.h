@@ -641,6 +641,24 @@ struct VoxelRaycastArgs {
 void launch_voxel_clear(const VoxelGrid &grid, int rx0, int rw, int ry0, int rh, int rz0, int rd, hipStream_t s);
 void launch_voxel_integrate(const VoxelIntegrateArgs &a, hipStream_t s);
 void launch_voxel_raycast(const VoxelRaycastArgs &a, hipStream_t s);
+// ---- frame-to-model pose tracking against the TSDF volume (modeltrack_kernels.hip) ----
+constexpr int kTrackCols = 2;           // sampled columns of a lane whose image loads and corner gathers are issued together
+struct ModelTrackArgs {                 // the sums, the row partials and the pose state are S26's (kDense*, DenseEgoState)
+    VoxelGrid grid;
+    cart_ego_camera cam;
+    cart_voxel_map_params mp;           // the map's own: the pixel gates, voxel_size and min_weight
+    cart_model_track_params p;
+    double pose0[12];
+    const int16_t *disp; size_t disp_step;
+    const uint8_t *mask; size_t mask_step;              // NULL = no mask
+    int w, h, ni, nj;                                   // the image and its sample grid
+    int rows_cap;                                       // rows of the partial table: word k of sampled row j is partial[k * rows_cap + j]
+    int empty;                                          // the map has no window: no pixel is a candidate
+    double *partial;
+    DenseEgoState *state;
+    cart_model_track_result *result;
+};
+void launch_model_track(const ModelTrackArgs &a, hipStream_t s);   // the 2 (iterations + 1) launches of one call
 void launch_narrow_copy(const void *src, void *dst, size_t bytes, int blocks, hipStream_t s);
 int kernel_count();
 

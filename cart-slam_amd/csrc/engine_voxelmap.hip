@@ -4,6 +4,7 @@
 // block is zeroed once at create and left all zero by every call.
 
 #include "engine_host.h"
+#include "engine_voxelmap.h"
 
 using namespace cart_amd;
 
@@ -12,28 +13,12 @@ extern "C" {
 static_assert(sizeof(cart_voxel) == 4, "cart_voxel is one 32-bit word");
 static_assert(sizeof(cart_voxel_map_params) == 8 * 8 + 2 * 4, "cart_voxel_map_params: eight doubles and two int32");
 
-struct cart_voxel_map : DeviceObject {
-    using DeviceObject::DeviceObject;
-    int n[3] = {0, 0, 0};                   // nx, ny, nz
-    cart_voxel_map_params p{};
-    uint32_t *voxels = nullptr;             // [nz][ny][nx], toroidal (engine_internal.h, VoxelGrid)
-    int32_t *counters = nullptr;            // [kVoxelCounters]
-    bool valid = false;                     // a window exists (guarded by mu)
-    int64_t o[3] = {0, 0, 0};               // its origin in absolute voxels
-};
-
 void cart_voxel_map_default_params(cart_voxel_map_params *p) {
     if (!p) return;
     *p = cart_voxel_map_params{0.125, 1.0, 0.5, 16.0, 0.25, 0.5, 8.0, 0.125, 64, 1};
 }
 
 static int64_t floor_div(int64_t a, int64_t b) { return a / b - ((a % b != 0) && ((a < 0) != (b < 0))); }
-static int floor_mod(int64_t a, int n) { return (int)(((a % n) + n) % n); }
-
-static VoxelGrid grid_of(const cart_voxel_map *m) {
-    return VoxelGrid{m->voxels, m->n[0], m->n[1], m->n[2], floor_mod(m->o[0], m->n[0]), floor_mod(m->o[1], m->n[1]), floor_mod(m->o[2], m->n[2]),
-                     (double)m->o[0], (double)m->o[1], (double)m->o[2]};
-}
 
 static int check_cells(const char *name, int n) {
     if (n < 16 || n > 1024 || n % 8) return fail(std::string(name) + " must be a multiple of 8 in [16, 1024]");

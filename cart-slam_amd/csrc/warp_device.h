@@ -7,7 +7,7 @@
 //   back-project  Z = fxb / d,  X = ((u - cx) * Z) / fx,  Y = ((v - cy) * Z) / fy          (fxb = fx * baseline, d = disparity in pixels)
 //   carry         q_r = ((P[4r] * X + P[4r + 1] * Y) + P[4r + 2] * Z) + P[4r + 3]          (r = 0, 1, 2)
 //   project       u = (fx * q_x) / q_z + cx,  v = (fy * q_y) / q_z + cy
-// Device only; included by planemap_kernels.hip, motion_kernels.hip, dense_ego_kernels.hip, fusion_kernels.hip and localba_kernels.hip.
+// Device only; included by planemap_kernels.hip, motion_kernels.hip, dense_ego_kernels.hip, fusion_kernels.hip, localba_kernels.hip and voxel_sample.h / modeltrack_kernels.hip.
 #pragma once
 
 #include "engine_internal.h"

@@ -24,6 +24,9 @@ struct DenseEgoOptions : CameraOptions {   // the factory fills the camera from 
 
 // The consumer's rule of S26: the refined pose iff status == 1, all 12 entries are finite and n_inliers >= n_initial.
 bool acceptDenseEgo(const cart_dense_ego_result &r);
+// The consumer's rule of spec S34 (frame-to-model tracking, the voxel_map module's "track"): the refined pose is taken iff status == 1, every
+// number of the record is finite, rms <= rms_initial and n_inliers >= minInliers (restated in tests/np_modeltrack.py, accept).
+bool acceptModelTrack(const cart_model_track_result &r, int minInliers);
 
 class DenseEgoModule : public SyncWrapperSystemModule {
    public:

@@ -2,6 +2,8 @@
 // raycast through cart_voxel_map_* (include/cart_engine.h), spec DESIGN.md S33.  Every frame's disparity is integrated into one rolling
 // volume through the frame's camera-to-world pose, and the volume is raycast from that pose into "disparity_model", an image in the
 // format of "disparity".  Factory type "voxel_map".
+// With "track" (spec DESIGN.md S34) the module keeps a pose chain of its own: every frame's predicted pose is refined against the volume
+// through cart_model_track_* before the frame is integrated and raycast at the refined pose, published as "model_pose".
 #pragma once
 #include <array>
 #include <mutex>
@@ -15,6 +17,8 @@
 #define CARTSLAM_KEY_DISPARITY_MODEL "disparity_model"                    // CV_16SC1, the format of "disparity"; empty without "raycast"
 #define CARTSLAM_KEY_DISPARITY_MODEL_STATUS "disparity_model_status"      // CV_8UC1: CART_VOXEL_RAY_*
 #define CARTSLAM_KEY_DISPARITY_MODEL_COUNTS "disparity_model_counts"      // VoxelRayCounts
+#define CARTSLAM_KEY_MODEL_POSE "model_pose"                              // EgoMotion, with "track" only: the tracked pose and the relative pose between tracked poses
+#define CARTSLAM_KEY_MODEL_TRACK_RESULT "model_track_result"              // cart_model_track_result as the device wrote it, with "track" only
 
 namespace cart {
 struct VoxelMap {
@@ -38,7 +42,12 @@ struct VoxelMapOptions : CameraOptions {   // the factory fills the camera from 
     std::string poseKey = "ego_motion";       // the blackboard EgoMotion whose accumulated pose the map takes; "dense_ego", "local_ba", "pose_graph"
     bool useMotion = false;                   // "motion" of this frame masks the integration
     bool raycast = true;                      // publish the model image of every frame
+    bool track = false;                       // S34: refine every frame's pose against the volume before integrating it
+    double residualGate = 0.9, damping = 0.01;   // cart_model_track_default_params
+    int iterations = 4, stride = 1, minInliers = 1024;
 };
+
+static_assert(sizeof(cart_model_track_result) == 136, "cart_model_track_result layout");
 
 class VoxelMapModule : public SyncWrapperSystemModule {
    public:
@@ -51,6 +60,9 @@ class VoxelMapModule : public SyncWrapperSystemModule {
     const bool snapshot;
     std::mutex mutex;                 // the frames arrive one at a time (the -1 dependency); this guards the lazy creation
     cart_voxel_map *map = nullptr;
-    DeviceScratch scratch;            // the one stream; the five counts on the device and the pinned buffer they are downloaded through
+    cart_model_track *tracker = nullptr;   // with "track": made with the map
+    bool haveTracked = false;         // with "track": `tracked` holds the previous frame's tracked pose
+    double tracked[12] = {};
+    DeviceScratch scratch;            // the one stream; the tracking record and the five counts on the device and the pinned buffer they are downloaded through
 };
 }  // namespace cart

@@ -299,6 +299,12 @@ void applyModuleConfig(const Value &modulesConfig, std::shared_ptr<System> syste
             o.poseKey = get<std::string>(moduleConfig, "pose_key", o.poseKey);                 // "dense_ego", "local_ba", "pose_graph": the refined trajectory
             o.useMotion = get(moduleConfig, "use_motion", o.useMotion);
             o.raycast = get(moduleConfig, "raycast", o.raycast);
+            o.track = get(moduleConfig, "track", o.track);   // S34: the pose refined against the volume, published as "model_pose"
+            o.residualGate = get(moduleConfig, "residual_gate", o.residualGate);
+            o.damping = get(moduleConfig, "damping", o.damping);
+            o.iterations = get(moduleConfig, "iterations", o.iterations);
+            o.stride = get(moduleConfig, "stride", o.stride);
+            o.minInliers = get(moduleConfig, "min_inliers", o.minInliers);
             system->addModule<VoxelMapModule>(o);
         } else if (endsWith(moduleType, "_visualization")) {
             std::cerr << "[cartconfig] skipping GUI module type " << moduleType << " (out of scope)\n";

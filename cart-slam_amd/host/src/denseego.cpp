@@ -25,6 +25,15 @@ bool acceptDenseEgo(const cart_dense_ego_result &r) {
     return true;
 }
 
+bool acceptModelTrack(const cart_model_track_result &r, int minInliers) {
+    if (r.status != 1 || r.n_inliers < minInliers || !(r.rms <= r.rms_initial) || !std::isfinite(r.rms) || !std::isfinite(r.rms_initial)) return false;
+    for (double v : r.R)
+        if (!std::isfinite(v)) return false;
+    for (double v : r.t)
+        if (!std::isfinite(v)) return false;
+    return true;
+}
+
 DenseEgoModule::DenseEgoModule(const DenseEgoOptions &options) : SyncWrapperSystemModule("DenseEgo"), options(options) {
     checkCamera(options);
     // the library's own checks, without a device: everything valid gets as far as the missing object

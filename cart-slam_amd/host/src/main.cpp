@@ -186,6 +186,12 @@ int main(int argc, char **argv) {
                     if (!vm->voxels.empty())   // with CARTSLAM_VOXEL_MAP_SNAPSHOT: the 4-byte voxels in window order
                         writeBin(dump, id, CARTSLAM_KEY_VOXEL_MAP "_voxels", vm->voxels.data(), vm->voxels.size() * sizeof(cart_voxel));
                 }
+                if (run->hasData(CARTSLAM_KEY_MODEL_POSE)) {   // voxel_map with "track": the 136-byte cart_model_track_result, then the tracked pose as 12 doubles
+                    auto record = run->getData<cart_model_track_result>(CARTSLAM_KEY_MODEL_TRACK_RESULT);
+                    auto tracked = run->getData<cart::EgoMotion>(CARTSLAM_KEY_MODEL_POSE);
+                    std::ofstream o = writeBin(dump, id, CARTSLAM_KEY_MODEL_POSE, record.get(), sizeof(*record));
+                    append(o, tracked->pose, sizeof(tracked->pose));
+                }
                 if (run->hasData(CARTSLAM_KEY_MOTION)) {   // int32 width, height; the filtered labels, the raw labels, the residual records
                     auto labels = run->getData<cart::image_t>(CARTSLAM_KEY_MOTION);
                     const int32_t shape[2] = {labels->cols, labels->rows};

@@ -4,6 +4,7 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "cartslam_amd/modules/denseego.hpp"
 #include "cartslam_amd/modules/disparity.hpp"
 #include "cartslam_amd/modules/egomotion.hpp"
 #include "cartslam_amd/modules/motionseg.hpp"
@@ -14,6 +15,17 @@ namespace {
 cart_voxel_map_params paramsOf(const VoxelMapOptions &o) {
     return cart_voxel_map_params{o.voxelSize, o.minDisparity, o.minDepth, o.maxDepth, o.truncation, o.disparitySigma, o.lookahead, o.marchStep, o.maxWeight, o.minWeight};
 }
+cart_model_track_params trackParamsOf(const VoxelMapOptions &o) { return cart_model_track_params{o.residualGate, o.damping, o.iterations, o.stride, o.minInliers}; }
+
+// p_cur = R p_prev + t between two camera-to-world poses: R = Rc^T Rp, t = Rc^T (tp - tc), in plain double loops
+void relativeOf(const double prev[12], const double cur[12], double R[9], double t[3]) {
+    for (int r = 0; r < 3; ++r) {
+        for (int c = 0; c < 3; ++c) R[3 * r + c] = (cur[r] * prev[c] + cur[4 + r] * prev[4 + c]) + cur[8 + r] * prev[8 + c];
+        t[r] = (cur[r] * (prev[3] - cur[3]) + cur[4 + r] * (prev[7] - cur[7])) + cur[8 + r] * (prev[11] - cur[11]);
+    }
+}
+
+constexpr size_t kCountsOffset = sizeof(cart_model_track_result);   // of the five counts in the scratch buffers, after the tracking record
 }  // namespace
 
 VoxelMapModule::VoxelMapModule(const VoxelMapOptions &options)
@@ -26,6 +38,15 @@ VoxelMapModule::VoxelMapModule(const VoxelMapOptions &options)
     requireLibraryAccepts();
     if (options.disparityKey.empty()) throw std::invalid_argument("disparity_key must name a blackboard image");
     if (options.poseKey.empty()) throw std::invalid_argument("pose_key must name a blackboard pose");
+    if (options.track) {
+        // the tracked chain is the previous tracked pose and this frame's relative pose: the record must carry one, and past poses must stay
+        if (options.poseKey != CARTSLAM_KEY_EGO_MOTION && options.poseKey != "dense_ego")
+            throw std::invalid_argument("track needs a pose_key whose record carries a relative pose and never revises past poses (ego_motion, dense_ego), not " + options.poseKey);
+        const cart_ego_camera cam = cameraOf(options);
+        const cart_model_track_params tp = trackParamsOf(options);
+        (void)cart_model_track_refine(nullptr, nullptr, &cam, kIdentityPose, &tp, nullptr, 0, nullptr, 0, 1, 1, nullptr, nullptr);
+        requireLibraryAccepts();
+    }
     this->requiresData.push_back(module_dependency_t(options.disparityKey));
     this->requiresData.push_back(module_dependency_t(options.poseKey));
     if (options.useMotion) this->requiresData.push_back(module_dependency_t(CARTSLAM_KEY_MOTION));
@@ -34,9 +55,16 @@ VoxelMapModule::VoxelMapModule(const VoxelMapOptions &options)
     this->providesData.push_back(CARTSLAM_KEY_DISPARITY_MODEL);
     this->providesData.push_back(CARTSLAM_KEY_DISPARITY_MODEL_STATUS);
     this->providesData.push_back(CARTSLAM_KEY_DISPARITY_MODEL_COUNTS);
+    if (options.track) {
+        this->providesData.push_back(CARTSLAM_KEY_MODEL_POSE);
+        this->providesData.push_back(CARTSLAM_KEY_MODEL_TRACK_RESULT);
+    }
 }
 
-VoxelMapModule::~VoxelMapModule() { cart_voxel_map_destroy(map); }
+VoxelMapModule::~VoxelMapModule() {
+    cart_model_track_destroy(tracker);
+    cart_voxel_map_destroy(map);
+}
 
 system_data_t VoxelMapModule::runInternal(System &, SystemRunData &data) {
     auto disparity = data.getData<image_t>(options.disparityKey);
@@ -48,7 +76,8 @@ system_data_t VoxelMapModule::runInternal(System &, SystemRunData &data) {
         requireImage(mask, CV_8UC1, rows, cols, "VoxelMapModule: motion must be a CV_8UC1 image of the disparity's size");
     }
     double pose[12];   // a frame whose pose status is 0 carries the kept pose
-    std::memcpy(pose, data.getData<EgoMotion>(options.poseKey)->pose, sizeof(pose));
+    auto ego = data.getData<EgoMotion>(options.poseKey);
+    std::memcpy(pose, ego->pose, sizeof(pose));
     auto result = std::make_shared<VoxelMap>();
     auto rays = std::make_shared<VoxelRayCounts>();
     auto model = options.raycast ? std::make_shared<image_t>(rows, cols, CV_16SC1) : std::make_shared<image_t>();
@@ -59,19 +88,55 @@ system_data_t VoxelMapModule::runInternal(System &, SystemRunData &data) {
         makeOnPostEngine(cols, rows, [&](cart_engine *e) {
             return cart_voxel_map_create(e, options.cellsX, options.cellsY, options.cellsZ, &p, &map) ? "cart_voxel_map_create" : nullptr;
         });
+        if (options.track)
+            makeOnPostEngine(cols, rows, [&](cart_engine *e) { return cart_model_track_create(e, cols, rows, &tracker) ? "cart_model_track_create" : nullptr; });
         scratch.create();
-        scratch.reserve(5 * sizeof(int32_t), 5 * sizeof(int32_t));
+        scratch.reserve(kCountsOffset + 5 * sizeof(int32_t), kCountsOffset + 5 * sizeof(int32_t));
     }
     const cart_ego_camera cam = cameraOf(options);
     hipStream_t s = scratch.stream();
-    int32_t *counts = scratch.dev<int32_t>();   // [0, 2): integrate; [2, 5): raycast
+    int32_t *counts = reinterpret_cast<int32_t *>(scratch.dev<char>() + kCountsOffset);   // [0, 2): integrate; [2, 5): raycast
+    std::shared_ptr<EgoMotion> modelPose;
+    std::shared_ptr<cart_model_track_result> trackResult;
+    if (options.track) {
+        // the prediction: the previous tracked pose chained with this frame's relative pose (kept where the frame has none); frame 1 takes the pose itself
+        if (haveTracked) chainPose(tracked, ego->result, pose);
+        const cart_model_track_params tp = trackParamsOf(options);
+        if (cart_model_track_refine(tracker, map, &cam, pose, &tp, disparity->ptr<int16_t>(), disparity->step, mask ? mask->ptr<uint8_t>() : nullptr, mask ? mask->step : 0,
+                                    cols, rows, scratch.dev<cart_model_track_result>(), s) != 0)
+            failAbi("cart_model_track_refine");
+        hipCheck(hipMemcpyAsync(scratch.host(), scratch.dev(), sizeof(cart_model_track_result), hipMemcpyDeviceToHost, s), "hipMemcpyAsync of the model tracking result");
+        scratch.wait();   // the pose decides where the frame is integrated: the host must see the record first
+        trackResult = std::make_shared<cart_model_track_result>();
+        std::memcpy(trackResult.get(), scratch.host(), sizeof(*trackResult));
+        if (acceptModelTrack(*trackResult, options.minInliers))
+            for (int r = 0; r < 3; ++r) {
+                for (int c = 0; c < 3; ++c) pose[4 * r + c] = trackResult->R[3 * r + c];
+                pose[4 * r + 3] = trackResult->t[r];
+            }
+        modelPose = std::make_shared<EgoMotion>();
+        modelPose->result = ego->result;   // the counts of the estimate the prediction came from; R and t are replaced below
+        if (haveTracked) {
+            relativeOf(tracked, pose, modelPose->result.R, modelPose->result.t);
+            modelPose->result.status = 1;
+        } else {
+            const double I[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+            std::memcpy(modelPose->result.R, I, sizeof(I));
+            modelPose->result.t[0] = modelPose->result.t[1] = modelPose->result.t[2] = 0.0;
+            modelPose->result.status = 0;
+        }
+        std::memcpy(modelPose->pose, pose, sizeof(pose));
+        std::memcpy(tracked, pose, sizeof(pose));
+        haveTracked = true;
+    }
     if (cart_voxel_map_integrate(map, &cam, pose, disparity->ptr<int16_t>(), disparity->step, cols, rows, mask ? mask->ptr<uint8_t>() : nullptr, mask ? mask->step : 0,
                                  counts, s) != 0)
         failAbi("cart_voxel_map_integrate");
     if (options.raycast &&
         cart_voxel_map_raycast(map, &cam, pose, cols, rows, model->ptr<int16_t>(), model->step, nullptr, 0, status->ptr<uint8_t>(), status->step, counts + 2, s) != 0)
         failAbi("cart_voxel_map_raycast");
-    hipCheck(hipMemcpyAsync(scratch.host(), scratch.dev(), (options.raycast ? 5 : 2) * sizeof(int32_t), hipMemcpyDeviceToHost, s), "hipMemcpyAsync of the voxel map counts");
+    int32_t *hostCounts = reinterpret_cast<int32_t *>(scratch.host<char>() + kCountsOffset);
+    hipCheck(hipMemcpyAsync(hostCounts, counts, (options.raycast ? 5 : 2) * sizeof(int32_t), hipMemcpyDeviceToHost, s), "hipMemcpyAsync of the voxel map counts");
     int valid = 0;
     if (cart_voxel_map_window(map, result->origin, result->cells, &valid) != 0) failAbi("cart_voxel_map_window");
     result->voxelSize = options.voxelSize;
@@ -80,9 +145,14 @@ system_data_t VoxelMapModule::runInternal(System &, SystemRunData &data) {
         if (cart_voxel_map_read(map, result->voxels.data(), result->origin, s) != 0) failAbi("cart_voxel_map_read");
     }
     scratch.wait();   // the frame's only blocking synchronisation
-    std::memcpy(result->counts, scratch.host<int32_t>(), sizeof(result->counts));
-    if (options.raycast) std::memcpy(rays->rays, scratch.host<int32_t>() + 2, sizeof(rays->rays));
-    return MODULE_RETURN_ALL(MODULE_PAIR(CARTSLAM_KEY_VOXEL_MAP, result), MODULE_PAIR(CARTSLAM_KEY_DISPARITY_MODEL, model),
-                             MODULE_PAIR(CARTSLAM_KEY_DISPARITY_MODEL_STATUS, status), MODULE_PAIR(CARTSLAM_KEY_DISPARITY_MODEL_COUNTS, rays));
+    std::memcpy(result->counts, hostCounts, sizeof(result->counts));
+    if (options.raycast) std::memcpy(rays->rays, hostCounts + 2, sizeof(rays->rays));
+    system_data_t out = MODULE_RETURN_ALL(MODULE_PAIR(CARTSLAM_KEY_VOXEL_MAP, result), MODULE_PAIR(CARTSLAM_KEY_DISPARITY_MODEL, model),
+                                          MODULE_PAIR(CARTSLAM_KEY_DISPARITY_MODEL_STATUS, status), MODULE_PAIR(CARTSLAM_KEY_DISPARITY_MODEL_COUNTS, rays));
+    if (options.track) {
+        out.push_back(MODULE_PAIR(CARTSLAM_KEY_MODEL_POSE, modelPose));
+        out.push_back(MODULE_PAIR(CARTSLAM_KEY_MODEL_TRACK_RESULT, trackResult));
+    }
+    return out;
 }
 }  // namespace cart

@@ -1166,6 +1166,69 @@ int cart_voxel_map_raycast(cart_voxel_map *map, const cart_ego_camera *camera, c
  * into host_voxels (HOST); without a window every voxel is empty and the origin is (0, 0, 0).  origin3 = int64 [3]. */
 int cart_voxel_map_read(cart_voxel_map *map, cart_voxel *host_voxels, int64_t *origin3, void *stream);
 
+/* ---- Frame-to-model pose tracking against the TSDF volume (spec S34) ---------------------------------------------
+ * An extension: the reference estimates no pose.  Gauss-Newton refinement of a camera-to-world pose P (3 x 4 as cart_voxel_map_raycast
+ * takes it) so that the frame's back-projected pixels lie on the zero level set of a cart_voxel_map: minimises sum F(P p)^2.  fp64 with
+ * + - * / floor sqrt only, every expression in the written order, no floating-point atomic: restated in tests/np_modeltrack.py, byte
+ * for byte over the whole result record.  The depth, disparity and weight gates are the map's own cart_voxel_map_params.
+ *   Sample grid: pixels (x, y) = (i stride, j stride) inside the image.  One evaluation at P, per sampled pixel:
+ *   1. s = disp[y][x] != -32768, d = s / 16.0 >= min_disparity, Z = (fx baseline) / d with min_depth <= Z <= max_depth, mask NULL or
+ *      mask[y][x] != 1 (MOVING): exactly the pixels cart_voxel_map_integrate could have used.
+ *   2. p = P applied to (((x - cx) Z) / fx, ((y - cy) Z) / fy, Z) in S33's carry order.  The sample at p is known by the raycast's rule
+ *      to the letter: a = p / voxel_size - 0.5, i0 = floor(a), fr = a - i0 per axis; a window exists, all eight corners i0 + {0,1}^3 lie
+ *      in it (compared as doubles; a NaN fails) and each has weight >= min_weight.  A pixel with a known sample is a candidate.
+ *   3. With t[dz][dy][dx] the eight tsdf integers: c[dy][dz], e0, e1 and F as the raycast's; g_z = e1 - e0; g_y = h0 + fr_z (h1 - h0)
+ *      with h0 = c[1][0] - c[0][0], h1 = c[1][1] - c[0][1]; g_x = a0 + fr_z (a1 - a0) with a0 = D[0][0] + fr_y (D[1][0] - D[0][0]),
+ *      a1 = D[0][1] + fr_y (D[1][1] - D[0][1]), D[dy][dz] = (double)(t[dz][dy][1] - t[dz][dy][0]).
+ *   4. r = F / 32767.0; the candidate is an inlier iff |r| < residual_gate (saturated free space, where the gradient vanishes, drops out).
+ *   5. G = g / (32767.0 voxel_size) (the product first), J = (p_y G_z - p_z G_y, p_z G_x - p_x G_z, p_x G_y - p_y G_x, G_x, G_y, G_z):
+ *      the row of the left update p <- Rq p + upsilon.
+ *   6. Sums in S26's layout: the 21 upper J_i J_j, the 6 J_i r, r r, the inlier count and the candidate count.
+ *   Order of every sum: S26's, word for word (cart_dense_ego_params above): for sampled row j, virtual lane l of 256 starts at +0.0 and
+ *   adds its inliers of sampled columns l, l + 256, ... in ascending order, then v[l] += v[l ^ o] for o = 1, 2, 4 .. 128 and lane 0 holds
+ *   the row's partial; virtual lane l then adds the partials of sampled rows l, l + 256, ... (every row, ascending), the same butterfly.
+ *   Iteration (S26's state machine): P = pose0; iterations + 1 evaluations, the last one only measures.  The first gives n_initial and
+ *   rms_initial.  Up to `iterations` times: evaluate, stop if the inlier count cnt < min_inliers, H[i][i] = H[i][i] + damping (double)cnt,
+ *   solve H delta = -g by S23's unpivoted Cholesky (stop at a pivot that is not > 0), update the pose as S23 does (R <- Rq R,
+ *   t <- Rq t + upsilon), steps += 1.  The evaluation that stops gives n_inliers, n_candidates and rms = sqrt(sum r r / cnt) (0.0 at 0).
+ *   Without a window there is no candidate: status 0 and the input pose.
+ *   Acceptance is the consumer's: take the pose iff status == 1, every number of the record is finite, rms <= rms_initial and
+ *   n_inliers >= min_inliers, else keep pose0. */
+typedef struct cart_model_track_params {
+    double residual_gate;                     /* fraction of the truncation, finite, 0 < . <= 1 */
+    double damping;                           /* finite, >= 0: added to H's diagonal times the inlier count */
+    int32_t iterations;                       /* 0..16 */
+    int32_t stride;                           /* 1..16 */
+    int32_t min_inliers;                      /* 6..2^30 */
+} cart_model_track_params;
+void cart_model_track_default_params(cart_model_track_params *p); /* extension: 0.9, 0.01, 4, 1, 1024 (build-owned, untuned) */
+#define CART_MODEL_TRACK_MAX_ITERATIONS 16
+typedef struct cart_model_track_result {      /* the layout of cart_dense_ego_result */
+    double R[9], t[3];                        /* the pose after `steps` updates; pose0's when status is 0 */
+    double rms_initial, rms;                  /* sqrt(sum r r / n) at pose0 and at (R, t) */
+    int32_t status;                           /* 1 iff steps > 0 */
+    int32_t n_candidates;                     /* pixels with a known sample at (R, t) */
+    int32_t n_initial, n_inliers;             /* inliers at pose0 and at (R, t) */
+    int32_t steps, reserved;
+} cart_model_track_result;
+
+typedef struct cart_model_track cart_model_track;
+/* Extension.  The workspace for frames of up to max_width x max_height (1..16384 each): one row partial per image row and the pose
+ * state; nothing is allocated per call.  The sizes are checked before the engine. */
+int cart_model_track_create(cart_engine *engine, int max_width, int max_height, cart_model_track **out);
+/* Extension.  Keeps the device it was created on, so it may be destroyed after its engine. */
+void cart_model_track_destroy(cart_model_track *obj);
+/* Extension.  One frame against `map`: pose0 = HOST double [12] (3 x 4 camera-to-world as cart_voxel_map_raycast's; all finite,
+ * |R entries| <= 2, |t entries| <= 1e6); disp = device int16 x16 (2-byte aligned), mask = device u8 labels of cart_motion_segment or
+ * NULL, both width x height (1..16384 each and within the object's maxima), steps in bytes.  result = DEVICE record (8-byte aligned,
+ * overlapping no input).  Checked in this order, all before any device call: params, camera, pose0, sizes, the object, the map, then
+ * pointers, alignment and steps; a refused call touches no output.  Reads the volume only and never moves the window.  Takes the
+ * object, then the map: the call is ordered after earlier calls on either, whatever their streams.  2 (iterations + 1) plain launches
+ * on `stream`, no host synchronisation. */
+int cart_model_track_refine(cart_model_track *obj, cart_voxel_map *map, const cart_ego_camera *camera, const double *pose0,
+                            const cart_model_track_params *params, const int16_t *disp, size_t disp_step, const uint8_t *mask,
+                            size_t mask_step, int width, int height, cart_model_track_result *result, void *stream);
+
 /* Stand-in for ImageOpticalFlowModule's device work (src/modules/optflow.cpp:96-140: cvtColor x2 +
  * cv::cuda::NvidiaOpticalFlow_2_0::calc(current, previous), NVIDIA fixed-function hardware): dense census block
  * matching (oracle S15).  cur / prev = the reference images of frame id and id-1 (1-channel gray or 3-channel BGR),
