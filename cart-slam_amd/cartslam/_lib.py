@@ -368,6 +368,7 @@ PROTOTYPES = {
     "cart_voxel_map_integrate": (_i, [_vp, C.POINTER(EgoCamera), C.POINTER(C.c_double), _vp, _sz, _i, _i, _vp, _sz, _vp, _vp]),
     "cart_voxel_map_raycast": (_i, [_vp, C.POINTER(EgoCamera), C.POINTER(C.c_double), _i, _i, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp]),
     "cart_voxel_map_read": (_i, [_vp, _vp, C.POINTER(C.c_int64), _vp]),
+    "cart_voxel_map_rebuild": (_i, [_vp, _vp, C.POINTER(EgoCamera), C.POINTER(C.c_uint64), C.POINTER(C.c_double), _i, C.POINTER(C.c_double), _i, C.POINTER(_i), _vp, _vp]),
     "cart_model_track_default_params": (None, [C.POINTER(ModelTrackParams)]),
     "cart_model_track_create": (_i, [_vp, _i, _i, C.POINTER(_vp)]),
     "cart_model_track_destroy": (None, [_vp]),

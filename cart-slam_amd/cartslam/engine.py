@@ -1498,6 +1498,30 @@ class VoxelMap(_DeviceObject):
     def clear(self):
         self._check(self._lib.cart_voxel_map_clear(self._h), "cart_voxel_map_clear")
 
+    def rebuild(self, store, ids, poses, window_pose, camera, use_mask=False, counts=True, stream=None):
+        """Spec S35: starts an empty window at `window_pose` (12 numbers, host) and integrates every frame of the PlaneStore
+        `store` that `ids` names into it, entry k through poses[k] (12 numbers each, host), in list order.  Ids the store does not hold are
+        skipped.  use_mask reads the stored uint8 plane as integrate's mask.  stream = a torch stream (default: the current one).
+        -> ((ox, oy, oz), used, counts int64 [2] (voxel updates over all used entries, of them with f < 1) or None when counts is false)."""
+        import torch
+        if not isinstance(store, PlaneStore):
+            raise EngineError("store must be a PlaneStore")
+        cam = _camera(camera)
+        ids = [int(i) for i in ids]
+        flat = np.ascontiguousarray(np.asarray(poses, np.float64).reshape(-1))
+        if len(flat) != 12 * len(ids):
+            raise EngineError("poses must hold 12 numbers for every id")
+        with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):   # the allocation on the call's stream
+            n = torch.empty(2, dtype=torch.int64, device="cuda") if counts else None
+        sp = C.c_void_p(stream.cuda_stream) if stream is not None else _stream_ptr()
+        used = C.c_int(0)
+        self._check(self._lib.cart_voxel_map_rebuild(self._h, store._h, C.byref(cam), (C.c_uint64 * max(len(ids), 1))(*ids),
+                                                     (C.c_double * max(len(flat), 1))(*flat.tolist()), len(ids), _pose12(window_pose), 1 if use_mask else 0,
+                                                     C.byref(used), C.c_void_p(n.data_ptr()) if counts else None, sp), "cart_voxel_map_rebuild")
+        if n is not None and stream is not None:
+            stream.synchronize()
+        return self.window()[0], used.value, (n.cpu().numpy() if n is not None else None)
+
 
 MODEL_TRACK_RESULT_DTYPE = np.dtype([("R", "<f8", 9), ("t", "<f8", 3), ("rms_initial", "<f8"), ("rms", "<f8"), ("status", "<i4"), ("n_candidates", "<i4"),
                                      ("n_initial", "<i4"), ("n_inliers", "<i4"), ("steps", "<i4"), ("reserved", "<i4")])   # cart_model_track_result

@@ -606,8 +606,8 @@ constexpr int kVoxelSlices = 4;         // z slices one lane of the integrate ke
 #define CART_VOXEL_DEPTH 16             // the A/B of DESIGN.md 7.15 also builds 4: one group of slices per workgroup, four times the workgroups and tickets
 #endif
 constexpr int kVoxelDepth = CART_VOXEL_DEPTH;   // z slices per workgroup of the integrate kernel: a multiple of kVoxelSlices
-constexpr int kVoxelCounters = 8;       // int32 words of the object's counter block, read as four uint64: integrate {updated | near << 32, ticket},
-                                        // raycast {NONE | HIT << 32, INSIDE | ticket << 32}; all zero between calls
+constexpr int kVoxelCounters = 14;      // int32 words of the object's counter block, read as seven uint64: integrate {updated | near << 32, ticket},
+                                        // raycast {NONE | HIT << 32, INSIDE | ticket << 32}, rebuild {updated, near, ticket}; all zero between calls
 struct VoxelGrid {
     uint32_t *voxels;                   // [nz][ny][nx] words: tsdf in the low half, weight in the high half
     int nx, ny, nz, mx, my, mz;
@@ -641,6 +641,20 @@ struct VoxelRaycastArgs {
 void launch_voxel_clear(const VoxelGrid &grid, int rx0, int rw, int ry0, int rh, int rz0, int rd, hipStream_t s);
 void launch_voxel_integrate(const VoxelIntegrateArgs &a, hipStream_t s);
 void launch_voxel_raycast(const VoxelRaycastArgs &a, hipStream_t s);
+// ---- rebuilding the volume from stored keyframes (voxel_rebuild_kernels.hip) ----
+struct VoxelRebuildArgs {
+    VoxelGrid grid;                                     // the rebuild's fixed window
+    cart_ego_camera cam;
+    cart_voxel_map_params p;
+    const int16_t *disp;                                // the store's planes: [capacity][h][w], packed
+    const uint8_t *planes;                              // NULL = use_mask 0: the u8 plane is not read
+    const PlaneRevoteRecord *records;                   // [entries], in list order
+    int entries;
+    int w, h;
+    long long *counts;                                  // may be NULL
+    int32_t *counters;                                  // the map's block; the rebuild's words start at uint64 word 4
+};
+void launch_voxel_rebuild(const VoxelRebuildArgs &a, hipStream_t s);   // one launch: every voxel of the window is written
 // ---- frame-to-model pose tracking against the TSDF volume (modeltrack_kernels.hip) ----
 constexpr int kTrackCols = 2;           // sampled columns of a lane whose image loads and corner gathers are issued together
 struct ModelTrackArgs {                 // the sums, the row partials and the pose state are S26's (kDense*, DenseEgoState)

@@ -3,6 +3,7 @@
 // cart_plane_store ring of keyframe images and cart_plane_map_rebuild.
 
 #include "engine_host.h"
+#include "engine_planemap.h"
 
 using namespace cart_amd;
 
@@ -15,28 +16,6 @@ struct cart_plane_map : DeviceObject {
     cart_plane_map_cell *cells = nullptr;   // [nz][nx], toroidal (engine_internal.h, PlaneMapGrid)
     bool valid = false;                     // a window exists (guarded by mu)
     int64_t ox = 0, oz = 0;                 // its origin in absolute cells
-};
-
-// S30: a ring of `capacity` frames of exactly w x h.  The id table and the insertion count are host state (guarded by mu).
-struct cart_plane_store : DeviceObject {
-    using DeviceObject::DeviceObject;
-    int w = 0, h = 0, capacity = 0;
-    int16_t *disp = nullptr;             // [capacity][h][w], packed
-    uint8_t *planes = nullptr;           // [capacity][h][w], packed
-    PlaneRevoteRecord *records = nullptr;          // device [kRevoteMaxEntries]: the entries of the rebuild in flight
-    PlaneRevoteRecord *staging = nullptr;          // pinned host [kRevoteMaxEntries]: what the upload reads
-    hipEvent_t uploaded = nullptr;       // recorded after every upload: the next rebuild waits for it before it rewrites `staging`
-    bool staged = false;
-    std::vector<uint64_t> ids;           // [capacity]: the frame_id of every slot
-    uint64_t inserted = 0;               // since create / clear: insertion n went to slot n mod capacity
-    int find(uint64_t id) const {        // newest first, so a repeated id names its latest insertion; -1 = not stored
-        const uint64_t live = std::min<uint64_t>(inserted, (uint64_t)capacity);
-        for (uint64_t k = 1; k <= live; ++k) {
-            const int slot = (int)((inserted - k) % (uint64_t)capacity);
-            if (ids[slot] == id) return slot;
-        }
-        return -1;
-    }
 };
 
 void cart_plane_map_default_params(cart_plane_map_params *p) {
@@ -209,21 +188,8 @@ int cart_plane_map_rebuild(cart_plane_map *m, cart_plane_store *s, const cart_eg
     if (map_call.begin()) return -1;
     ObjectCall store_call(*s, stream);
     if (store_call.begin()) return -1;
-    // the previous rebuild's upload may still be reading the pinned records: wait for that copy alone, not for the stream
-    if (s->staged) HIP_TRY(hipEventSynchronize(s->uploaded));
     int used = 0;
-    for (int k = 0; k < count; ++k) {
-        const int slot = s->find(ids[k]);
-        if (slot < 0) continue;   // evicted or never inserted: skipped and counted
-        PlaneRevoteRecord &r = s->staging[used++];
-        r.slot = slot; r.pad = 0;
-        std::memcpy(r.pose, poses + 12 * (size_t)k, sizeof(r.pose));
-    }
-    if (used) {
-        HIP_TRY(hipMemcpyAsync(s->records, s->staging, sizeof(PlaneRevoteRecord) * (size_t)used, hipMemcpyHostToDevice, stream));
-        HIP_TRY(hipEventRecord(s->uploaded, stream));
-        s->staged = true;
-    }
+    if (stage_rebuild_entries(s, ids, poses, count, stream, &used)) return -1;
     // the window (S24) of window_pose, emptied whole
     const int64_t cx = (int64_t)std::floor(window_pose[3] / m->p.cell_size), cz = (int64_t)std::floor(window_pose[11] / m->p.cell_size);
     m->ox = 16 * floor_div(cx - m->nx / 2, 16); m->oz = 16 * floor_div(cz - m->nz / 2, 16); m->valid = true;

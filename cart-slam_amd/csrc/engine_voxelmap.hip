@@ -1,9 +1,11 @@
 // engine_voxelmap.hip -- C ABI of the rolling TSDF voxel map (include/cart_engine.h): argument checks, the window
 // arithmetic (host, int64) and the cart_voxel_map device object, which owns the volume and the counter block.  The volume is never
 // cleared by hipMemset: the first integrate after create / clear empties the whole window by a kernel on the call's stream.  The counter
-// block is zeroed once at create and left all zero by every call.
+// block is zeroed once at create and left all zero by every call.  cart_voxel_map_rebuild (S35) integrates the frames of a cart_plane_store
+// (engine_planemap.h) into a fixed window in one launch.
 
 #include "engine_host.h"
+#include "engine_planemap.h"
 #include "engine_voxelmap.h"
 
 using namespace cart_amd;
@@ -125,6 +127,44 @@ int cart_voxel_map_integrate(cart_voxel_map *m, const cart_ego_camera *cam, cons
     a.disp = disp; a.disp_step = disp_step; a.mask = mask; a.mask_step = mask_step; a.counts = counts; a.counters = m->counters; a.w = w; a.h = h;
     launch_voxel_integrate(a, stream);
     HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int cart_voxel_map_rebuild(cart_voxel_map *m, cart_plane_store *s, const cart_ego_camera *cam, const uint64_t *ids, const double *poses, int count,
+                           const double *window_pose, int use_mask, int *used_out, int64_t *counts, void *stream_) {
+    if (count < 0 || count > kRevoteMaxEntries) return fail("count must be in [0, 4096]");
+    if (use_mask != 0 && use_mask != 1) return fail("use_mask must be 0 or 1");
+    if (check_camera(cam) || check_pose("window_pose", window_pose)) return -1;
+    if (count > 0 && !ids) return fail("ids is NULL");
+    if (count > 0 && !poses) return fail("poses is NULL");
+    for (int k = 0; k < count; ++k)
+        if (check_pose(("poses[" + std::to_string(k) + "]").c_str(), poses + 12 * (size_t)k)) return -1;
+    if (!m) return fail("map is NULL");
+    if (!s) return fail("store is NULL");
+    if (m->device_id != s->device_id) return fail("map and store are on different devices");
+    if (reinterpret_cast<uintptr_t>(counts) % 8) return fail("counts must be 8-byte aligned");
+
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    ObjectCall map_call(*m, stream);   // the map first, then the store, as cart_plane_map_rebuild: insert takes the store alone, so the order cannot invert
+    if (map_call.begin()) return -1;
+    ObjectCall store_call(*s, stream);
+    if (store_call.begin()) return -1;
+    int used = 0;
+    if (stage_rebuild_entries(s, ids, poses, count, stream, &used)) return -1;
+    // the window (S33) of window_pose; the kernel writes every voxel of it, so nothing is emptied first
+    for (int a = 0; a < 3; ++a) {
+        const int64_t c = (int64_t)std::floor((window_pose[4 * a + 3] + m->p.lookahead * window_pose[4 * a + 2]) / m->p.voxel_size);
+        m->o[a] = 8 * floor_div(c - m->n[a] / 2, 8);
+    }
+    m->valid = true;
+    VoxelRebuildArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.grid = grid_of(m); a.cam = *cam; a.p = m->p;
+    a.disp = s->disp; a.planes = use_mask ? s->planes : nullptr; a.records = s->records; a.entries = used; a.w = s->w; a.h = s->h;
+    a.counts = reinterpret_cast<long long *>(counts); a.counters = m->counters;
+    launch_voxel_rebuild(a, stream);
+    HIP_TRY(hipGetLastError());
+    if (used_out) *used_out = used;
     return 0;
 }
 

@@ -4,6 +4,9 @@
 // format of "disparity".  Factory type "voxel_map".
 // With "track" (spec DESIGN.md S34) the module keeps a pose chain of its own: every frame's predicted pose is refined against the volume
 // through cart_model_track_* before the frame is integrated and raycast at the refined pose, published as "model_pose".
+// With "rebuild" (spec DESIGN.md S35; needs "pose_key": "pose_graph" and no "track") the module keeps every keyframe's disparity in a
+// device-resident store, and on a frame whose pose graph was optimised it rebuilds the whole volume from them through the corrected node
+// poses (cart_voxel_map_rebuild) in place of the integrate, as the plane_map module does for its grid (S30).
 #pragma once
 #include <array>
 #include <mutex>
@@ -27,6 +30,9 @@ struct VoxelMap {
     double voxelSize = 0;
     int32_t counts[2] = {0, 0};         // of this frame's integrate: voxels updated, of them with f < 1
     std::vector<cart_voxel> voxels;     // the voxels in window order; filled only when CARTSLAM_VOXEL_MAP_SNAPSHOT is set
+    int rebuilt = 0, rebuildUsed = 0;   // on a frame that rebuilt the volume (S35): the entries handed in, and those the store still held;
+    int64_t rebuildCounts[2] = {0, 0};  // the rebuild's own counts (`counts` holds them cut to int32)
+    std::vector<uint64_t> rebuildIds;   // the frame ids of the entries, in list order
 };
 struct VoxelRayCounts {
     int32_t rays[3] = {0, 0, 0};        // CART_VOXEL_RAY_NONE, _HIT, _INSIDE
@@ -43,6 +49,8 @@ struct VoxelMapOptions : CameraOptions {   // the factory fills the camera from 
     bool useMotion = false;                   // "motion" of this frame masks the integration
     bool raycast = true;                      // publish the model image of every frame
     bool track = false;                       // S34: refine every frame's pose against the volume before integrating it
+    bool rebuild = false;                     // S35: keep the keyframes' disparity and rebuild the volume when the pose graph was optimised
+    int storeCapacity = 256;                  // keyframes the store holds (a ring: the oldest leaves)
     double residualGate = 0.9, damping = 0.01;   // cart_model_track_default_params
     int iterations = 4, stride = 1, minInliers = 1024;
 };
@@ -61,6 +69,9 @@ class VoxelMapModule : public SyncWrapperSystemModule {
     std::mutex mutex;                 // the frames arrive one at a time (the -1 dependency); this guards the lazy creation
     cart_voxel_map *map = nullptr;
     cart_model_track *tracker = nullptr;   // with "track": made with the map
+    cart_plane_store *store = nullptr;     // with "rebuild": made with the map
+    std::vector<uint64_t> nodeFrame;       // with "rebuild": the frame id of every pose-graph node
+    image_t zeroPlane;                     // with "rebuild" and without "use_motion": the stored u8 plane, zeroed once
     bool haveTracked = false;         // with "track": `tracked` holds the previous frame's tracked pose
     double tracked[12] = {};
     DeviceScratch scratch;            // the one stream; the tracking record and the five counts on the device and the pinned buffer they are downloaded through

@@ -300,6 +300,8 @@ void applyModuleConfig(const Value &modulesConfig, std::shared_ptr<System> syste
             o.useMotion = get(moduleConfig, "use_motion", o.useMotion);
             o.raycast = get(moduleConfig, "raycast", o.raycast);
             o.track = get(moduleConfig, "track", o.track);   // S34: the pose refined against the volume, published as "model_pose"
+            o.rebuild = get(moduleConfig, "rebuild", o.rebuild);   // S35: the volume rebuilt from stored keyframes when the pose graph was optimised
+            o.storeCapacity = get(moduleConfig, "store_capacity", o.storeCapacity);
             o.residualGate = get(moduleConfig, "residual_gate", o.residualGate);
             o.damping = get(moduleConfig, "damping", o.damping);
             o.iterations = get(moduleConfig, "iterations", o.iterations);

@@ -185,6 +185,11 @@ int main(int argc, char **argv) {
                     }
                     if (!vm->voxels.empty())   // with CARTSLAM_VOXEL_MAP_SNAPSHOT: the 4-byte voxels in window order
                         writeBin(dump, id, CARTSLAM_KEY_VOXEL_MAP "_voxels", vm->voxels.data(), vm->voxels.size() * sizeof(cart_voxel));
+                    if (vm->rebuilt > 0) {   // a frame that rebuilt the volume (S35): int32 count, used; the ids as uint64 (the plane map's layout)
+                        const int32_t counts[2] = {vm->rebuilt, vm->rebuildUsed};
+                        std::ofstream r = writeBin(dump, id, CARTSLAM_KEY_VOXEL_MAP "_rebuild", counts, sizeof(counts));
+                        append(r, vm->rebuildIds.data(), vm->rebuildIds.size() * sizeof(uint64_t));
+                    }
                 }
                 if (run->hasData(CARTSLAM_KEY_MODEL_POSE)) {   // voxel_map with "track": the 136-byte cart_model_track_result, then the tracked pose as 12 doubles
                     auto record = run->getData<cart_model_track_result>(CARTSLAM_KEY_MODEL_TRACK_RESULT);

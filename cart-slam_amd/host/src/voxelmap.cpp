@@ -1,6 +1,7 @@
-// voxelmap.cpp -- VoxelMapModule (cartslam_amd/modules/voxelmap.hpp): the rolling TSDF voxel map with model raycast, spec DESIGN.md S33.
+// voxelmap.cpp -- VoxelMapModule (cartslam_amd/modules/voxelmap.hpp): the rolling TSDF voxel map with model raycast, spec DESIGN.md S33; its rebuild from stored keyframes, S35.
 #include "cartslam_amd/modules/voxelmap.hpp"
 
+#include <algorithm>
 #include <cstdlib>
 #include <cstring>
 
@@ -8,6 +9,7 @@
 #include "cartslam_amd/modules/disparity.hpp"
 #include "cartslam_amd/modules/egomotion.hpp"
 #include "cartslam_amd/modules/motionseg.hpp"
+#include "cartslam_amd/modules/posegraph.hpp"
 #include "module_support.hpp"
 
 namespace cart {
@@ -26,6 +28,8 @@ void relativeOf(const double prev[12], const double cur[12], double R[9], double
 }
 
 constexpr size_t kCountsOffset = sizeof(cart_model_track_result);   // of the five counts in the scratch buffers, after the tracking record
+constexpr size_t kRebuildCountsOffset = kCountsOffset + 8 * sizeof(int32_t);   // of the rebuild's two int64 counts, 8-byte aligned
+static_assert(kRebuildCountsOffset % 8 == 0, "the rebuild's counts are int64");
 }  // namespace
 
 VoxelMapModule::VoxelMapModule(const VoxelMapOptions &options)
@@ -47,9 +51,20 @@ VoxelMapModule::VoxelMapModule(const VoxelMapOptions &options)
         (void)cart_model_track_refine(nullptr, nullptr, &cam, kIdentityPose, &tp, nullptr, 0, nullptr, 0, 1, 1, nullptr, nullptr);
         requireLibraryAccepts();
     }
+    if (options.rebuild) {
+        if (options.poseKey != CARTSLAM_KEY_POSE_GRAPH || options.track)
+            throw std::invalid_argument("rebuild requires \"pose_key\": \"pose_graph\" and no track");
+        cart_plane_store *none = nullptr;
+        (void)cart_plane_store_create(nullptr, 1, 1, options.storeCapacity, &none);
+        if (std::strcmp(cart_last_error(nullptr), "bad arguments") != 0) throw std::invalid_argument(std::string("store_capacity: ") + cart_last_error(nullptr));
+    }
     this->requiresData.push_back(module_dependency_t(options.disparityKey));
     this->requiresData.push_back(module_dependency_t(options.poseKey));
     if (options.useMotion) this->requiresData.push_back(module_dependency_t(CARTSLAM_KEY_MOTION));
+    if (options.rebuild) {
+        this->requiresData.push_back(module_dependency_t(CARTSLAM_KEY_POSE_GRAPH_RESULT));
+        this->requiresData.push_back(module_dependency_t(CARTSLAM_KEY_POSE_GRAPH_NODES));
+    }
     this->requiresData.push_back(module_dependency_t(CARTSLAM_KEY_VOXEL_MAP, -1));   // one frame at a time, in order
     this->providesData.push_back(CARTSLAM_KEY_VOXEL_MAP);
     this->providesData.push_back(CARTSLAM_KEY_DISPARITY_MODEL);
@@ -64,6 +79,7 @@ VoxelMapModule::VoxelMapModule(const VoxelMapOptions &options)
 VoxelMapModule::~VoxelMapModule() {
     cart_model_track_destroy(tracker);
     cart_voxel_map_destroy(map);
+    cart_plane_store_destroy(store);
 }
 
 system_data_t VoxelMapModule::runInternal(System &, SystemRunData &data) {
@@ -90,8 +106,16 @@ system_data_t VoxelMapModule::runInternal(System &, SystemRunData &data) {
         });
         if (options.track)
             makeOnPostEngine(cols, rows, [&](cart_engine *e) { return cart_model_track_create(e, cols, rows, &tracker) ? "cart_model_track_create" : nullptr; });
+        if (options.rebuild) {
+            makeOnPostEngine(cols, rows, [&](cart_engine *e) { return cart_plane_store_create(e, cols, rows, options.storeCapacity, &store) ? "cart_plane_store_create" : nullptr; });
+            if (!options.useMotion) {   // the store keeps a u8 plane beside every disparity: zeros, which mask nothing
+                zeroPlane.create(rows, cols, CV_8UC1);
+                zeroPlane.setTo(0);
+                hipCheck(hipDeviceSynchronize(), "hipDeviceSynchronize after zeroing the store's plane");
+            }
+        }
         scratch.create();
-        scratch.reserve(kCountsOffset + 5 * sizeof(int32_t), kCountsOffset + 5 * sizeof(int32_t));
+        scratch.reserve(kRebuildCountsOffset + 2 * sizeof(int64_t), kRebuildCountsOffset + 2 * sizeof(int64_t));
     }
     const cart_ego_camera cam = cameraOf(options);
     hipStream_t s = scratch.stream();
@@ -129,9 +153,33 @@ system_data_t VoxelMapModule::runInternal(System &, SystemRunData &data) {
         std::memcpy(tracked, pose, sizeof(pose));
         haveTracked = true;
     }
-    if (cart_voxel_map_integrate(map, &cam, pose, disparity->ptr<int16_t>(), disparity->step, cols, rows, mask ? mask->ptr<uint8_t>() : nullptr, mask ? mask->step : 0,
-                                 counts, s) != 0)
+    const std::vector<double> *nodes = nullptr;   // S35: every node's estimate, on the frames whose graph was optimised
+    if (options.rebuild) {
+        const int32_t node = data.getData<PoseGraphRecord>(CARTSLAM_KEY_POSE_GRAPH_RESULT)->node;
+        if (node >= 0) {   // a keyframe: its disparity goes into the store under the frame's id, with the motion labels or the zeroed plane
+            const image_t &plane = mask ? *mask : zeroPlane;
+            if (cart_plane_store_insert(store, data.id, disparity->ptr<int16_t>(), disparity->step, plane.ptr<uint8_t>(), plane.step, cols, rows, s) != 0)
+                failAbi("cart_plane_store_insert");
+            if (nodeFrame.size() <= (size_t)node) nodeFrame.resize((size_t)node + 1, 0);
+            nodeFrame[node] = data.id;
+        }
+        const auto published = data.getData<std::vector<double>>(CARTSLAM_KEY_POSE_GRAPH_NODES);
+        if (published && !published->empty()) nodes = published.get();
+    }
+    int64_t *rebuildCounts = reinterpret_cast<int64_t *>(scratch.dev<char>() + kRebuildCountsOffset);
+    if (nodes) {   // this frame is the newest node and is in the store: it is integrated once, after every other keyframe, in node order
+        const size_t count = std::min(nodes->size() / 12, nodeFrame.size());
+        result->rebuildIds.assign(nodeFrame.begin(), nodeFrame.begin() + count);
+        if (cart_voxel_map_rebuild(map, store, &cam, result->rebuildIds.data(), nodes->data(), (int)count, pose, options.useMotion ? 1 : 0, &result->rebuildUsed,
+                                   rebuildCounts, s) != 0)
+            failAbi("cart_voxel_map_rebuild");
+        result->rebuilt = (int)count;
+        hipCheck(hipMemcpyAsync(scratch.host<char>() + kRebuildCountsOffset, rebuildCounts, 2 * sizeof(int64_t), hipMemcpyDeviceToHost, s),
+                 "hipMemcpyAsync of the voxel map rebuild counts");
+    } else if (cart_voxel_map_integrate(map, &cam, pose, disparity->ptr<int16_t>(), disparity->step, cols, rows, mask ? mask->ptr<uint8_t>() : nullptr,
+                                        mask ? mask->step : 0, counts, s) != 0) {
         failAbi("cart_voxel_map_integrate");
+    }
     if (options.raycast &&
         cart_voxel_map_raycast(map, &cam, pose, cols, rows, model->ptr<int16_t>(), model->step, nullptr, 0, status->ptr<uint8_t>(), status->step, counts + 2, s) != 0)
         failAbi("cart_voxel_map_raycast");
@@ -146,6 +194,10 @@ system_data_t VoxelMapModule::runInternal(System &, SystemRunData &data) {
     }
     scratch.wait();   // the frame's only blocking synchronisation
     std::memcpy(result->counts, hostCounts, sizeof(result->counts));
+    if (result->rebuilt > 0) {   // the integrate's two words were not written on this frame: the rebuild's counts, cut to int32
+        std::memcpy(result->rebuildCounts, scratch.host<char>() + kRebuildCountsOffset, sizeof(result->rebuildCounts));
+        for (int k = 0; k < 2; ++k) result->counts[k] = (int32_t)std::min<int64_t>(result->rebuildCounts[k], INT32_MAX);
+    }
     if (options.raycast) std::memcpy(rays->rays, hostCounts + 2, sizeof(rays->rays));
     system_data_t out = MODULE_RETURN_ALL(MODULE_PAIR(CARTSLAM_KEY_VOXEL_MAP, result), MODULE_PAIR(CARTSLAM_KEY_DISPARITY_MODEL, model),
                                           MODULE_PAIR(CARTSLAM_KEY_DISPARITY_MODEL_STATUS, status), MODULE_PAIR(CARTSLAM_KEY_DISPARITY_MODEL_COUNTS, rays));

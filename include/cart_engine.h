@@ -1166,6 +1166,34 @@ int cart_voxel_map_raycast(cart_voxel_map *map, const cart_ego_camera *camera, c
  * into host_voxels (HOST); without a window every voxel is empty and the origin is (0, 0, 0).  origin3 = int64 [3]. */
 int cart_voxel_map_read(cart_voxel_map *map, cart_voxel *host_voxels, int64_t *origin3, void *stream);
 
+/* ---- Rebuilding the TSDF volume after a pose correction (spec S35) -------------------------------------------------
+ * An extension.  The frames of a cart_plane_store (S30, as it is: the int16 x16 disparity and a u8 plane per keyframe) integrated again,
+ * each through a NEW pose, into one fixed window, in one launch.  S33's running average depends on the order of the observations (floor
+ * division, and a weight cap that turns the mean into an exponential one), so the order is part of the spec: the caller's list order.
+ * S33's arithmetic to the letter; restated in tests/np_voxelmap_rebuild.py, byte for byte.
+ *   1. The window origin is S33's Window arithmetic applied to window_pose, with the map's own lookahead and voxel_size.
+ *   2. Every voxel of that window starts empty, (0, 0).
+ *   3. For k = 0 .. count - 1 in that order, an entry (ids[k], poses[k]) whose id the store holds (looked up newest first) is integrated
+ *      into that fixed window by S33's Integrate rule, gates 1 to 6 unchanged, with the map's own params: the image is the stored frame,
+ *      width x height of the store; with use_mask = 1 the stored u8 plane is integrate's mask (gate 3 passes where it is != 1), with
+ *      use_mask = 0 it is not read.  The window does not move between entries; voxels outside it do not exist.
+ *   4. Entries whose id is not in the store are skipped and counted: used = count - skipped.  An id listed twice is integrated twice.
+ *      count = 0 leaves an empty valid window at the new origin.
+ *   5. counts = the voxel updates summed over all used entries, and how many of them had f < 1.
+ * Afterwards the map is valid at that origin; cart_voxel_map_integrate, _raycast, _read and cart_model_track_refine continue on it as
+ * after any integrate.  The rebuilt volume equals cart_voxel_map_clear followed by one cart_voxel_map_integrate per used entry in list
+ * order, provided every entry's own pose yields the rebuild's window origin.
+ *
+ * ids = HOST uint64 [count], poses = HOST double [count][12], count in 0..4096, window_pose = HOST double [12]; used_out (HOST, may be
+ * NULL); counts = DEVICE int64 [2] (8-byte aligned, may be NULL: then no counter is touched; int64 because 4096 entries x 2^26 voxels pass
+ * int32).  Checked in this order, everything up to the objects without a device: count and use_mask, the camera, window_pose and every
+ * poses[k], the map, the store (on the map's device), the alignment of counts.  A refused call launches nothing and changes nothing.  The
+ * entries travel through the store's pinned buffer as in cart_plane_map_rebuild: the only host synchronisation is the wait for the
+ * previous rebuild's upload.  Holds the map, then the store. */
+int cart_voxel_map_rebuild(cart_voxel_map *map, cart_plane_store *store, const cart_ego_camera *camera, const uint64_t *ids,
+                           const double *poses, int count, const double *window_pose, int use_mask, int *used_out, int64_t *counts,
+                           void *stream);
+
 /* ---- Frame-to-model pose tracking against the TSDF volume (spec S34) ---------------------------------------------
  * An extension: the reference estimates no pose.  Gauss-Newton refinement of a camera-to-world pose P (3 x 4 as cart_voxel_map_raycast
  * takes it) so that the frame's back-projected pixels lie on the zero level set of a cart_voxel_map: minimises sum F(P p)^2.  fp64 with
