@@ -209,6 +209,16 @@ class Voxel(C.Structure):
 VOXEL_RAY_NONE, VOXEL_RAY_HIT, VOXEL_RAY_INSIDE = range(3)   # CART_VOXEL_RAY_*
 
 
+class MeshVertex(C.Structure):
+    # mirrors cart_mesh_vertex (include/cart_engine.h, spec S36)
+    _fields_ = [("position", C.c_float * 3), ("normal", C.c_float * 3)]
+
+
+class MeshQuad(C.Structure):
+    # mirrors cart_mesh_quad (include/cart_engine.h, spec S36)
+    _fields_ = [("v", C.c_int32 * 4)]
+
+
 class ModelTrackParams(C.Structure):
     # mirrors cart_model_track_params (include/cart_engine.h, spec S34); the defaults are cart_model_track_default_params' (build-owned, untuned)
     _fields_ = [(n, C.c_double) for n in ("residual_gate", "damping")] + [(n, C.c_int32) for n in ("iterations", "stride", "min_inliers")]
@@ -368,6 +378,8 @@ PROTOTYPES = {
     "cart_voxel_map_integrate": (_i, [_vp, C.POINTER(EgoCamera), C.POINTER(C.c_double), _vp, _sz, _i, _i, _vp, _sz, _vp, _vp]),
     "cart_voxel_map_raycast": (_i, [_vp, C.POINTER(EgoCamera), C.POINTER(C.c_double), _i, _i, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp]),
     "cart_voxel_map_read": (_i, [_vp, _vp, C.POINTER(C.c_int64), _vp]),
+    "cart_voxel_map_mesh": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, C.POINTER(C.c_int64), _vp]),
+    "cart_voxel_map_write": (_i, [_vp, _vp, C.POINTER(C.c_int64), _vp]),
     "cart_voxel_map_rebuild": (_i, [_vp, _vp, C.POINTER(EgoCamera), C.POINTER(C.c_uint64), C.POINTER(C.c_double), _i, C.POINTER(C.c_double), _i, C.POINTER(_i), _vp, _vp]),
     "cart_model_track_default_params": (None, [C.POINTER(ModelTrackParams)]),
     "cart_model_track_create": (_i, [_vp, _i, _i, C.POINTER(_vp)]),

@@ -1413,6 +1413,8 @@ class DisparityFusion(_DeviceObject):
 
 
 VOXEL_DTYPE = np.dtype([("tsdf", "<i2"), ("weight", "<u2")])   # cart_voxel
+MESH_VERTEX_DTYPE = np.dtype([("position", "<f4", 3), ("normal", "<f4", 3)])   # cart_mesh_vertex
+MESH_QUAD_DTYPE = np.dtype([("v", "<i4", 4)])                                  # cart_mesh_quad
 
 
 def voxel_map_params(**fields):
@@ -1495,6 +1497,40 @@ class VoxelMap(_DeviceObject):
         self._check(self._lib.cart_voxel_map_read(self._h, C.c_void_p(voxels.ctypes.data), o, _stream_ptr()), "cart_voxel_map_read")
         return voxels, tuple(o)
 
+    def write(self, voxels, origin):
+        """The counterpart of read(): voxels VOXEL_DTYPE [cells_z, cells_y, cells_x] in window order (host) become the window at origin =
+        (ox, oy, oz), each a multiple of 8 within 2^27; synchronises."""
+        v = np.ascontiguousarray(voxels, VOXEL_DTYPE)
+        if v.shape != (self.cells_z, self.cells_y, self.cells_x):
+            raise EngineError("voxels must be a VOXEL_DTYPE array of [cells_z, cells_y, cells_x]")
+        o = (C.c_int64 * 3)(*[int(c) for c in origin])
+        self._check(self._lib.cart_voxel_map_write(self._h, C.c_void_p(v.ctypes.data), o, _stream_ptr()), "cart_voxel_map_write")
+
+    def mesh(self, max_vertices, max_quads, min_weight=0, raw=False, stream=None):
+        """The surface of the current window by naive surface nets (spec S36).  min_weight = 0 takes the map's own.
+        -> (vertices MESH_VERTEX_DTYPE [written], quads MESH_QUAD_DTYPE [written], counts int32 [4] = vertices found, quads found, vertices
+        written, quads written, (ox, oy, oz)): positions are metres relative to the window origin; the mesh is whole iff found == written
+        for both.  raw=True returns the device tensors instead (vertices float32 [max_vertices, 6], quads int32 [max_quads, 4], counts int32
+        [4]) with no host round trip: rows beyond the written counts are uninitialised."""
+        import torch
+        nv, nq = int(max_vertices), int(max_quads)
+        with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):   # the allocations on the call's stream
+            vt = torch.empty((max(nv, 0), 6), dtype=torch.float32, device="cuda")
+            qt = torch.empty((max(nq, 0), 4), dtype=torch.int32, device="cuda")
+            n = torch.empty(4, dtype=torch.int32, device="cuda")
+        sp = C.c_void_p(stream.cuda_stream) if stream is not None else _stream_ptr()
+        o = (C.c_int64 * 3)()
+        self._check(self._lib.cart_voxel_map_mesh(self._h, int(min_weight), C.c_void_p(vt.data_ptr()), nv, C.c_void_p(qt.data_ptr()), nq, C.c_void_p(n.data_ptr()), o, sp),
+                    "cart_voxel_map_mesh")
+        if raw:
+            return vt, qt, n, tuple(o)
+        if stream is not None:
+            stream.synchronize()
+        counts = n.cpu().numpy()
+        vertices = vt[:int(counts[2])].cpu().numpy().view(MESH_VERTEX_DTYPE).reshape(-1)
+        quads = qt[:int(counts[3])].cpu().numpy().view(MESH_QUAD_DTYPE).reshape(-1)
+        return vertices, quads, counts, tuple(o)
+
     def clear(self):
         self._check(self._lib.cart_voxel_map_clear(self._h), "cart_voxel_map_clear")
 
@@ -1521,6 +1557,26 @@ class VoxelMap(_DeviceObject):
         if n is not None and stream is not None:
             stream.synchronize()
         return self.window()[0], used.value, (n.cpu().numpy() if n is not None else None)
+
+
+def write_ply(path, vertices, quads, origin, voxel_size):
+    """A mesh of VoxelMap.mesh as a binary little-endian PLY file with quad faces and normals.  origin = the window origin (ox, oy, oz) in
+    voxels: the positions are moved to the world frame, o_a voxel_size + p_a in fp64, before the conversion to float."""
+    v = np.asarray(vertices, MESH_VERTEX_DTYPE).reshape(-1)
+    q = np.asarray(quads, MESH_QUAD_DTYPE).reshape(-1)
+    shift = np.array([int(c) for c in origin], np.float64) * np.float64(voxel_size)
+    out = np.empty(len(v), np.dtype([("p", "<f4", 3), ("n", "<f4", 3)]))
+    out["p"] = (shift + v["position"].astype(np.float64)).astype(np.float32)
+    out["n"] = v["normal"]
+    faces = np.empty(len(q), np.dtype([("k", "u1"), ("v", "<i4", 4)]))
+    faces["k"], faces["v"] = 4, q["v"]
+    header = "ply\nformat binary_little_endian 1.0\ncomment cartslam voxel_map surface nets\nelement vertex %d\n" % len(v) + \
+             "".join("property float %s\n" % c for c in ("x", "y", "z", "nx", "ny", "nz")) + \
+             "element face %d\nproperty list uchar int vertex_indices\nend_header\n" % len(q)
+    with open(path, "wb") as f:
+        f.write(header.encode("ascii"))
+        f.write(out.tobytes())
+        f.write(faces.tobytes())
 
 
 MODEL_TRACK_RESULT_DTYPE = np.dtype([("R", "<f8", 9), ("t", "<f8", 3), ("rms_initial", "<f8"), ("rms", "<f8"), ("status", "<i4"), ("n_candidates", "<i4"),

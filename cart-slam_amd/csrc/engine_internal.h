@@ -655,6 +655,29 @@ struct VoxelRebuildArgs {
     int32_t *counters;                                  // the map's block; the rebuild's words start at uint64 word 4
 };
 void launch_voxel_rebuild(const VoxelRebuildArgs &a, hipStream_t s);   // one launch: every voxel of the window is written
+// ---- surface mesh of the volume by naive surface nets (voxelmesh_kernels.hip) ----
+// A thread owns the window voxel of its linear index v = (z ny + y) nx + x, which is also the order of the cells and of the voxels that own
+// edges; a workgroup of kMeshBlock consecutive voxels is the unit of the two prefix sums.
+#ifndef CART_MESH_BLOCK
+#define CART_MESH_BLOCK 1024            // the A/B of DESIGN.md 7.18 also builds 256 and 512: fewer, larger units shorten the one-workgroup scan
+#endif
+constexpr int kMeshBlock = CART_MESH_BLOCK;   // a multiple of 64; the last workgroup may be partly outside the volume
+constexpr int kMeshScanThreads = 1024;  // the one workgroup of the scan
+constexpr uint32_t kMeshKnown = 1u, kMeshActive = 2u, kMeshCrossX = 4u, kMeshInside = 32u;   // the cell word; cross y, z = 8, 16
+constexpr int kMeshIndexShift = 6;      // the cell's vertex index (< 2^26) above the flags
+struct VoxelMeshArgs {
+    VoxelGrid grid;
+    double voxel_size;
+    int min_weight;                                     // resolved: never 0
+    int max_vertices, max_quads;
+    int blocks;                                         // workgroups of the per-voxel passes; 0 = the map has no window
+    uint32_t *cells;                                    // [nz ny nx] cell words, window order
+    uint32_t *block_vertices, *block_quads;             // [blocks] counts, then exclusive offsets
+    cart_mesh_vertex *vertices;
+    cart_mesh_quad *quads;
+    int32_t *counts;
+};
+void launch_voxel_mesh(const VoxelMeshArgs &a, hipStream_t s);   // 5 launches, or 1 without a window
 // ---- frame-to-model pose tracking against the TSDF volume (modeltrack_kernels.hip) ----
 constexpr int kTrackCols = 2;           // sampled columns of a lane whose image loads and corner gathers are issued together
 struct ModelTrackArgs {                 // the sums, the row partials and the pose state are S26's (kDense*, DenseEgoState)

@@ -14,6 +14,8 @@ struct cart_voxel_map : cart_amd::DeviceObject {
     int32_t *counters = nullptr;            // [kVoxelCounters]
     bool valid = false;                     // a window exists (guarded by mu)
     int64_t o[3] = {0, 0, 0};               // its origin in absolute voxels
+    uint32_t *mesh_cells = nullptr;         // cart_voxel_map_mesh's workspace (S36), allocated by its first call: [nz ny nx] cell words ...
+    uint32_t *mesh_blocks = nullptr;        // ... and [2][nz ny nx / kMeshBlock] per-workgroup counts
 };
 
 }  // extern "C"

@@ -2,7 +2,8 @@
 // arithmetic (host, int64) and the cart_voxel_map device object, which owns the volume and the counter block.  The volume is never
 // cleared by hipMemset: the first integrate after create / clear empties the whole window by a kernel on the call's stream.  The counter
 // block is zeroed once at create and left all zero by every call.  cart_voxel_map_rebuild (S35) integrates the frames of a cart_plane_store
-// (engine_planemap.h) into a fixed window in one launch.
+// (engine_planemap.h) into a fixed window in one launch.  cart_voxel_map_mesh (S36) extracts the window's surface (voxelmesh_kernels.hip) and
+// cart_voxel_map_write puts host voxels under the kernels.
 
 #include "engine_host.h"
 #include "engine_planemap.h"
@@ -222,6 +223,68 @@ int cart_voxel_map_read(cart_voxel_map *m, cart_voxel *host_voxels, int64_t *ori
             std::copy(row, row + g.mx, dst + (g.nx - g.mx));
         }
     for (int a = 0; a < 3; ++a) origin3[a] = m->o[a];
+    return 0;
+}
+
+int cart_voxel_map_mesh(cart_voxel_map *m, int min_weight, cart_mesh_vertex *vertices, int max_vertices, cart_mesh_quad *quads, int max_quads,
+                        int32_t *counts, int64_t *origin3, void *stream_) {
+    if (min_weight < 0 || min_weight > 65535) return fail("min_weight must be 0 (the map's own) or in [1, 65535]");
+    if (max_vertices < 1 || max_vertices > 1 << 26) return fail("max_vertices must be in [1, 2^26]");
+    if (max_quads < 1 || max_quads > 1 << 26) return fail("max_quads must be in [1, 2^26]");
+    if (!m) return fail("map is NULL");
+    if (!vertices) return fail("vertices is NULL");
+    if (!quads) return fail("quads is NULL");
+    if (!counts) return fail("counts is NULL");
+    const size_t vbytes = (size_t)max_vertices * sizeof(cart_mesh_vertex), qbytes = (size_t)max_quads * sizeof(cart_mesh_quad);
+    const Extent all[] = {Extent{"vertices", vertices, vbytes, 4, vbytes, 1}, Extent{"quads", quads, qbytes, 4, qbytes, 1}, Extent{"counts", counts, 16, 4, 16, 1}};
+    for (const Extent &x : all)
+        if (x.begin() % 4) return fail(std::string(x.name) + " must be 4-byte aligned");   // not pitched: its own wording
+    if (check_outputs_apart(all, 0, 3)) return -1;
+
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    ObjectCall call(*m, stream);
+    if (call.begin()) return -1;
+    const size_t voxels = (size_t)m->n[0] * m->n[1] * m->n[2], blocks = (voxels + kMeshBlock - 1) / kMeshBlock;
+    // the first call: the workspace, kept for the object's life (a call whose second allocation failed leaves the first for the next one)
+    if (!m->mesh_cells && m->alloc(&m->mesh_cells, voxels * sizeof(uint32_t))) return -1;
+    if (!m->mesh_blocks && m->alloc(&m->mesh_blocks, 2 * blocks * sizeof(uint32_t))) return -1;
+    VoxelMeshArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.grid = grid_of(m); a.voxel_size = m->p.voxel_size; a.min_weight = min_weight ? min_weight : m->p.min_weight;
+    a.max_vertices = max_vertices; a.max_quads = max_quads; a.blocks = m->valid ? (int)blocks : 0;
+    a.cells = m->mesh_cells; a.block_vertices = m->mesh_blocks; a.block_quads = m->mesh_blocks + blocks;
+    a.vertices = vertices; a.quads = quads; a.counts = counts;
+    launch_voxel_mesh(a, stream);
+    HIP_TRY(hipGetLastError());
+    if (origin3)
+        for (int k = 0; k < 3; ++k) origin3[k] = m->valid ? m->o[k] : 0;
+    return 0;
+}
+
+int cart_voxel_map_write(cart_voxel_map *m, const cart_voxel *host_voxels, const int64_t *origin3, void *stream_) {
+    if (!origin3) return fail("origin3 is NULL");
+    for (int a = 0; a < 3; ++a)
+        if (origin3[a] % 8 || std::llabs(origin3[a]) > ((int64_t)1 << 27)) return fail("origin3[" + std::to_string(a) + "] must be a multiple of 8 within 2^27");
+    if (!m) return fail("map is NULL");
+    if (!host_voxels) return fail("host_voxels is NULL");
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    ObjectCall call(*m, stream);
+    if (call.begin()) return -1;
+    VoxelGrid g = grid_of(m);
+    g.mx = floor_mod(origin3[0], g.nx); g.my = floor_mod(origin3[1], g.ny); g.mz = floor_mod(origin3[2], g.nz);
+    const size_t count = (size_t)g.nx * g.ny * g.nz;
+    std::vector<cart_voxel> stored(count);   // window order -> toroidal storage: two pieces per row, the inverse of _read
+    for (int rz = 0; rz < g.nz; ++rz)
+        for (int ry = 0; ry < g.ny; ++ry) {
+            cart_voxel *row = stored.data() + ((size_t)((rz + g.mz) % g.nz) * g.ny + (size_t)((ry + g.my) % g.ny)) * g.nx;
+            const cart_voxel *src = host_voxels + ((size_t)rz * g.ny + ry) * g.nx;
+            std::copy(src, src + (g.nx - g.mx), row + g.mx);
+            std::copy(src + (g.nx - g.mx), src + g.nx, row);
+        }
+    HIP_TRY(hipMemcpyAsync(m->voxels, stored.data(), count * sizeof(cart_voxel), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    for (int a = 0; a < 3; ++a) m->o[a] = origin3[a];
+    m->valid = true;
     return 0;
 }
 

@@ -7,6 +7,9 @@
 // With "rebuild" (spec DESIGN.md S35; needs "pose_key": "pose_graph" and no "track") the module keeps every keyframe's disparity in a
 // device-resident store, and on a frame whose pose graph was optimised it rebuilds the whole volume from them through the corrected node
 // poses (cart_voxel_map_rebuild) in place of the integrate, as the plane_map module does for its grid (S30).
+// With "mesh" (spec DESIGN.md S36) every "mesh_interval"-th frame the module sees also extracts the window's surface after the integrate or
+// rebuild (cart_voxel_map_mesh) and downloads the written records, published as "voxel_mesh".  The written counts size the download, so
+// such a frame waits for the device twice; every other frame, and every frame without "mesh", once as before.
 #pragma once
 #include <array>
 #include <mutex>
@@ -20,6 +23,7 @@
 #define CARTSLAM_KEY_DISPARITY_MODEL "disparity_model"                    // CV_16SC1, the format of "disparity"; empty without "raycast"
 #define CARTSLAM_KEY_DISPARITY_MODEL_STATUS "disparity_model_status"      // CV_8UC1: CART_VOXEL_RAY_*
 #define CARTSLAM_KEY_DISPARITY_MODEL_COUNTS "disparity_model_counts"      // VoxelRayCounts
+#define CARTSLAM_KEY_VOXEL_MESH "voxel_mesh"                              // VoxelMesh, with "mesh" only
 #define CARTSLAM_KEY_MODEL_POSE "model_pose"                              // EgoMotion, with "track" only: the tracked pose and the relative pose between tracked poses
 #define CARTSLAM_KEY_MODEL_TRACK_RESULT "model_track_result"              // cart_model_track_result as the device wrote it, with "track" only
 
@@ -33,6 +37,14 @@ struct VoxelMap {
     int rebuilt = 0, rebuildUsed = 0;   // on a frame that rebuilt the volume (S35): the entries handed in, and those the store still held;
     int64_t rebuildCounts[2] = {0, 0};  // the rebuild's own counts (`counts` holds them cut to int32)
     std::vector<uint64_t> rebuildIds;   // the frame ids of the entries, in list order
+};
+struct VoxelMesh {                      // S36; `extracted` is false on the frames between two extractions, and everything else empty
+    bool extracted = false;
+    int64_t origin[3] = {0, 0, 0};      // the window the mesh belongs to
+    double voxelSize = 0;
+    int32_t counts[4] = {0, 0, 0, 0};   // vertices found, quads found, vertices written, quads written
+    std::vector<cart_mesh_vertex> vertices;   // the written ones; positions relative to the window origin
+    std::vector<cart_mesh_quad> quads;
 };
 struct VoxelRayCounts {
     int32_t rays[3] = {0, 0, 0};        // CART_VOXEL_RAY_NONE, _HIT, _INSIDE
@@ -51,6 +63,8 @@ struct VoxelMapOptions : CameraOptions {   // the factory fills the camera from 
     bool track = false;                       // S34: refine every frame's pose against the volume before integrating it
     bool rebuild = false;                     // S35: keep the keyframes' disparity and rebuild the volume when the pose graph was optimised
     int storeCapacity = 256;                  // keyframes the store holds (a ring: the oldest leaves)
+    bool mesh = false;                        // S36: extract the window's surface every meshInterval-th frame
+    int meshInterval = 10, meshMaxVertices = 1 << 20, meshMaxQuads = 1 << 20, meshMinWeight = 0;   // 0 = minWeight
     double residualGate = 0.9, damping = 0.01;   // cart_model_track_default_params
     int iterations = 4, stride = 1, minInliers = 1024;
 };
@@ -74,6 +88,8 @@ class VoxelMapModule : public SyncWrapperSystemModule {
     image_t zeroPlane;                     // with "rebuild" and without "use_motion": the stored u8 plane, zeroed once
     bool haveTracked = false;         // with "track": `tracked` holds the previous frame's tracked pose
     double tracked[12] = {};
+    DeviceScratch meshBuffers;        // with "mesh": the device vertices and quads of one extraction (no stream, no host side)
+    long long meshFrames = 0;         // with "mesh": frames seen
     DeviceScratch scratch;            // the one stream; the tracking record and the five counts on the device and the pinned buffer they are downloaded through
 };
 }  // namespace cart

@@ -302,6 +302,11 @@ void applyModuleConfig(const Value &modulesConfig, std::shared_ptr<System> syste
             o.track = get(moduleConfig, "track", o.track);   // S34: the pose refined against the volume, published as "model_pose"
             o.rebuild = get(moduleConfig, "rebuild", o.rebuild);   // S35: the volume rebuilt from stored keyframes when the pose graph was optimised
             o.storeCapacity = get(moduleConfig, "store_capacity", o.storeCapacity);
+            o.mesh = get(moduleConfig, "mesh", o.mesh);   // S36: the window's surface as a quad mesh, published as "voxel_mesh" every mesh_interval-th frame
+            o.meshInterval = get(moduleConfig, "mesh_interval", o.meshInterval);
+            o.meshMaxVertices = get(moduleConfig, "mesh_max_vertices", o.meshMaxVertices);
+            o.meshMaxQuads = get(moduleConfig, "mesh_max_quads", o.meshMaxQuads);
+            o.meshMinWeight = get(moduleConfig, "mesh_min_weight", o.meshMinWeight);
             o.residualGate = get(moduleConfig, "residual_gate", o.residualGate);
             o.damping = get(moduleConfig, "damping", o.damping);
             o.iterations = get(moduleConfig, "iterations", o.iterations);

@@ -191,6 +191,16 @@ int main(int argc, char **argv) {
                         append(r, vm->rebuildIds.data(), vm->rebuildIds.size() * sizeof(uint64_t));
                     }
                 }
+                if (run->hasData(CARTSLAM_KEY_VOXEL_MESH)) {   // voxel_map with "mesh", on the frames that extracted: int64 origin [3]; double voxel_size; int32 counts [4]; the written vertices (24 bytes) and quads (16 bytes)
+                    auto mesh = run->getData<cart::VoxelMesh>(CARTSLAM_KEY_VOXEL_MESH);
+                    if (mesh->extracted) {
+                        std::ofstream o = writeBin(dump, id, CARTSLAM_KEY_VOXEL_MESH, mesh->origin, sizeof(mesh->origin));
+                        append(o, &mesh->voxelSize, sizeof(mesh->voxelSize));
+                        append(o, mesh->counts, sizeof(mesh->counts));
+                        append(o, mesh->vertices.data(), mesh->vertices.size() * sizeof(cart_mesh_vertex));
+                        append(o, mesh->quads.data(), mesh->quads.size() * sizeof(cart_mesh_quad));
+                    }
+                }
                 if (run->hasData(CARTSLAM_KEY_MODEL_POSE)) {   // voxel_map with "track": the 136-byte cart_model_track_result, then the tracked pose as 12 doubles
                     auto record = run->getData<cart_model_track_result>(CARTSLAM_KEY_MODEL_TRACK_RESULT);
                     auto tracked = run->getData<cart::EgoMotion>(CARTSLAM_KEY_MODEL_POSE);

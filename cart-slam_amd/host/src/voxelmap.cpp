@@ -1,4 +1,4 @@
-// voxelmap.cpp -- VoxelMapModule (cartslam_amd/modules/voxelmap.hpp): the rolling TSDF voxel map with model raycast, spec DESIGN.md S33; its rebuild from stored keyframes, S35.
+// voxelmap.cpp -- VoxelMapModule (cartslam_amd/modules/voxelmap.hpp): the rolling TSDF voxel map with model raycast, spec DESIGN.md S33; its rebuild from stored keyframes, S35; its surface mesh, S36.
 #include "cartslam_amd/modules/voxelmap.hpp"
 
 #include <algorithm>
@@ -30,6 +30,8 @@ void relativeOf(const double prev[12], const double cur[12], double R[9], double
 constexpr size_t kCountsOffset = sizeof(cart_model_track_result);   // of the five counts in the scratch buffers, after the tracking record
 constexpr size_t kRebuildCountsOffset = kCountsOffset + 8 * sizeof(int32_t);   // of the rebuild's two int64 counts, 8-byte aligned
 static_assert(kRebuildCountsOffset % 8 == 0, "the rebuild's counts are int64");
+constexpr size_t kMeshCountsOffset = kRebuildCountsOffset + 2 * sizeof(int64_t);   // of the mesh's four counts
+constexpr size_t kScratchBytes = kMeshCountsOffset + 4 * sizeof(int32_t);
 }  // namespace
 
 VoxelMapModule::VoxelMapModule(const VoxelMapOptions &options)
@@ -58,6 +60,12 @@ VoxelMapModule::VoxelMapModule(const VoxelMapOptions &options)
         (void)cart_plane_store_create(nullptr, 1, 1, options.storeCapacity, &none);
         if (std::strcmp(cart_last_error(nullptr), "bad arguments") != 0) throw std::invalid_argument(std::string("store_capacity: ") + cart_last_error(nullptr));
     }
+    if (options.mesh) {
+        if (options.meshInterval < 1) throw std::invalid_argument("mesh_interval must be at least 1");
+        if (options.meshMaxVertices < 1 || options.meshMaxVertices > 1 << 26) throw std::invalid_argument("mesh_max_vertices must be in [1, 2^26]");
+        if (options.meshMaxQuads < 1 || options.meshMaxQuads > 1 << 26) throw std::invalid_argument("mesh_max_quads must be in [1, 2^26]");
+        if (options.meshMinWeight < 0 || options.meshMinWeight > 65535) throw std::invalid_argument("mesh_min_weight must be 0 (min_weight) or in [1, 65535]");
+    }
     this->requiresData.push_back(module_dependency_t(options.disparityKey));
     this->requiresData.push_back(module_dependency_t(options.poseKey));
     if (options.useMotion) this->requiresData.push_back(module_dependency_t(CARTSLAM_KEY_MOTION));
@@ -74,6 +82,7 @@ VoxelMapModule::VoxelMapModule(const VoxelMapOptions &options)
         this->providesData.push_back(CARTSLAM_KEY_MODEL_POSE);
         this->providesData.push_back(CARTSLAM_KEY_MODEL_TRACK_RESULT);
     }
+    if (options.mesh) this->providesData.push_back(CARTSLAM_KEY_VOXEL_MESH);
 }
 
 VoxelMapModule::~VoxelMapModule() {
@@ -115,7 +124,9 @@ system_data_t VoxelMapModule::runInternal(System &, SystemRunData &data) {
             }
         }
         scratch.create();
-        scratch.reserve(kRebuildCountsOffset + 2 * sizeof(int64_t), kRebuildCountsOffset + 2 * sizeof(int64_t));
+        scratch.reserve(kScratchBytes, kScratchBytes);
+        if (options.mesh)
+            meshBuffers.reserve((size_t)options.meshMaxVertices * sizeof(cart_mesh_vertex) + (size_t)options.meshMaxQuads * sizeof(cart_mesh_quad), 0);
     }
     const cart_ego_camera cam = cameraOf(options);
     hipStream_t s = scratch.stream();
@@ -185,6 +196,28 @@ system_data_t VoxelMapModule::runInternal(System &, SystemRunData &data) {
         failAbi("cart_voxel_map_raycast");
     int32_t *hostCounts = reinterpret_cast<int32_t *>(scratch.host<char>() + kCountsOffset);
     hipCheck(hipMemcpyAsync(hostCounts, counts, (options.raycast ? 5 : 2) * sizeof(int32_t), hipMemcpyDeviceToHost, s), "hipMemcpyAsync of the voxel map counts");
+    std::shared_ptr<VoxelMesh> mesh;
+    if (options.mesh) {
+        mesh = std::make_shared<VoxelMesh>();
+        if (++meshFrames % options.meshInterval == 0) {   // S36: the surface of the window as this frame left it
+            cart_mesh_vertex *vertices = meshBuffers.dev<cart_mesh_vertex>();
+            cart_mesh_quad *quads = reinterpret_cast<cart_mesh_quad *>(meshBuffers.dev<char>() + (size_t)options.meshMaxVertices * sizeof(cart_mesh_vertex));
+            int32_t *meshCounts = reinterpret_cast<int32_t *>(scratch.dev<char>() + kMeshCountsOffset);
+            if (cart_voxel_map_mesh(map, options.meshMinWeight, vertices, options.meshMaxVertices, quads, options.meshMaxQuads, meshCounts, mesh->origin, s) != 0)
+                failAbi("cart_voxel_map_mesh");
+            hipCheck(hipMemcpyAsync(scratch.host<char>() + kMeshCountsOffset, meshCounts, sizeof(mesh->counts), hipMemcpyDeviceToHost, s), "hipMemcpyAsync of the mesh counts");
+            scratch.wait();   // the second synchronisation of such a frame: the written counts size the download
+            std::memcpy(mesh->counts, scratch.host<char>() + kMeshCountsOffset, sizeof(mesh->counts));
+            mesh->vertices.resize((size_t)mesh->counts[2]);
+            mesh->quads.resize((size_t)mesh->counts[3]);
+            if (mesh->counts[2])
+                hipCheck(hipMemcpyAsync(mesh->vertices.data(), vertices, mesh->vertices.size() * sizeof(cart_mesh_vertex), hipMemcpyDeviceToHost, s), "hipMemcpyAsync of the mesh vertices");
+            if (mesh->counts[3])
+                hipCheck(hipMemcpyAsync(mesh->quads.data(), quads, mesh->quads.size() * sizeof(cart_mesh_quad), hipMemcpyDeviceToHost, s), "hipMemcpyAsync of the mesh quads");
+            mesh->voxelSize = options.voxelSize;
+            mesh->extracted = true;
+        }
+    }
     int valid = 0;
     if (cart_voxel_map_window(map, result->origin, result->cells, &valid) != 0) failAbi("cart_voxel_map_window");
     result->voxelSize = options.voxelSize;
@@ -201,6 +234,7 @@ system_data_t VoxelMapModule::runInternal(System &, SystemRunData &data) {
     if (options.raycast) std::memcpy(rays->rays, hostCounts + 2, sizeof(rays->rays));
     system_data_t out = MODULE_RETURN_ALL(MODULE_PAIR(CARTSLAM_KEY_VOXEL_MAP, result), MODULE_PAIR(CARTSLAM_KEY_DISPARITY_MODEL, model),
                                           MODULE_PAIR(CARTSLAM_KEY_DISPARITY_MODEL_STATUS, status), MODULE_PAIR(CARTSLAM_KEY_DISPARITY_MODEL_COUNTS, rays));
+    if (options.mesh) out.push_back(MODULE_PAIR(CARTSLAM_KEY_VOXEL_MESH, mesh));
     if (options.track) {
         out.push_back(MODULE_PAIR(CARTSLAM_KEY_MODEL_POSE, modelPose));
         out.push_back(MODULE_PAIR(CARTSLAM_KEY_MODEL_TRACK_RESULT, trackResult));

@@ -1194,6 +1194,59 @@ int cart_voxel_map_rebuild(cart_voxel_map *map, cart_plane_store *store, const c
                            const double *poses, int count, const double *window_pose, int use_mask, int *used_out, int64_t *counts,
                            void *stream);
 
+/* ---- Surface mesh of the TSDF volume (spec S36) --------------------------------------------------------------------
+ * An extension.  The surface of the current window as an indexed quad mesh with per-vertex normals, by naive surface nets: one vertex per
+ * cell the surface passes through, one quad per voxel edge the surface crosses.  S33's arithmetic rules: fp64 with + - * / floor sqrt,
+ * every expression in the written association order; no atomic decides where a record lands.  Restated in tests/np_voxelmesh.py, byte
+ * for byte.
+ *   Cells: with a window of Nx x Ny x Nz voxels at origin o, cell c = (cx, cy, cz) exists for 0 <= c_a <= N_a - 2 (window-local indices:
+ *   the window's last and first voxel are not neighbours, although they are adjacent in the toroidal storage).  Its corners are the window
+ *   voxels c + (dx, dy, dz), d in {0,1}^3, with corner tsdf t[dy][dz][dx].  mw = the call's min_weight, or the map's own when that is 0.
+ *   A cell is known iff all eight corners have weight >= mw; a corner is inside iff tsdf <= 0 (the raycast's F <= 0); a cell is active
+ *   iff it is known and its corners are neither all inside nor all outside.
+ *   Vertex of an active cell: the twelve cell edges in this order: the four x-edges (dy, dz) = (0,0), (1,0), (0,1), (1,1), the four y-edges
+ *   (dx, dz) in the same order, the four z-edges (dx, dy) in the same order.  An edge from corner a (lower) to corner b (upper along its
+ *   axis) crosses iff exactly one of them is inside; then f = (double)t_a / (double)(t_a - t_b) (the subtraction in integers, never zero
+ *   on a crossing edge), and the edge contributes f along its own axis and (double)d along the other two.  Three sums s_x, s_y, s_z start
+ *   at 0.0 and take the contributions in edge order; n counts the crossings.  l_a = s_a / (double)n, p_a = (((double)c_a + 0.5) + l_a)
+ *   voxel_size: metres relative to the window origin; the world position is o_a voxel_size + p_a.
+ *   Normal: (gx, gy, gz) = the gradient of S34's trilinear sample of the cell's eight corners at fr = (l_x, l_y, l_z); n2 = (gx gx + gy gy)
+ *   + gz gz; the normal is g_a / sqrt(n2) where n2 > 0, else (0, 0, 0).  It points towards positive tsdf: free space, the cameras' side.
+ *   Vertex record: position and normal, each component the fp64 value converted once to fp32; vertices are ordered by ascending cell index
+ *   (cz (Ny - 1) + cy) (Nx - 1) + cx.
+ *   Quads: voxel (i, j, k) owns the three edges that leave it in +x, +y, +z, taken in that axis order.  An edge emits a quad iff its upper
+ *   voxel is in the window, the edge crosses, and the four cells around it all exist and are known (they are then active):
+ *     x-edge: (i, j-1, k-1), (i, j, k-1), (i, j, k), (i, j-1, k)
+ *     y-edge: (i-1, j, k-1), (i-1, j, k), (i, j, k), (i, j, k-1)
+ *     z-edge: (i-1, j-1, k), (i, j-1, k), (i, j, k), (i-1, j, k)
+ *   The record holds the four cells' vertex indices, in the listed order when the lower voxel is inside and reversed (4th, 3rd, 2nd, 1st)
+ *   when it is outside: (p2 - p0) x (p3 - p1) then points to free space.  Quads are ordered by ascending (cell index of (i, j, k), axis).
+ *   Capacity: the first max_vertices vertices and the first max_quads quads in these orders are written and nothing beyond them is touched;
+ *   after a truncation a quad may name a vertex that was not written: a consumer takes the mesh iff found == written for both.
+ * Limits: no colour, no decimation; surface nets round sharp edges and can be non-manifold where two surfaces meet within a cell; a mesh
+ * covers the current window only. */
+typedef struct cart_mesh_vertex {
+    float position[3];                        /* metres, relative to the window origin */
+    float normal[3];                          /* unit length, or (0, 0, 0) */
+} cart_mesh_vertex;                           /* 24 bytes */
+typedef struct cart_mesh_quad {
+    int32_t v[4];                             /* vertex indices */
+} cart_mesh_quad;
+/* Extension.  min_weight = 0 (the map's own) or 1..65535; vertices = DEVICE cart_mesh_vertex [max_vertices], quads = DEVICE cart_mesh_quad
+ * [max_quads], both 4-byte aligned, capacities in 1..2^26; counts = DEVICE int32 [4] (4-byte aligned) = vertices found, quads found,
+ * vertices written, quads written: all 0 without a window.  origin3 = HOST int64 [3] or NULL: the window origin the mesh belongs to, written
+ * under the map's lock as cart_voxel_map_window does (zeros without a window).  Reads the volume only.  Checked in this order, all before
+ * any device call: min_weight, the capacities, the object, then pointers, alignment and overlaps (no output may overlap another).  Five
+ * launches, no host synchronisation, except that the first call on a map allocates its workspace: one 4-byte word per voxel plus two
+ * 4-byte words per 1024 voxels, 4.01 bytes per voxel, as much as the volume itself, kept until the map is destroyed. */
+int cart_voxel_map_mesh(cart_voxel_map *map, int min_weight, cart_mesh_vertex *vertices, int max_vertices, cart_mesh_quad *quads,
+                        int max_quads, int32_t *counts, int64_t *origin3, void *stream);
+/* Extension.  The counterpart of cart_voxel_map_read: host_voxels (HOST, window order [cells_z][cells_y][cells_x]) become the window at
+ * origin3 = HOST int64 [3], each component a multiple of 8 with |o_a| <= 2^27 (every origin the window arithmetic can produce).  Checked
+ * before any device call: origin3, the object, host_voxels.  Synchronises `stream`, as _read does.  Afterwards the map is valid at that
+ * origin; cart_voxel_map_integrate, _raycast, _read, _mesh and cart_model_track_refine continue on it as after any integrate. */
+int cart_voxel_map_write(cart_voxel_map *map, const cart_voxel *host_voxels, const int64_t *origin3, void *stream);
+
 /* ---- Frame-to-model pose tracking against the TSDF volume (spec S34) ---------------------------------------------
  * An extension: the reference estimates no pose.  Gauss-Newton refinement of a camera-to-world pose P (3 x 4 as cart_voxel_map_raycast
  * takes it) so that the frame's back-projected pixels lie on the zero level set of a cart_voxel_map: minimises sum F(P p)^2.  fp64 with
