@@ -206,6 +206,12 @@ class Voxel(C.Structure):
     _fields_ = [("tsdf", C.c_int16), ("weight", C.c_uint16)]
 
 
+class VoxelRgb(C.Structure):
+    # mirrors cart_voxel_rgb (include/cart_engine.h, spec S37)
+    _fields_ = [("b", C.c_uint8), ("g", C.c_uint8), ("r", C.c_uint8), ("weight", C.c_uint8)]
+
+
+VOXEL_COLOR_DEFAULT_MAX_WEIGHT = 64   # CART_VOXEL_COLOR_DEFAULT_MAX_WEIGHT (build-owned, untuned)
 VOXEL_RAY_NONE, VOXEL_RAY_HIT, VOXEL_RAY_INSIDE = range(3)   # CART_VOXEL_RAY_*
 
 
@@ -381,6 +387,15 @@ PROTOTYPES = {
     "cart_voxel_map_mesh": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, C.POINTER(C.c_int64), _vp]),
     "cart_voxel_map_write": (_i, [_vp, _vp, C.POINTER(C.c_int64), _vp]),
     "cart_voxel_map_rebuild": (_i, [_vp, _vp, C.POINTER(EgoCamera), C.POINTER(C.c_uint64), C.POINTER(C.c_double), _i, C.POINTER(C.c_double), _i, C.POINTER(_i), _vp, _vp]),
+    "cart_voxel_color_create": (_i, [_vp, _vp, _i, C.POINTER(_vp)]),
+    "cart_voxel_color_destroy": (None, [_vp]),
+    "cart_voxel_color_clear": (_i, [_vp]),
+    "cart_voxel_color_window": (_i, [_vp, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(_i)]),
+    "cart_voxel_color_integrate": (_i, [_vp, _vp, C.POINTER(EgoCamera), C.POINTER(C.c_double), _vp, _sz, _vp, _sz, _i, _i, _i, _vp, _sz, _vp, _vp]),
+    "cart_voxel_color_vertices": (_i, [_vp, _vp, _vp, _i, C.POINTER(C.c_int64), _vp, _vp]),
+    "cart_voxel_color_render": (_i, [_vp, C.POINTER(EgoCamera), C.POINTER(C.c_double), _vp, _sz, _i, _i, _vp, _sz, _vp, _sz, _vp, _vp]),
+    "cart_voxel_color_read": (_i, [_vp, _vp, C.POINTER(C.c_int64), _vp]),
+    "cart_voxel_color_write": (_i, [_vp, _vp, C.POINTER(C.c_int64), _vp]),
     "cart_model_track_default_params": (None, [C.POINTER(ModelTrackParams)]),
     "cart_model_track_create": (_i, [_vp, _i, _i, C.POINTER(_vp)]),
     "cart_model_track_destroy": (None, [_vp]),

@@ -1559,19 +1559,149 @@ class VoxelMap(_DeviceObject):
         return self.window()[0], used.value, (n.cpu().numpy() if n is not None else None)
 
 
-def write_ply(path, vertices, quads, origin, voxel_size):
+VOXEL_RGB_DTYPE = np.dtype([("b", "u1"), ("g", "u1"), ("r", "u1"), ("weight", "u1")])   # cart_voxel_rgb
+
+
+class VoxelColor(_DeviceObject):
+    """Colour for a VoxelMap (cart_voxel_color_* in the C ABI, spec S37 in DESIGN.md 7.19): a second volume of (b, g, r, weight) bytes under
+    the map's window, which every frame's image is averaged into where the frame's disparity saw the surface, and two read-outs of it: the
+    colours of a mesh's vertices and an image of the model behind a disparity image.  Keeps the map's shape and parameters, not the map.
+    A context manager; close() destroys the device object."""
+    _name = "voxel_color"
+
+    def __init__(self, engine, voxel_map, max_weight=_lib.VOXEL_COLOR_DEFAULT_MAX_WEIGHT):
+        if not isinstance(voxel_map, VoxelMap):
+            raise EngineError("voxel_map must be a VoxelMap")
+        self.cells_x, self.cells_y, self.cells_z, self.max_weight = voxel_map.cells_x, voxel_map.cells_y, voxel_map.cells_z, int(max_weight)
+        self._map = voxel_map
+        super().__init__(engine, voxel_map._h, self.max_weight)
+
+    def integrate(self, camera, pose, disp, image, mask=None, counts=True, raw=False, stream=None):
+        """After the map's integrate of the same frame, with its camera, pose, disp and mask (VoxelMap.integrate), plus image = uint8 [h, w]
+        (gray) or [h, w, 3] (B, G, R).  Device tensors are taken as they are (rows may be pitched), host arrays go up.  -> counts int32 [2]
+        (voxels coloured, of them without a colour before) as a numpy array, or None when counts is false; raw=True returns the device tensor
+        with no host round trip."""
+        import torch
+        cam = _camera(camera)
+        with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):   # uploads and allocations on the call's stream
+            d, im, m = _to_device(disp, torch.int16), _to_device(image, torch.uint8), _to_device(mask, torch.uint8)
+            if not isinstance(d, torch.Tensor) or d.dtype != torch.int16 or d.dim() != 2:
+                raise EngineError("disp must be an int16 [h, w] image")
+            if not isinstance(im, torch.Tensor) or im.dim() not in (2, 3):
+                raise EngineError("image must be a uint8 [h, w] or [h, w, 3] image")
+            channels = int(im.shape[2]) if im.dim() == 3 else 1
+            _check_frame_image(im, torch.uint8, "image", d, channels if im.dim() == 3 else None)
+            if m is not None:
+                _check_frame_image(m, torch.uint8, "mask", d)
+            n = torch.empty(2, dtype=torch.int32, device=d.device) if counts else None
+        sp = C.c_void_p(stream.cuda_stream) if stream is not None else _stream_ptr()
+        self._check(self._lib.cart_voxel_color_integrate(self._h, self._map._h, C.byref(cam), _pose12(pose), *_pitched(d, 1), *_pitched(im, im.dim() - 1), channels,
+                                                         int(d.shape[1]), int(d.shape[0]), *_pitched(m, 1), C.c_void_p(n.data_ptr()) if counts else None, sp),
+                    "cart_voxel_color_integrate")
+        if raw or n is None:
+            return n
+        if stream is not None:
+            stream.synchronize()
+        return n.cpu().numpy()
+
+    def colorize(self, vertices, n, origin, raw=False, stream=None):
+        """The colours of a mesh's vertices.  vertices, n, origin as VoxelMap.mesh returns them: with raw=True there the float32
+        [max_vertices, 6] tensor and the int32 [4] counts tensor (its third word is the count: no host round trip), else the
+        MESH_VERTEX_DTYPE array (n is then ignored).  -> VOXEL_RGB_DTYPE [count] whose weight field holds alpha; raw=True returns the
+        device tensor uint8 [max_vertices, 4] (b, g, r, alpha), rows beyond the count uninitialised."""
+        import torch
+        with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
+            if isinstance(vertices, torch.Tensor):
+                vt, nt = vertices, n[2:3] if n.numel() == 4 else n
+                if vt.dtype != torch.float32 or vt.dim() != 2 or vt.shape[1] != 6 or not vt.is_contiguous() or nt.dtype != torch.int32:
+                    raise EngineError("vertices must be a contiguous float32 [max_vertices, 6] tensor and n an int32 tensor")
+            else:
+                v = np.ascontiguousarray(np.asarray(vertices, MESH_VERTEX_DTYPE).reshape(-1))
+                vt = torch.from_numpy(v.view(np.float32).reshape(-1, 6).copy() if len(v) else np.zeros((1, 6), np.float32)).cuda()
+                nt = torch.tensor([len(v)], dtype=torch.int32).cuda()
+            cap = int(vt.shape[0])
+            out = torch.empty((max(cap, 0), 4), dtype=torch.uint8, device="cuda")
+        sp = C.c_void_p(stream.cuda_stream) if stream is not None else _stream_ptr()
+        o = (C.c_int64 * 3)(*[int(c) for c in origin])
+        self._check(self._lib.cart_voxel_color_vertices(self._h, C.c_void_p(vt.data_ptr()), C.c_void_p(nt.data_ptr()), cap, o, C.c_void_p(out.data_ptr()), sp),
+                    "cart_voxel_color_vertices")
+        if raw:
+            return out
+        if stream is not None:
+            stream.synchronize()
+        count = max(0, min(int(nt.cpu()[0]), cap))
+        return out[:count].cpu().numpy().view(VOXEL_RGB_DTYPE).reshape(-1)
+
+    def render(self, camera, pose, disp, alpha=True, counts=True, raw=False, stream=None):
+        """The model's colours behind a disparity image (the purpose: VoxelMap.raycast's model disparity from the same camera and pose).
+        disp int16 [h, w].  -> (image uint8 [h, w, 3] B, G, R, alpha uint8 [h, w], counts int32 [1] = pixels with alpha > 0) as numpy arrays,
+        None for an output that was not asked for; raw=True returns the device tensors."""
+        import torch
+        cam = _camera(camera)
+        with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
+            d = _to_device(disp, torch.int16)
+            if not isinstance(d, torch.Tensor) or d.dtype != torch.int16 or d.dim() != 2:
+                raise EngineError("disp must be an int16 [h, w] image")
+            h, w = int(d.shape[0]), int(d.shape[1])
+            im = torch.empty((h, w, 3), dtype=torch.uint8, device=d.device)
+            al = torch.empty((h, w), dtype=torch.uint8, device=d.device) if alpha else None
+            n = torch.empty(1, dtype=torch.int32, device=d.device) if counts else None
+        sp = C.c_void_p(stream.cuda_stream) if stream is not None else _stream_ptr()
+        self._check(self._lib.cart_voxel_color_render(self._h, C.byref(cam), _pose12(pose), *_pitched(d, 1), w, h, C.c_void_p(im.data_ptr()), 3 * w,
+                                                      *([C.c_void_p(al.data_ptr()), w] if alpha else [None, 0]), C.c_void_p(n.data_ptr()) if counts else None, sp),
+                    "cart_voxel_color_render")
+        out = (im, al, n)
+        if raw:
+            return out
+        if stream is not None:
+            stream.synchronize()
+        return tuple(t.cpu().numpy() if t is not None else None for t in out)
+
+    def window(self):
+        """-> ((ox, oy, oz), (cells_x, cells_y, cells_z), valid): the colour volume's own window, the map's as of the last integrate."""
+        o, n, valid = (C.c_int64 * 3)(), (C.c_int32 * 3)(), C.c_int(0)
+        self._check(self._lib.cart_voxel_color_window(self._h, o, n, C.byref(valid)), "cart_voxel_color_window")
+        return tuple(o), tuple(n), bool(valid.value)
+
+    def read(self):
+        """-> (voxels VOXEL_RGB_DTYPE [cells_z, cells_y, cells_x] in window order, (ox, oy, oz)); synchronises."""
+        voxels = np.empty((self.cells_z, self.cells_y, self.cells_x), VOXEL_RGB_DTYPE)
+        o = (C.c_int64 * 3)()
+        self._check(self._lib.cart_voxel_color_read(self._h, C.c_void_p(voxels.ctypes.data), o, _stream_ptr()), "cart_voxel_color_read")
+        return voxels, tuple(o)
+
+    def write(self, voxels, origin):
+        """The counterpart of read(), as VoxelMap.write; synchronises."""
+        v = np.ascontiguousarray(voxels, VOXEL_RGB_DTYPE)
+        if v.shape != (self.cells_z, self.cells_y, self.cells_x):
+            raise EngineError("voxels must be a VOXEL_RGB_DTYPE array of [cells_z, cells_y, cells_x]")
+        o = (C.c_int64 * 3)(*[int(c) for c in origin])
+        self._check(self._lib.cart_voxel_color_write(self._h, C.c_void_p(v.ctypes.data), o, _stream_ptr()), "cart_voxel_color_write")
+
+    def clear(self):
+        self._check(self._lib.cart_voxel_color_clear(self._h), "cart_voxel_color_clear")
+
+
+def write_ply(path, vertices, quads, origin, voxel_size, colors=None):
     """A mesh of VoxelMap.mesh as a binary little-endian PLY file with quad faces and normals.  origin = the window origin (ox, oy, oz) in
-    voxels: the positions are moved to the world frame, o_a voxel_size + p_a in fp64, before the conversion to float."""
+    voxels: the positions are moved to the world frame, o_a voxel_size + p_a in fp64, before the conversion to float.  colors = the
+    VOXEL_RGB_DTYPE array of VoxelColor.colorize, one record per vertex: the vertex element then carries uchar red, green, blue, alpha."""
     v = np.asarray(vertices, MESH_VERTEX_DTYPE).reshape(-1)
     q = np.asarray(quads, MESH_QUAD_DTYPE).reshape(-1)
     shift = np.array([int(c) for c in origin], np.float64) * np.float64(voxel_size)
-    out = np.empty(len(v), np.dtype([("p", "<f4", 3), ("n", "<f4", 3)]))
+    out = np.empty(len(v), np.dtype([("p", "<f4", 3), ("n", "<f4", 3)] + ([("c", "u1", 4)] if colors is not None else [])))
     out["p"] = (shift + v["position"].astype(np.float64)).astype(np.float32)
     out["n"] = v["normal"]
+    if colors is not None:
+        c = np.asarray(colors, VOXEL_RGB_DTYPE).reshape(-1)
+        if len(c) != len(v):
+            raise EngineError("colors must hold one record per vertex")
+        out["c"] = np.stack([c["r"], c["g"], c["b"], c["weight"]], axis=1)
     faces = np.empty(len(q), np.dtype([("k", "u1"), ("v", "<i4", 4)]))
     faces["k"], faces["v"] = 4, q["v"]
     header = "ply\nformat binary_little_endian 1.0\ncomment cartslam voxel_map surface nets\nelement vertex %d\n" % len(v) + \
              "".join("property float %s\n" % c for c in ("x", "y", "z", "nx", "ny", "nz")) + \
+             ("".join("property uchar %s\n" % c for c in ("red", "green", "blue", "alpha")) if colors is not None else "") + \
              "element face %d\nproperty list uchar int vertex_indices\nend_header\n" % len(q)
     with open(path, "wb") as f:
         f.write(header.encode("ascii"))

@@ -696,6 +696,51 @@ struct ModelTrackArgs {                 // the sums, the row partials and the po
     cart_model_track_result *result;
 };
 void launch_model_track(const ModelTrackArgs &a, hipStream_t s);   // the 2 (iterations + 1) launches of one call
+// ---- the colour companion of the TSDF volume (voxelcolor_kernels.hip) ----
+// The colour volume is a VoxelGrid of its own: words b | g << 8 | r << 16 | weight << 24, the empty word 0, S33's toroidal storage.
+constexpr int kColorDepth = 16;         // z slices per workgroup of the colour integrate kernel: a multiple of kVoxelSlices (nz is a multiple of 8)
+constexpr int kColorCounters = 8;       // int32 words of the object's counter block, read as four uint64: integrate {coloured | fresh << 32, ticket},
+                                        // render {pixels with alpha > 0 | ticket << 32, unused}; all zero between calls
+struct ColorIntegrateArgs {
+    VoxelGrid grid;                                     // the colour volume under the map's current origin
+    cart_ego_camera cam;
+    cart_voxel_map_params p;                            // the map's own: the gates are S33's
+    double pose[12];
+    const int16_t *disp; size_t disp_step;
+    const uint8_t *mask; size_t mask_step;              // NULL = no mask
+    const uint8_t *image; size_t image_step;
+    int channels;                                       // 1 (gray) or 3 (B, G, R)
+    int max_weight;
+    int32_t *counts;                                    // [2] or NULL
+    int32_t *counters;
+    int w, h;
+};
+struct ColorRenderArgs {
+    VoxelGrid grid;
+    cart_ego_camera cam;
+    double voxel_size;
+    double pose[12];
+    const int16_t *disp; size_t disp_step;
+    uint8_t *image; size_t image_step;                  // 8UC3
+    uint8_t *alpha; size_t alpha_step;                  // NULL = not asked for
+    int32_t *counts;                                    // [1] or NULL
+    int32_t *counters;
+    int w, h;
+    int empty;                                          // the colour object has no window: every sample is (0, 0, 0, 0)
+};
+struct ColorVerticesArgs {
+    VoxelGrid grid;
+    double voxel_size;
+    double mx, my, mz;                                  // the mesh origin (|o| <= 2^27: exact)
+    const cart_mesh_vertex *vertices;
+    const int32_t *n_vertices;                          // DEVICE
+    int max_vertices;
+    uint32_t *colors;                                   // [max_vertices] cart_voxel_rgb words
+    int empty;
+};
+void launch_color_integrate(const ColorIntegrateArgs &a, hipStream_t s);
+void launch_color_render(const ColorRenderArgs &a, hipStream_t s);
+void launch_color_vertices(const ColorVerticesArgs &a, hipStream_t s);
 void launch_narrow_copy(const void *src, void *dst, size_t bytes, int blocks, hipStream_t s);
 int kernel_count();
 

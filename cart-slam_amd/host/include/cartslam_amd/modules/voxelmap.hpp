@@ -10,6 +10,10 @@
 // With "mesh" (spec DESIGN.md S36) every "mesh_interval"-th frame the module sees also extracts the window's surface after the integrate or
 // rebuild (cart_voxel_map_mesh) and downloads the written records, published as "voxel_mesh".  The written counts size the download, so
 // such a frame waits for the device twice; every other frame, and every frame without "mesh", once as before.
+// With "color" (spec DESIGN.md S37) the module keeps a cart_voxel_color beside the map and colour-integrates the frame's reference image
+// (8UC1 or 8UC3) right after the geometry integrate; on a frame that rebuilt the volume nothing is colour-integrated and the stored colours
+// stay (the keyframe store holds no images).  With "raycast" it also publishes "image_model" and "image_model_alpha", the model's colours
+// behind "disparity_model"; with "mesh", "voxel_mesh_colors" beside the unchanged "voxel_mesh".  Without "color" nothing changes.
 #pragma once
 #include <array>
 #include <mutex>
@@ -24,6 +28,10 @@
 #define CARTSLAM_KEY_DISPARITY_MODEL_STATUS "disparity_model_status"      // CV_8UC1: CART_VOXEL_RAY_*
 #define CARTSLAM_KEY_DISPARITY_MODEL_COUNTS "disparity_model_counts"      // VoxelRayCounts
 #define CARTSLAM_KEY_VOXEL_MESH "voxel_mesh"                              // VoxelMesh, with "mesh" only
+#define CARTSLAM_KEY_VOXEL_COLOR "voxel_color"                            // VoxelColorFrame, with "color" only
+#define CARTSLAM_KEY_IMAGE_MODEL "image_model"                            // CV_8UC3 (B, G, R), with "color" and "raycast"
+#define CARTSLAM_KEY_IMAGE_MODEL_ALPHA "image_model_alpha"                // CV_8UC1: min(sum of the eight weights, 255); 0 = no colour
+#define CARTSLAM_KEY_VOXEL_MESH_COLORS "voxel_mesh_colors"                // VoxelMeshColors, with "color" and "mesh"
 #define CARTSLAM_KEY_MODEL_POSE "model_pose"                              // EgoMotion, with "track" only: the tracked pose and the relative pose between tracked poses
 #define CARTSLAM_KEY_MODEL_TRACK_RESULT "model_track_result"              // cart_model_track_result as the device wrote it, with "track" only
 
@@ -46,6 +54,17 @@ struct VoxelMesh {                      // S36; `extracted` is false on the fram
     std::vector<cart_mesh_vertex> vertices;   // the written ones; positions relative to the window origin
     std::vector<cart_mesh_quad> quads;
 };
+struct VoxelColorFrame {                // S37
+    bool integrated = false;            // false on a frame that rebuilt the volume: nothing was colour-integrated
+    int32_t counts[2] = {0, 0};         // of this frame's colour integrate: voxels coloured, of them without a colour before
+    int32_t rendered = 0;               // pixels of "image_model" with alpha > 0 (0 without "raycast")
+    int64_t origin[3] = {0, 0, 0};      // the colour volume's window
+    std::vector<cart_voxel_rgb> voxels; // the colour voxels in window order; filled only when CARTSLAM_VOXEL_MAP_SNAPSHOT is set
+};
+struct VoxelMeshColors {                // S37: one record per written vertex of the frame's "voxel_mesh", the weight byte holding alpha
+    bool extracted = false;
+    std::vector<cart_voxel_rgb> colors;
+};
 struct VoxelRayCounts {
     int32_t rays[3] = {0, 0, 0};        // CART_VOXEL_RAY_NONE, _HIT, _INSIDE
 };
@@ -65,6 +84,8 @@ struct VoxelMapOptions : CameraOptions {   // the factory fills the camera from 
     int storeCapacity = 256;                  // keyframes the store holds (a ring: the oldest leaves)
     bool mesh = false;                        // S36: extract the window's surface every meshInterval-th frame
     int meshInterval = 10, meshMaxVertices = 1 << 20, meshMaxQuads = 1 << 20, meshMinWeight = 0;   // 0 = minWeight
+    bool color = false;                       // S37: a colour volume beside the map, fed with the frame's reference image
+    int colorMaxWeight = CART_VOXEL_COLOR_DEFAULT_MAX_WEIGHT;
     double residualGate = 0.9, damping = 0.01;   // cart_model_track_default_params
     int iterations = 4, stride = 1, minInliers = 1024;
 };
@@ -84,6 +105,7 @@ class VoxelMapModule : public SyncWrapperSystemModule {
     cart_voxel_map *map = nullptr;
     cart_model_track *tracker = nullptr;   // with "track": made with the map
     cart_plane_store *store = nullptr;     // with "rebuild": made with the map
+    cart_voxel_color *color = nullptr;     // with "color": made with the map
     std::vector<uint64_t> nodeFrame;       // with "rebuild": the frame id of every pose-graph node
     image_t zeroPlane;                     // with "rebuild" and without "use_motion": the stored u8 plane, zeroed once
     bool haveTracked = false;         // with "track": `tracked` holds the previous frame's tracked pose

@@ -307,6 +307,8 @@ void applyModuleConfig(const Value &modulesConfig, std::shared_ptr<System> syste
             o.meshMaxVertices = get(moduleConfig, "mesh_max_vertices", o.meshMaxVertices);
             o.meshMaxQuads = get(moduleConfig, "mesh_max_quads", o.meshMaxQuads);
             o.meshMinWeight = get(moduleConfig, "mesh_min_weight", o.meshMinWeight);
+            o.color = get(moduleConfig, "color", o.color);   // S37: a colour volume beside the map; "image_model" with "raycast", "voxel_mesh_colors" with "mesh"
+            o.colorMaxWeight = get(moduleConfig, "color_max_weight", o.colorMaxWeight);
             o.residualGate = get(moduleConfig, "residual_gate", o.residualGate);
             o.damping = get(moduleConfig, "damping", o.damping);
             o.iterations = get(moduleConfig, "iterations", o.iterations);

@@ -201,6 +201,30 @@ int main(int argc, char **argv) {
                         append(o, mesh->quads.data(), mesh->quads.size() * sizeof(cart_mesh_quad));
                     }
                 }
+                if (run->hasData(CARTSLAM_KEY_VOXEL_COLOR)) {   // voxel_map with "color": int32 integrated, colour counts [2], rendered, width, height; the model image (B, G, R) and its alpha (u8)
+                    auto vc = run->getData<cart::VoxelColorFrame>(CARTSLAM_KEY_VOXEL_COLOR);
+                    auto image = run->getData<cart::image_t>(CARTSLAM_KEY_IMAGE_MODEL);
+                    const int32_t head[6] = {vc->integrated ? 1 : 0, vc->counts[0], vc->counts[1], vc->rendered, image->cols, image->rows};   // 0 x 0 without "raycast"
+                    std::ofstream o = writeBin(dump, id, CARTSLAM_KEY_VOXEL_COLOR, head, sizeof(head));
+                    if (!image->empty()) {
+                        for (const char *k : {CARTSLAM_KEY_IMAGE_MODEL, CARTSLAM_KEY_IMAGE_MODEL_ALPHA}) {
+                            const auto bytes = run->getData<cart::image_t>(k)->downloadTight();
+                            append(o, bytes.data(), bytes.size());
+                        }
+                    }
+                    if (!vc->voxels.empty()) {   // with CARTSLAM_VOXEL_MAP_SNAPSHOT: int64 origin [3], then the 4-byte colour voxels in window order
+                        std::ofstream v = writeBin(dump, id, CARTSLAM_KEY_VOXEL_COLOR "_voxels", vc->origin, sizeof(vc->origin));
+                        append(v, vc->voxels.data(), vc->voxels.size() * sizeof(cart_voxel_rgb));
+                    }
+                }
+                if (run->hasData(CARTSLAM_KEY_VOXEL_MESH_COLORS)) {   // with "color" and "mesh", on the frames that extracted: int32 count, then one 4-byte (b, g, r, alpha) per written vertex
+                    auto colors = run->getData<cart::VoxelMeshColors>(CARTSLAM_KEY_VOXEL_MESH_COLORS);
+                    if (colors->extracted) {
+                        const int32_t count = (int32_t)colors->colors.size();
+                        std::ofstream o = writeBin(dump, id, CARTSLAM_KEY_VOXEL_MESH_COLORS, &count, sizeof(count));
+                        append(o, colors->colors.data(), colors->colors.size() * sizeof(cart_voxel_rgb));
+                    }
+                }
                 if (run->hasData(CARTSLAM_KEY_MODEL_POSE)) {   // voxel_map with "track": the 136-byte cart_model_track_result, then the tracked pose as 12 doubles
                     auto record = run->getData<cart_model_track_result>(CARTSLAM_KEY_MODEL_TRACK_RESULT);
                     auto tracked = run->getData<cart::EgoMotion>(CARTSLAM_KEY_MODEL_POSE);

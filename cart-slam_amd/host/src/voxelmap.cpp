@@ -1,4 +1,4 @@
-// voxelmap.cpp -- VoxelMapModule (cartslam_amd/modules/voxelmap.hpp): the rolling TSDF voxel map with model raycast, spec DESIGN.md S33; its rebuild from stored keyframes, S35; its surface mesh, S36.
+// voxelmap.cpp -- VoxelMapModule (cartslam_amd/modules/voxelmap.hpp): the rolling TSDF voxel map with model raycast, spec DESIGN.md S33; its rebuild from stored keyframes, S35; its surface mesh, S36; its colour companion, S37.
 #include "cartslam_amd/modules/voxelmap.hpp"
 
 #include <algorithm>
@@ -31,7 +31,8 @@ constexpr size_t kCountsOffset = sizeof(cart_model_track_result);   // of the fi
 constexpr size_t kRebuildCountsOffset = kCountsOffset + 8 * sizeof(int32_t);   // of the rebuild's two int64 counts, 8-byte aligned
 static_assert(kRebuildCountsOffset % 8 == 0, "the rebuild's counts are int64");
 constexpr size_t kMeshCountsOffset = kRebuildCountsOffset + 2 * sizeof(int64_t);   // of the mesh's four counts
-constexpr size_t kScratchBytes = kMeshCountsOffset + 4 * sizeof(int32_t);
+constexpr size_t kColorCountsOffset = kMeshCountsOffset + 4 * sizeof(int32_t);   // of the colour integrate's two counts and the render's one
+constexpr size_t kScratchBytes = kColorCountsOffset + 4 * sizeof(int32_t);
 }  // namespace
 
 VoxelMapModule::VoxelMapModule(const VoxelMapOptions &options)
@@ -66,6 +67,11 @@ VoxelMapModule::VoxelMapModule(const VoxelMapOptions &options)
         if (options.meshMaxQuads < 1 || options.meshMaxQuads > 1 << 26) throw std::invalid_argument("mesh_max_quads must be in [1, 2^26]");
         if (options.meshMinWeight < 0 || options.meshMinWeight > 65535) throw std::invalid_argument("mesh_min_weight must be 0 (min_weight) or in [1, 65535]");
     }
+    if (options.color) {
+        cart_voxel_color *none = nullptr;
+        (void)cart_voxel_color_create(nullptr, nullptr, options.colorMaxWeight, &none);
+        if (std::strcmp(cart_last_error(nullptr), "bad arguments") != 0) throw std::invalid_argument(std::string("color_max_weight: ") + cart_last_error(nullptr));
+    }
     this->requiresData.push_back(module_dependency_t(options.disparityKey));
     this->requiresData.push_back(module_dependency_t(options.poseKey));
     if (options.useMotion) this->requiresData.push_back(module_dependency_t(CARTSLAM_KEY_MOTION));
@@ -83,10 +89,17 @@ VoxelMapModule::VoxelMapModule(const VoxelMapOptions &options)
         this->providesData.push_back(CARTSLAM_KEY_MODEL_TRACK_RESULT);
     }
     if (options.mesh) this->providesData.push_back(CARTSLAM_KEY_VOXEL_MESH);
+    if (options.color) {
+        this->providesData.push_back(CARTSLAM_KEY_VOXEL_COLOR);
+        this->providesData.push_back(CARTSLAM_KEY_IMAGE_MODEL);
+        this->providesData.push_back(CARTSLAM_KEY_IMAGE_MODEL_ALPHA);
+        if (options.mesh) this->providesData.push_back(CARTSLAM_KEY_VOXEL_MESH_COLORS);
+    }
 }
 
 VoxelMapModule::~VoxelMapModule() {
     cart_model_track_destroy(tracker);
+    cart_voxel_color_destroy(color);
     cart_voxel_map_destroy(map);
     cart_plane_store_destroy(store);
 }
@@ -123,10 +136,13 @@ system_data_t VoxelMapModule::runInternal(System &, SystemRunData &data) {
                 hipCheck(hipDeviceSynchronize(), "hipDeviceSynchronize after zeroing the store's plane");
             }
         }
+        if (options.color)
+            makeOnPostEngine(cols, rows, [&](cart_engine *e) { return cart_voxel_color_create(e, map, options.colorMaxWeight, &color) ? "cart_voxel_color_create" : nullptr; });
         scratch.create();
         scratch.reserve(kScratchBytes, kScratchBytes);
-        if (options.mesh)
-            meshBuffers.reserve((size_t)options.meshMaxVertices * sizeof(cart_mesh_vertex) + (size_t)options.meshMaxQuads * sizeof(cart_mesh_quad), 0);
+        if (options.mesh)   // the vertices, the quads and, with "color", one 4-byte colour per vertex
+            meshBuffers.reserve((size_t)options.meshMaxVertices * (sizeof(cart_mesh_vertex) + (options.color ? sizeof(cart_voxel_rgb) : 0)) +
+                                    (size_t)options.meshMaxQuads * sizeof(cart_mesh_quad), 0);
     }
     const cart_ego_camera cam = cameraOf(options);
     hipStream_t s = scratch.stream();
@@ -194,17 +210,46 @@ system_data_t VoxelMapModule::runInternal(System &, SystemRunData &data) {
     if (options.raycast &&
         cart_voxel_map_raycast(map, &cam, pose, cols, rows, model->ptr<int16_t>(), model->step, nullptr, 0, status->ptr<uint8_t>(), status->step, counts + 2, s) != 0)
         failAbi("cart_voxel_map_raycast");
+    std::shared_ptr<VoxelColorFrame> colour;
+    auto imageModel = std::make_shared<image_t>(), imageAlpha = std::make_shared<image_t>();
+    if (options.color) {   // S37: the frame's image into the colour volume right after the geometry, then the model's colours behind the model disparity
+        colour = std::make_shared<VoxelColorFrame>();
+        int32_t *colorCounts = reinterpret_cast<int32_t *>(scratch.dev<char>() + kColorCountsOffset);
+        if (!nodes) {   // a rebuild frame colour-integrates nothing and the stored colours stay: the store holds no images
+            const image_t image = getReferenceImage(data.dataElement);
+            if ((image.type() != CV_8UC3 && image.type() != CV_8UC1) || image.rows != rows || image.cols != cols)
+                throw std::runtime_error("VoxelMapModule: color needs a CV_8UC1 or CV_8UC3 reference image of the disparity's size");
+            if (cart_voxel_color_integrate(color, map, &cam, pose, disparity->ptr<int16_t>(), disparity->step, image.ptr<uint8_t>(), image.step,
+                                           image.type() == CV_8UC3 ? 3 : 1, cols, rows, mask ? mask->ptr<uint8_t>() : nullptr, mask ? mask->step : 0, colorCounts, s) != 0)
+                failAbi("cart_voxel_color_integrate");
+            colour->integrated = true;
+        }
+        if (options.raycast) {
+            imageModel = std::make_shared<image_t>(rows, cols, CV_8UC3);
+            imageAlpha = std::make_shared<image_t>(rows, cols, CV_8UC1);
+            if (cart_voxel_color_render(color, &cam, pose, model->ptr<int16_t>(), model->step, cols, rows, imageModel->ptr<uint8_t>(), imageModel->step,
+                                        imageAlpha->ptr<uint8_t>(), imageAlpha->step, colorCounts + 2, s) != 0)
+                failAbi("cart_voxel_color_render");
+        }
+        hipCheck(hipMemcpyAsync(scratch.host<char>() + kColorCountsOffset, colorCounts, 3 * sizeof(int32_t), hipMemcpyDeviceToHost, s), "hipMemcpyAsync of the colour counts");
+    }
     int32_t *hostCounts = reinterpret_cast<int32_t *>(scratch.host<char>() + kCountsOffset);
     hipCheck(hipMemcpyAsync(hostCounts, counts, (options.raycast ? 5 : 2) * sizeof(int32_t), hipMemcpyDeviceToHost, s), "hipMemcpyAsync of the voxel map counts");
     std::shared_ptr<VoxelMesh> mesh;
+    std::shared_ptr<VoxelMeshColors> meshColors;
     if (options.mesh) {
         mesh = std::make_shared<VoxelMesh>();
+        if (options.color) meshColors = std::make_shared<VoxelMeshColors>();
         if (++meshFrames % options.meshInterval == 0) {   // S36: the surface of the window as this frame left it
             cart_mesh_vertex *vertices = meshBuffers.dev<cart_mesh_vertex>();
             cart_mesh_quad *quads = reinterpret_cast<cart_mesh_quad *>(meshBuffers.dev<char>() + (size_t)options.meshMaxVertices * sizeof(cart_mesh_vertex));
             int32_t *meshCounts = reinterpret_cast<int32_t *>(scratch.dev<char>() + kMeshCountsOffset);
             if (cart_voxel_map_mesh(map, options.meshMinWeight, vertices, options.meshMaxVertices, quads, options.meshMaxQuads, meshCounts, mesh->origin, s) != 0)
                 failAbi("cart_voxel_map_mesh");
+            cart_voxel_rgb *colors = reinterpret_cast<cart_voxel_rgb *>(reinterpret_cast<char *>(quads) + (size_t)options.meshMaxQuads * sizeof(cart_mesh_quad));
+            if (options.color &&   // the written count is read on the device: no round trip between the two calls
+                cart_voxel_color_vertices(color, vertices, meshCounts + 2, options.meshMaxVertices, mesh->origin, colors, s) != 0)
+                failAbi("cart_voxel_color_vertices");
             hipCheck(hipMemcpyAsync(scratch.host<char>() + kMeshCountsOffset, meshCounts, sizeof(mesh->counts), hipMemcpyDeviceToHost, s), "hipMemcpyAsync of the mesh counts");
             scratch.wait();   // the second synchronisation of such a frame: the written counts size the download
             std::memcpy(mesh->counts, scratch.host<char>() + kMeshCountsOffset, sizeof(mesh->counts));
@@ -214,6 +259,12 @@ system_data_t VoxelMapModule::runInternal(System &, SystemRunData &data) {
                 hipCheck(hipMemcpyAsync(mesh->vertices.data(), vertices, mesh->vertices.size() * sizeof(cart_mesh_vertex), hipMemcpyDeviceToHost, s), "hipMemcpyAsync of the mesh vertices");
             if (mesh->counts[3])
                 hipCheck(hipMemcpyAsync(mesh->quads.data(), quads, mesh->quads.size() * sizeof(cart_mesh_quad), hipMemcpyDeviceToHost, s), "hipMemcpyAsync of the mesh quads");
+            if (options.color) {
+                meshColors->colors.resize((size_t)mesh->counts[2]);
+                if (mesh->counts[2])
+                    hipCheck(hipMemcpyAsync(meshColors->colors.data(), colors, meshColors->colors.size() * sizeof(cart_voxel_rgb), hipMemcpyDeviceToHost, s), "hipMemcpyAsync of the mesh colours");
+                meshColors->extracted = true;
+            }
             mesh->voxelSize = options.voxelSize;
             mesh->extracted = true;
         }
@@ -225,7 +276,16 @@ system_data_t VoxelMapModule::runInternal(System &, SystemRunData &data) {
         result->voxels.resize((size_t)options.cellsX * options.cellsY * options.cellsZ);
         if (cart_voxel_map_read(map, result->voxels.data(), result->origin, s) != 0) failAbi("cart_voxel_map_read");
     }
+    if (options.color && snapshot) {   // synchronises
+        colour->voxels.resize((size_t)options.cellsX * options.cellsY * options.cellsZ);
+        if (cart_voxel_color_read(color, colour->voxels.data(), colour->origin, s) != 0) failAbi("cart_voxel_color_read");
+    }
     scratch.wait();   // the frame's only blocking synchronisation
+    if (options.color) {
+        const int32_t *cc = reinterpret_cast<const int32_t *>(scratch.host<char>() + kColorCountsOffset);
+        if (colour->integrated) std::memcpy(colour->counts, cc, sizeof(colour->counts));
+        if (options.raycast) colour->rendered = cc[2];
+    }
     std::memcpy(result->counts, hostCounts, sizeof(result->counts));
     if (result->rebuilt > 0) {   // the integrate's two words were not written on this frame: the rebuild's counts, cut to int32
         std::memcpy(result->rebuildCounts, scratch.host<char>() + kRebuildCountsOffset, sizeof(result->rebuildCounts));
@@ -235,6 +295,12 @@ system_data_t VoxelMapModule::runInternal(System &, SystemRunData &data) {
     system_data_t out = MODULE_RETURN_ALL(MODULE_PAIR(CARTSLAM_KEY_VOXEL_MAP, result), MODULE_PAIR(CARTSLAM_KEY_DISPARITY_MODEL, model),
                                           MODULE_PAIR(CARTSLAM_KEY_DISPARITY_MODEL_STATUS, status), MODULE_PAIR(CARTSLAM_KEY_DISPARITY_MODEL_COUNTS, rays));
     if (options.mesh) out.push_back(MODULE_PAIR(CARTSLAM_KEY_VOXEL_MESH, mesh));
+    if (options.color) {
+        out.push_back(MODULE_PAIR(CARTSLAM_KEY_VOXEL_COLOR, colour));
+        out.push_back(MODULE_PAIR(CARTSLAM_KEY_IMAGE_MODEL, imageModel));
+        out.push_back(MODULE_PAIR(CARTSLAM_KEY_IMAGE_MODEL_ALPHA, imageAlpha));
+        if (options.mesh) out.push_back(MODULE_PAIR(CARTSLAM_KEY_VOXEL_MESH_COLORS, meshColors));
+    }
     if (options.track) {
         out.push_back(MODULE_PAIR(CARTSLAM_KEY_MODEL_POSE, modelPose));
         out.push_back(MODULE_PAIR(CARTSLAM_KEY_MODEL_TRACK_RESULT, trackResult));

@@ -1223,7 +1223,7 @@ int cart_voxel_map_rebuild(cart_voxel_map *map, cart_plane_store *store, const c
  *   when it is outside: (p2 - p0) x (p3 - p1) then points to free space.  Quads are ordered by ascending (cell index of (i, j, k), axis).
  *   Capacity: the first max_vertices vertices and the first max_quads quads in these orders are written and nothing beyond them is touched;
  *   after a truncation a quad may name a vertex that was not written: a consumer takes the mesh iff found == written for both.
- * Limits: no colour, no decimation; surface nets round sharp edges and can be non-manifold where two surfaces meet within a cell; a mesh
+ * Limits: no colour in the records themselves (cart_voxel_color_vertices, S37 below, colours them from a colour volume), no decimation; surface nets round sharp edges and can be non-manifold where two surfaces meet within a cell; a mesh
  * covers the current window only. */
 typedef struct cart_mesh_vertex {
     float position[3];                        /* metres, relative to the window origin */
@@ -1246,6 +1246,81 @@ int cart_voxel_map_mesh(cart_voxel_map *map, int min_weight, cart_mesh_vertex *v
  * before any device call: origin3, the object, host_voxels.  Synchronises `stream`, as _read does.  Afterwards the map is valid at that
  * origin; cart_voxel_map_integrate, _raycast, _read, _mesh and cart_model_track_refine continue on it as after any integrate. */
 int cart_voxel_map_write(cart_voxel_map *map, const cart_voxel *host_voxels, const int64_t *origin3, void *stream);
+
+/* ---- Colour for the TSDF volume (spec S37) -----------------------------------------------------------------------
+ * An extension.  cart_voxel_color is a companion of one cart_voxel_map; it does not extend that map's voxel: the 4-byte cart_voxel,
+ * cart_voxel_map_read / _write and every S33 - S36 kernel stay as they are.  The colour object copies cells_x/y/z and the map's
+ * cart_voxel_map_params at create and owns a second volume of 4-byte words cart_voxel_rgb, stored as b | g << 8 | r << 16 | weight << 24
+ * (the empty word is 0) in S33's toroidal storage (global voxel g at g mod N per axis, x fastest), its own window origin (int64) and
+ * valid flag, and one parameter: max_weight (1..255, default 64, build-owned and untuned).  S33's arithmetic rules: fp64 with + - * /
+ * floor only, every expression in the written order, integers after the projection, no atomic on the volume.  Restated in
+ * tests/np_voxelcolor.py, byte for byte.
+ *   Window: none of its own.  cart_voxel_color_integrate takes the MAP's current origin, read under the map's lock (lock order: map,
+ *   then colour).  If the colour object has no window, or the origin moved by >= N on any axis, every colour voxel is emptied; otherwise
+ *   the slabs that entered are emptied by S33's move rule.  Voxels that stay keep their colour: they are anchored in the world.  After
+ *   cart_voxel_map_rebuild, _write or a jump the same rule applies at the next colour integrate.
+ *   Integrate: called after cart_voxel_map_integrate of the same frame with the same camera, pose, disparity and mask, plus the frame's
+ *   image: width x height of channels = 1 (gray) or 3 (B, G, R) bytes per pixel.  For every voxel of the window: gates 1 - 5 of S33 to the
+ *   letter with the map's parameters, then f < 1.0 on the unclamped f of gate 5 (the voxels S33 counts in counts[1]: -tr <= sdf < tr).  A
+ *   voxel that passes takes obs_c = the byte of channel c at pixel (x, y) (b = g = r for one channel) and, with its stored (c, w) in
+ *   integers, c' = (2 (w c + obs_c) + (w + 1)) / (2 (w + 1)) (plain integer division of non-negative terms: rounds half up), w' = min(w +
+ *   1, max_weight).  A voxel that fails a gate is neither read nor written; nothing of the TSDF volume is read.  counts = {voxels
+ *   coloured, of them with w = 0 before}.
+ *   Hand-worked (S33's case: identity pose, fx = fy = 256, cx = 8, cy = 4, baseline 0.5, disparity 64 px, voxel_size 0.25): voxel (0, 0,
+ *   7) projects to pixel (25, 21), f = 0.125 / 0.265625 < 1; gray 200 leaves (200, 200, 200, 1); a second frame with 101 there gives
+ *   604 / 4 = 151, weight 2; a third with 0 gives 607 / 6 = 101, weight 3.
+ *   Sample rule, for a world point p in metres: per axis a = p / voxel_size - 0.5, i0 = floor(a); the eight corners i0 + {0,1}^3 must all
+ *   lie in the colour window (compared as doubles: a NaN fails).  W = sum w_k and S_c = sum w_k c_k over the eight corners, in integers.
+ *   Without a window, with a corner outside or with W = 0 the sample is (0, 0, 0, 0); otherwise c = (2 S_c + W) / (2 W) per channel and
+ *   alpha = min(W, 255).  Hand-worked: corners (b = 10, w = 1) and (b = 20, w = 3) and six empty ones give W = 4, b = (140 + 4) / 8 = 18.
+ *   Vertex colours: for vertex k < min(*n_vertices, max_vertices) of a cart_mesh_vertex array with its mesh origin o: a = (double)
+ *   position_a / voxel_size - 0.5 (the fp32 record, as S36 wrote it), absolute corner index = o_a + floor(a) (a double sum), then the
+ *   sample rule.  The rule is defined on the record, not on the cell that produced it: a position that fp32 rounding put on a cell face
+ *   takes the neighbouring cell.  colors[k] for k beyond that count is not touched.
+ *   Render: for pixel (x, y) of a disparity image in the format of `disparity` (the purpose is cart_voxel_map_raycast's model disparity):
+ *   s != -32768 and s >= 1, d = s / 16.0, Z = (fx baseline) / d, p = the pose applied to (((x - cx) Z) / fx, ((y - cy) Z) / fy, Z) in S33's
+ *   carry order, then the sample rule: B, G, R into an 8UC3 image and alpha into an optional u8 image; every other pixel gets zeros.
+ *   counts = {pixels with alpha > 0}.
+ * Memory: 4 bytes per voxel, as much as the map itself.  Limits: cart_voxel_map_rebuild restores no colour (the store keeps no images);
+ * the colour pass is a launch of its own; the read-outs are weight-weighted integer means of eight voxels, not trilinear; no exposure
+ * compensation. */
+typedef struct cart_voxel_rgb { uint8_t b, g, r, weight; } cart_voxel_rgb;   /* 4 bytes */
+typedef struct cart_voxel_color cart_voxel_color;
+#define CART_VOXEL_COLOR_DEFAULT_MAX_WEIGHT 64
+/* Extension.  max_weight in 1..255.  The object keeps the map's shape and parameters and the device it was created on, not the map: it
+ * may outlive it.  Checked in this order: max_weight, engine and out ("bad arguments"), map, the map's device. */
+int cart_voxel_color_create(cart_engine *engine, cart_voxel_map *map, int max_weight, cart_voxel_color **out);
+void cart_voxel_color_destroy(cart_voxel_color *color);
+/* Host only: the next integrate empties the colour volume on its stream; until then the read-outs give zeros. */
+int cart_voxel_color_clear(cart_voxel_color *color);
+/* Host getter, as cart_voxel_map_window: origin3 = zeros and *valid = 0 without a window. */
+int cart_voxel_color_window(cart_voxel_color *color, int64_t *origin3, int32_t *shape3, int *valid);
+/* Extension.  disp, image and mask are DEVICE images with steps in bytes (disp and its step 2-byte aligned; image_step >= channels width);
+ * mask may be NULL; counts = DEVICE int32 [2] (4-byte aligned) or NULL.  Checked in this order, all before any device call: channels,
+ * camera, pose, width and height, the colour object, the map, their devices and shapes, then pointers, alignment, steps and overlaps
+ * (counts may overlap no input); the map's window under its lock.  A refused call launches nothing and changes nothing.  One or more
+ * emptying launches and one integrate launch; no host synchronisation. */
+int cart_voxel_color_integrate(cart_voxel_color *color, cart_voxel_map *map, const cart_ego_camera *camera, const double *pose,
+                               const int16_t *disp, size_t disp_step, const uint8_t *image, size_t image_step, int channels, int width,
+                               int height, const uint8_t *mask, size_t mask_step, int32_t *counts, void *stream);
+/* Extension.  vertices = DEVICE cart_mesh_vertex [max_vertices], n_vertices = DEVICE int32 (both as cart_voxel_map_mesh wrote them: pass
+ * counts + 2), max_vertices in 1..2^26, origin3 = HOST int64 [3] with |o_a| <= 2^27 (the mesh's origin), colors = DEVICE cart_voxel_rgb
+ * [max_vertices] whose weight byte holds alpha.  Checked in this order: max_vertices, origin3, the object, then pointers, 4-byte
+ * alignment and overlaps (colors may overlap neither input).  One launch, no host synchronisation. */
+int cart_voxel_color_vertices(cart_voxel_color *color, const cart_mesh_vertex *vertices, const int32_t *n_vertices, int max_vertices,
+                              const int64_t *origin3, cart_voxel_rgb *colors, void *stream);
+/* Extension.  disp = DEVICE int16 image; image_bgr = DEVICE 8UC3 image (image_step >= 3 width), alpha = DEVICE u8 image or NULL, counts =
+ * DEVICE int32 [1] (4-byte aligned) or NULL.  Checked in this order: camera, pose, width and height, the object, then pointers, alignment,
+ * steps and overlaps (no output may overlap disp or another output).  One launch, no host synchronisation. */
+int cart_voxel_color_render(cart_voxel_color *color, const cart_ego_camera *camera, const double *pose, const int16_t *disp,
+                            size_t disp_step, int width, int height, uint8_t *image_bgr, size_t image_step, uint8_t *alpha,
+                            size_t alpha_step, int32_t *counts, void *stream);
+/* Extension.  As cart_voxel_map_read / _write, on HOST cart_voxel_rgb [cells_z][cells_y][cells_x] in window order; both synchronise
+ * `stream`.  _read gives zeros and a zero origin without a window.  _write takes the origins cart_voxel_map_write takes (multiples of 8
+ * within 2^27; checked first, then the object, then host_voxels) and leaves the object valid at that origin: a saved map restores with
+ * its colours, and tests can sample arbitrary volumes. */
+int cart_voxel_color_read(cart_voxel_color *color, cart_voxel_rgb *host_voxels, int64_t *origin3, void *stream);
+int cart_voxel_color_write(cart_voxel_color *color, const cart_voxel_rgb *host_voxels, const int64_t *origin3, void *stream);
 
 /* ---- Frame-to-model pose tracking against the TSDF volume (spec S34) ---------------------------------------------
  * An extension: the reference estimates no pose.  Gauss-Newton refinement of a camera-to-world pose P (3 x 4 as cart_voxel_map_raycast
