@@ -239,6 +239,17 @@ class ModelTrackResult(C.Structure):
 MODEL_TRACK_MAX_ITERATIONS = 16   # CART_MODEL_TRACK_MAX_ITERATIONS
 
 
+class ModelTrackColorParams(C.Structure):
+    # mirrors cart_model_track_color_params (include/cart_engine.h, spec S38); the defaults are cart_model_track_color_default_params' (build-owned, untuned)
+    _fields_ = [(n, C.c_double) for n in ("photo_weight", "photo_gate")] + [(n, C.c_int32) for n in ("color_min_weight", "reserved")]
+
+
+class ModelTrackColorResult(C.Structure):
+    # mirrors cart_model_track_color_result (include/cart_engine.h, spec S38): cart_model_track_result, then the photometric figures
+    _fields_ = ModelTrackResult._fields_ + [(n, C.c_double) for n in ("rms_photo_initial", "rms_photo", "cost_initial", "cost")] + \
+               [(n, C.c_int32) for n in ("n_photo_initial", "n_photo")]
+
+
 FUSION_NONE, FUSION_MEASURED, FUSION_AGREED, FUSION_REPLACED, FUSION_PREDICTED = range(5)   # CART_FUSION_*
 
 
@@ -400,6 +411,9 @@ PROTOTYPES = {
     "cart_model_track_create": (_i, [_vp, _i, _i, C.POINTER(_vp)]),
     "cart_model_track_destroy": (None, [_vp]),
     "cart_model_track_refine": (_i, [_vp, _vp, C.POINTER(EgoCamera), C.POINTER(C.c_double), C.POINTER(ModelTrackParams), _vp, _sz, _vp, _sz, _i, _i, _vp, _vp]),
+    "cart_model_track_color_default_params": (None, [C.POINTER(ModelTrackColorParams)]),
+    "cart_model_track_refine_color": (_i, [_vp, _vp, _vp, C.POINTER(EgoCamera), C.POINTER(C.c_double), C.POINTER(ModelTrackParams), C.POINTER(ModelTrackColorParams),
+                                           _vp, _sz, _vp, _sz, _i, _vp, _sz, _i, _i, _vp, _vp]),
     "cart_optical_flow": (_i, [_vp, _vp, _sz, _vp, _sz, _i, _i, _i, _vp, _sz, _vp]),
     "cart_flow_default_params": (None, [C.POINTER(FlowParams)]),
     "cart_flow_pyramid_levels": (_i, [_i, _i, _i, C.POINTER(_i), C.POINTER(_i)]),

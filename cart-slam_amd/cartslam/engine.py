@@ -10,7 +10,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import DenseEgoParams, ModelTrackParams, EgoCamera, EgoParams, EngineParams, FusionParams, LocalBAParams, MatchParams, MotionParams, ObjectParams, PlaceParams, PlaneMapParams, PlaneParams, PoseGraphParams, SuperpixelParams, VoxelMapParams
+from ._lib import DenseEgoParams, ModelTrackColorParams, ModelTrackParams, EgoCamera, EgoParams, EngineParams, FusionParams, LocalBAParams, MatchParams, MotionParams, ObjectParams, PlaceParams, PlaneMapParams, PlaneParams, PoseGraphParams, SuperpixelParams, VoxelMapParams
 
 INVALID = -32768  # CARTSLAM_DISPARITY_INVALID, reference include/modules/disparity.hpp:17
 
@@ -1713,9 +1713,18 @@ MODEL_TRACK_RESULT_DTYPE = np.dtype([("R", "<f8", 9), ("t", "<f8", 3), ("rms_ini
                                      ("n_initial", "<i4"), ("n_inliers", "<i4"), ("steps", "<i4"), ("reserved", "<i4")])   # cart_model_track_result
 
 
+MODEL_TRACK_COLOR_RESULT_DTYPE = np.dtype(MODEL_TRACK_RESULT_DTYPE.descr + [("rms_photo_initial", "<f8"), ("rms_photo", "<f8"), ("cost_initial", "<f8"), ("cost", "<f8"),
+                                                                            ("n_photo_initial", "<i4"), ("n_photo", "<i4")])   # cart_model_track_color_result
+
+
 def model_track_params(**fields):
     """cart_model_track_default_params (spec S34; the defaults are build-owned and untuned) with the given fields replaced."""
     return _default_params(ModelTrackParams, "model_track", fields)
+
+
+def model_track_color_params(**fields):
+    """cart_model_track_color_default_params (spec S38; the defaults are build-owned and untuned) with the given fields replaced."""
+    return _default_params(ModelTrackColorParams, "model_track_color", fields)
 
 
 class ModelTrack(_DeviceObject):
@@ -1753,6 +1762,37 @@ class ModelTrack(_DeviceObject):
         if stream is not None:
             stream.synchronize()
         return res.cpu().numpy().view(MODEL_TRACK_RESULT_DTYPE).reshape(-1)
+
+    def refine_color(self, voxel_map, voxel_color, camera, pose0, disp, image, params=None, color_params=None, mask=None, stream=None, raw=False):
+        """refine() with a photometric term (cart_model_track_refine_color, spec S38 in DESIGN.md 7.20): voxel_color = the VoxelColor of
+        voxel_map, image = the frame's uint8 [h, w] (gray) or [h, w, 3] (B, G, R) image, color_params = model_track_color_params(...).
+        Reads both volumes only.  -> the result as a MODEL_TRACK_COLOR_RESULT_DTYPE array of one record (host); raw=True returns the
+        device tensor (176 bytes as float64) with no host round trip."""
+        import torch
+        cam = _camera(camera)
+        p = params if params is not None else model_track_params()
+        cp = color_params if color_params is not None else model_track_color_params()
+        with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):   # uploads and the result's allocation on the call's stream
+            d, im, mk = _to_device(disp, torch.int16), _to_device(image, torch.uint8), _to_device(mask, torch.uint8)
+            if not isinstance(d, torch.Tensor) or d.dtype != torch.int16 or d.dim() != 2:
+                raise EngineError("disp must be an int16 [h, w] image")
+            if not isinstance(im, torch.Tensor) or im.dim() not in (2, 3):
+                raise EngineError("image must be a uint8 [h, w] or [h, w, 3] image")
+            channels = int(im.shape[2]) if im.dim() == 3 else 1
+            _check_frame_image(im, torch.uint8, "image", d, channels if im.dim() == 3 else None)
+            if mk is not None:
+                _check_frame_image(mk, torch.uint8, "mask", d)
+            res = torch.empty(MODEL_TRACK_COLOR_RESULT_DTYPE.itemsize // 8, dtype=torch.float64, device=d.device)   # every byte is written by the call
+        h, w = int(d.shape[0]), int(d.shape[1])
+        sp = C.c_void_p(stream.cuda_stream) if stream is not None else _stream_ptr()
+        self._check(self._lib.cart_model_track_refine_color(self._h, voxel_map._h, voxel_color._h, C.byref(cam), _pose12(pose0), C.byref(p), C.byref(cp), *_pitched(d, 1),
+                                                            *_pitched(im, im.dim() - 1), channels, *_pitched(mk, 1), w, h, C.c_void_p(res.data_ptr()), sp),
+                    "cart_model_track_refine_color")
+        if raw:
+            return res
+        if stream is not None:
+            stream.synchronize()
+        return res.cpu().numpy().view(MODEL_TRACK_COLOR_RESULT_DTYPE).reshape(-1)
 
 
 OBJECT_DTYPE = np.dtype([("component", "<i4"), ("area", "<i4"), ("x0", "<i4"), ("y0", "<i4"), ("x1", "<i4"), ("y1", "<i4"), ("median_bin", "<i4"), ("n_hist", "<i4"),

@@ -741,6 +741,36 @@ struct ColorVerticesArgs {
 void launch_color_integrate(const ColorIntegrateArgs &a, hipStream_t s);
 void launch_color_render(const ColorRenderArgs &a, hipStream_t s);
 void launch_color_vertices(const ColorVerticesArgs &a, hipStream_t s);
+// ---- colour-aided frame-to-model tracking (modeltrack_color_kernels.hip) ----
+constexpr int kTrackColorSums = 29;     // S34's 28 sums, then the sum of rc rc
+constexpr int kTrackColorWords = 31;    // 8-byte words of a row partial: the sums, (count, candidates) as two int32, (photometric count, 0)
+constexpr int kTrackColorCols = 1;      // sampled columns of a lane whose loads and sixteen corner gathers are issued together
+struct ModelTrackColorState {           // what stays on the device between the launches of one call
+    double R[9], t[3];
+    double rms_initial, rms_photo_initial, cost_initial;
+    int32_t n_initial, n_photo_initial, n_candidates, steps, stop, reserved;
+};
+struct ModelTrackColorArgs {
+    VoxelGrid grid;                     // the TSDF volume under the map's origin
+    VoxelGrid cgrid;                    // the colour volume under the colour object's own origin
+    cart_ego_camera cam;
+    cart_voxel_map_params mp;           // the map's own: the pixel gates, voxel_size and min_weight
+    cart_model_track_params p;
+    cart_model_track_color_params cp;
+    double pose0[12];
+    const int16_t *disp; size_t disp_step;
+    const uint8_t *mask; size_t mask_step;              // NULL = no mask
+    const uint8_t *image; size_t image_step;
+    int channels;                                       // 1 (gray) or 3 (B, G, R)
+    int w, h, ni, nj;                                   // the image and its sample grid
+    int rows_cap;                                       // rows of the partial table: word k of sampled row j is partial[k * rows_cap + j]
+    int empty;                                          // the map has no window: no pixel is a candidate
+    int cempty;                                         // the colour object has no window: no pixel is a photometric inlier
+    double *partial;
+    ModelTrackColorState *state;
+    cart_model_track_color_result *result;
+};
+void launch_model_track_color(const ModelTrackColorArgs &a, hipStream_t s);   // the 2 (iterations + 1) launches of one call
 void launch_narrow_copy(const void *src, void *dst, size_t bytes, int blocks, hipStream_t s);
 int kernel_count();
 

@@ -3,6 +3,7 @@
 // the call is given (engine_voxelmap.h) and is only read.
 
 #include "engine_host.h"
+#include "engine_modeltrack.h"
 #include "engine_voxelmap.h"
 
 using namespace cart_amd;
@@ -11,12 +12,6 @@ extern "C" {
 
 static_assert(sizeof(cart_model_track_params) == 2 * 8 + 3 * 4 + 4, "cart_model_track_params: two doubles and three int32");
 static_assert(sizeof(cart_model_track_result) == sizeof(cart_dense_ego_result), "cart_model_track_result has the layout of cart_dense_ego_result");
-
-struct cart_model_track : SizedObject {
-    using SizedObject::SizedObject;
-    double *partial = nullptr;          // [kDenseWords][max_height]
-    DenseEgoState *state = nullptr;
-};
 
 void cart_model_track_default_params(cart_model_track_params *p) {
     if (!p) return;
@@ -29,7 +24,8 @@ int cart_model_track_create(cart_engine *e, int max_width, int max_height, cart_
     HIP_TRY(hipSetDevice(e->params.device_id));
     cart_model_track *g = new (std::nothrow) cart_model_track(e, max_width, max_height);
     if (!g) return fail("out of host memory");
-    if (g->alloc(&g->partial, (size_t)kDenseWords * max_height * sizeof(double)) || g->alloc(&g->state, sizeof(DenseEgoState)) || g->create_event()) {
+    if (g->alloc(&g->partial, (size_t)kTrackColorWords * max_height * sizeof(double)) || g->alloc(&g->state, sizeof(DenseEgoState)) ||
+        g->alloc(&g->color_state, sizeof(ModelTrackColorState)) || g->create_event()) {
         destroy_object(g);
         return fail("allocating the model tracking workspaces failed");
     }
@@ -42,12 +38,7 @@ void cart_model_track_destroy(cart_model_track *g) { destroy_object(g); }
 int cart_model_track_refine(cart_model_track *g, cart_voxel_map *m, const cart_ego_camera *cam, const double *pose0, const cart_model_track_params *p,
                             const int16_t *disp, size_t disp_step, const uint8_t *mask, size_t mask_step, int w, int h, cart_model_track_result *result,
                             void *stream_) {
-    if (!p) return fail("params is NULL");
-    if (!(p->residual_gate > 0) || !(p->residual_gate <= 1)) return fail("residual_gate must be a number in (0, 1]");
-    if (!(p->damping >= 0) || !std::isfinite(p->damping)) return fail("damping must be a number that is not negative");
-    if (p->iterations < 0 || p->iterations > CART_MODEL_TRACK_MAX_ITERATIONS) return fail("iterations must be in [0, 16]");
-    if (p->stride < 1 || p->stride > 16) return fail("stride must be in [1, 16]");
-    if (p->min_inliers < 6 || p->min_inliers > (1 << 30)) return fail("min_inliers must be in [6, 2^30]");
+    if (check_model_track_params(p)) return -1;
     if (check_camera(cam) || check_pose("pose0", pose0) || check_frame_size(w, h)) return -1;
     if (!g) return fail("bad arguments");
     if (!m) return fail("map is NULL");

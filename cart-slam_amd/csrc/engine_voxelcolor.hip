@@ -6,6 +6,7 @@
 // call's stream.  The counter block is zeroed once at create and left all zero by every call.
 
 #include "engine_host.h"
+#include "engine_voxelcolor.h"
 #include "engine_voxelmap.h"
 
 using namespace cart_amd;
@@ -13,22 +14,6 @@ using namespace cart_amd;
 extern "C" {
 
 static_assert(sizeof(cart_voxel_rgb) == 4, "cart_voxel_rgb is one 32-bit word");
-
-struct cart_voxel_color : DeviceObject {
-    using DeviceObject::DeviceObject;
-    int n[3] = {0, 0, 0};                   // nx, ny, nz: the map's
-    cart_voxel_map_params p{};              // the map's, copied at create
-    int max_weight = CART_VOXEL_COLOR_DEFAULT_MAX_WEIGHT;
-    uint32_t *voxels = nullptr;             // [nz][ny][nx] words b | g << 8 | r << 16 | weight << 24, toroidal (engine_internal.h, VoxelGrid)
-    int32_t *counters = nullptr;            // [kColorCounters]
-    bool valid = false;                     // a window exists (guarded by mu)
-    int64_t o[3] = {0, 0, 0};               // its origin in absolute voxels
-};
-
-static VoxelGrid color_grid(const cart_voxel_color *c) {
-    return VoxelGrid{c->voxels, c->n[0], c->n[1], c->n[2], floor_mod(c->o[0], c->n[0]), floor_mod(c->o[1], c->n[1]), floor_mod(c->o[2], c->n[2]),
-                     (double)c->o[0], (double)c->o[1], (double)c->o[2]};
-}
 
 int cart_voxel_color_create(cart_engine *e, cart_voxel_map *map, int max_weight, cart_voxel_color **out) {
     if (max_weight < 1 || max_weight > 255) return fail("max_weight must be in [1, 255]");

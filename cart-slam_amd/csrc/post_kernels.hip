@@ -883,6 +883,6 @@ void launch_narrow_copy(const void *src, void *dst, size_t bytes, int blocks, hi
     hipLaunchKernelGGL(narrow_copy_kernel, dim3(blocks), dim3(256), 0, s, static_cast<const uint8_t *>(src), static_cast<uint8_t *>(dst), bytes);
 }
 
-int kernel_count() { return 151; }  // device kernels in the library (counted from the generated ISA): the SGM files 39 (sgm_census 1; sgm_aggregate 8; sgm_wta 28: wta x6, wta_band x7, wta_fused x8, rv_merge x6, uniq_table; sgm_post 2: post, post_interp) + post_kernels 17 + superpixel_kernels 8 + flow 17 (flow_kernels 3; flow_pyramid_kernels 14: downsample, refine x12, median) + planefit_kernels 11 + orb_kernels 4 + match_kernels 3 + ego_kernels 6 + planemap_kernels 3 + motion_kernels 2 + dense_ego_kernels 2 + place_kernels 3 + posegraph_kernels 3 + object_kernels 6 + localba_kernels 13 + voxelmap_kernels 3 + modeltrack_kernels 2 + voxel_rebuild_kernels 1 + voxelmesh_kernels 5 + voxelcolor_kernels 3
+int kernel_count() { return 153; }  // device kernels in the library (counted from the generated ISA): the SGM files 39 (sgm_census 1; sgm_aggregate 8; sgm_wta 28: wta x6, wta_band x7, wta_fused x8, rv_merge x6, uniq_table; sgm_post 2: post, post_interp) + post_kernels 17 + superpixel_kernels 8 + flow 17 (flow_kernels 3; flow_pyramid_kernels 14: downsample, refine x12, median) + planefit_kernels 11 + orb_kernels 4 + match_kernels 3 + ego_kernels 6 + planemap_kernels 3 + motion_kernels 2 + dense_ego_kernels 2 + place_kernels 3 + posegraph_kernels 3 + object_kernels 6 + localba_kernels 13 + voxelmap_kernels 3 + modeltrack_kernels 2 + voxel_rebuild_kernels 1 + voxelmesh_kernels 5 + voxelcolor_kernels 3 + modeltrack_color_kernels 2
 
 }  // namespace cart_amd

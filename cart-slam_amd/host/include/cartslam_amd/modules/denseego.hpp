@@ -27,6 +27,9 @@ bool acceptDenseEgo(const cart_dense_ego_result &r);
 // The consumer's rule of spec S34 (frame-to-model tracking, the voxel_map module's "track"): the refined pose is taken iff status == 1, every
 // number of the record is finite, rms <= rms_initial and n_inliers >= minInliers (restated in tests/np_modeltrack.py, accept).
 bool acceptModelTrack(const cart_model_track_result &r, int minInliers);
+// The consumer's rule of spec S38 (colour-aided tracking, the voxel_map module's "track_color"): the refined pose is taken iff status == 1,
+// every number of the record is finite, cost <= cost_initial and n_inliers >= minInliers (restated in tests/np_modeltrack_color.py, accept).
+bool acceptModelTrackColor(const cart_model_track_color_result &r, int minInliers);
 
 class DenseEgoModule : public SyncWrapperSystemModule {
    public:

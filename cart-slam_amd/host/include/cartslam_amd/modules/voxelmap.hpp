@@ -14,6 +14,9 @@
 // (8UC1 or 8UC3) right after the geometry integrate; on a frame that rebuilt the volume nothing is colour-integrated and the stored colours
 // stay (the keyframe store holds no images).  With "raycast" it also publishes "image_model" and "image_model_alpha", the model's colours
 // behind "disparity_model"; with "mesh", "voxel_mesh_colors" beside the unchanged "voxel_mesh".  Without "color" nothing changes.
+// With "track_color" (spec DESIGN.md S38; needs "track" and "color") the frame's pose is refined through cart_model_track_refine_color with
+// the frame's reference image, before the frame's geometry and colour integrates, so the model holds earlier frames only; the pose is
+// taken by the cost rule and the whole record is published as "model_track_color_result" beside the unchanged "model_track_result".
 #pragma once
 #include <array>
 #include <mutex>
@@ -34,6 +37,7 @@
 #define CARTSLAM_KEY_VOXEL_MESH_COLORS "voxel_mesh_colors"                // VoxelMeshColors, with "color" and "mesh"
 #define CARTSLAM_KEY_MODEL_POSE "model_pose"                              // EgoMotion, with "track" only: the tracked pose and the relative pose between tracked poses
 #define CARTSLAM_KEY_MODEL_TRACK_RESULT "model_track_result"              // cart_model_track_result as the device wrote it, with "track" only
+#define CARTSLAM_KEY_MODEL_TRACK_COLOR_RESULT "model_track_color_result"  // cart_model_track_color_result as the device wrote it, with "track_color" only
 
 namespace cart {
 struct VoxelMap {
@@ -88,9 +92,13 @@ struct VoxelMapOptions : CameraOptions {   // the factory fills the camera from 
     int colorMaxWeight = CART_VOXEL_COLOR_DEFAULT_MAX_WEIGHT;
     double residualGate = 0.9, damping = 0.01;   // cart_model_track_default_params
     int iterations = 4, stride = 1, minInliers = 1024;
+    bool trackColor = false;                  // S38: "track" with the photometric term; needs track and color
+    double photoWeight = 64.0, photoGate = 0.25;   // cart_model_track_color_default_params
+    int colorMinWeight = 1;
 };
 
 static_assert(sizeof(cart_model_track_result) == 136, "cart_model_track_result layout");
+static_assert(sizeof(cart_model_track_color_result) == 176, "cart_model_track_color_result layout");
 
 class VoxelMapModule : public SyncWrapperSystemModule {
    public:
@@ -112,6 +120,6 @@ class VoxelMapModule : public SyncWrapperSystemModule {
     double tracked[12] = {};
     DeviceScratch meshBuffers;        // with "mesh": the device vertices and quads of one extraction (no stream, no host side)
     long long meshFrames = 0;         // with "mesh": frames seen
-    DeviceScratch scratch;            // the one stream; the tracking record and the five counts on the device and the pinned buffer they are downloaded through
+    DeviceScratch scratch;            // the one stream; the tracking records and the counts on the device and the pinned buffer they are downloaded through
 };
 }  // namespace cart

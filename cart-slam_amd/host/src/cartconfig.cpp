@@ -314,6 +314,10 @@ void applyModuleConfig(const Value &modulesConfig, std::shared_ptr<System> syste
             o.iterations = get(moduleConfig, "iterations", o.iterations);
             o.stride = get(moduleConfig, "stride", o.stride);
             o.minInliers = get(moduleConfig, "min_inliers", o.minInliers);
+            o.trackColor = get(moduleConfig, "track_color", o.trackColor);   // S38: "track" with a photometric term against the colour volume; needs "track" and "color"
+            o.photoWeight = get(moduleConfig, "photo_weight", o.photoWeight);
+            o.photoGate = get(moduleConfig, "photo_gate", o.photoGate);
+            o.colorMinWeight = get(moduleConfig, "color_min_weight", o.colorMinWeight);
             system->addModule<VoxelMapModule>(o);
         } else if (endsWith(moduleType, "_visualization")) {
             std::cerr << "[cartconfig] skipping GUI module type " << moduleType << " (out of scope)\n";

@@ -34,6 +34,17 @@ bool acceptModelTrack(const cart_model_track_result &r, int minInliers) {
     return true;
 }
 
+bool acceptModelTrackColor(const cart_model_track_color_result &r, int minInliers) {
+    if (r.status != 1 || r.n_inliers < minInliers || !(r.cost <= r.cost_initial)) return false;
+    for (double v : {r.rms_initial, r.rms, r.rms_photo_initial, r.rms_photo, r.cost_initial, r.cost})
+        if (!std::isfinite(v)) return false;
+    for (double v : r.R)
+        if (!std::isfinite(v)) return false;
+    for (double v : r.t)
+        if (!std::isfinite(v)) return false;
+    return true;
+}
+
 DenseEgoModule::DenseEgoModule(const DenseEgoOptions &options) : SyncWrapperSystemModule("DenseEgo"), options(options) {
     checkCamera(options);
     // the library's own checks, without a device: everything valid gets as far as the missing object

@@ -231,6 +231,10 @@ int main(int argc, char **argv) {
                     std::ofstream o = writeBin(dump, id, CARTSLAM_KEY_MODEL_POSE, record.get(), sizeof(*record));
                     append(o, tracked->pose, sizeof(tracked->pose));
                 }
+                if (run->hasData(CARTSLAM_KEY_MODEL_TRACK_COLOR_RESULT)) {   // voxel_map with "track_color": the 176-byte cart_model_track_color_result
+                    auto record = run->getData<cart_model_track_color_result>(CARTSLAM_KEY_MODEL_TRACK_COLOR_RESULT);
+                    writeBin(dump, id, "model_track_color", record.get(), sizeof(*record));
+                }
                 if (run->hasData(CARTSLAM_KEY_MOTION)) {   // int32 width, height; the filtered labels, the raw labels, the residual records
                     auto labels = run->getData<cart::image_t>(CARTSLAM_KEY_MOTION);
                     const int32_t shape[2] = {labels->cols, labels->rows};

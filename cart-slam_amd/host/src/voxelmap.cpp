@@ -1,4 +1,4 @@
-// voxelmap.cpp -- VoxelMapModule (cartslam_amd/modules/voxelmap.hpp): the rolling TSDF voxel map with model raycast, spec DESIGN.md S33; its rebuild from stored keyframes, S35; its surface mesh, S36; its colour companion, S37.
+// voxelmap.cpp -- VoxelMapModule (cartslam_amd/modules/voxelmap.hpp): the rolling TSDF voxel map with model raycast, spec DESIGN.md S33; its rebuild from stored keyframes, S35; its surface mesh, S36; its colour companion, S37; colour-aided tracking, S38.
 #include "cartslam_amd/modules/voxelmap.hpp"
 
 #include <algorithm>
@@ -18,6 +18,7 @@ cart_voxel_map_params paramsOf(const VoxelMapOptions &o) {
     return cart_voxel_map_params{o.voxelSize, o.minDisparity, o.minDepth, o.maxDepth, o.truncation, o.disparitySigma, o.lookahead, o.marchStep, o.maxWeight, o.minWeight};
 }
 cart_model_track_params trackParamsOf(const VoxelMapOptions &o) { return cart_model_track_params{o.residualGate, o.damping, o.iterations, o.stride, o.minInliers}; }
+cart_model_track_color_params trackColorParamsOf(const VoxelMapOptions &o) { return cart_model_track_color_params{o.photoWeight, o.photoGate, o.colorMinWeight, 0}; }
 
 // p_cur = R p_prev + t between two camera-to-world poses: R = Rc^T Rp, t = Rc^T (tp - tc), in plain double loops
 void relativeOf(const double prev[12], const double cur[12], double R[9], double t[3]) {
@@ -32,7 +33,9 @@ constexpr size_t kRebuildCountsOffset = kCountsOffset + 8 * sizeof(int32_t);   /
 static_assert(kRebuildCountsOffset % 8 == 0, "the rebuild's counts are int64");
 constexpr size_t kMeshCountsOffset = kRebuildCountsOffset + 2 * sizeof(int64_t);   // of the mesh's four counts
 constexpr size_t kColorCountsOffset = kMeshCountsOffset + 4 * sizeof(int32_t);   // of the colour integrate's two counts and the render's one
-constexpr size_t kScratchBytes = kColorCountsOffset + 4 * sizeof(int32_t);
+constexpr size_t kTrackColorOffset = kColorCountsOffset + 4 * sizeof(int32_t);   // of the colour-aided tracking record (S38), 8-byte aligned
+static_assert(kTrackColorOffset % 8 == 0, "the colour-aided tracking record holds doubles");
+constexpr size_t kScratchBytes = kTrackColorOffset + sizeof(cart_model_track_color_result);
 }  // namespace
 
 VoxelMapModule::VoxelMapModule(const VoxelMapOptions &options)
@@ -52,6 +55,14 @@ VoxelMapModule::VoxelMapModule(const VoxelMapOptions &options)
         const cart_ego_camera cam = cameraOf(options);
         const cart_model_track_params tp = trackParamsOf(options);
         (void)cart_model_track_refine(nullptr, nullptr, &cam, kIdentityPose, &tp, nullptr, 0, nullptr, 0, 1, 1, nullptr, nullptr);
+        requireLibraryAccepts();
+    }
+    if (options.trackColor) {
+        if (!options.track || !options.color) throw std::invalid_argument("track_color requires \"track\": true and \"color\": true");
+        const cart_ego_camera cam = cameraOf(options);
+        const cart_model_track_params tp = trackParamsOf(options);
+        const cart_model_track_color_params cp = trackColorParamsOf(options);
+        (void)cart_model_track_refine_color(nullptr, nullptr, nullptr, &cam, kIdentityPose, &tp, &cp, nullptr, 0, nullptr, 0, 1, nullptr, 0, 1, 1, nullptr, nullptr);
         requireLibraryAccepts();
     }
     if (options.rebuild) {
@@ -87,6 +98,7 @@ VoxelMapModule::VoxelMapModule(const VoxelMapOptions &options)
     if (options.track) {
         this->providesData.push_back(CARTSLAM_KEY_MODEL_POSE);
         this->providesData.push_back(CARTSLAM_KEY_MODEL_TRACK_RESULT);
+        if (options.trackColor) this->providesData.push_back(CARTSLAM_KEY_MODEL_TRACK_COLOR_RESULT);
     }
     if (options.mesh) this->providesData.push_back(CARTSLAM_KEY_VOXEL_MESH);
     if (options.color) {
@@ -149,18 +161,39 @@ system_data_t VoxelMapModule::runInternal(System &, SystemRunData &data) {
     int32_t *counts = reinterpret_cast<int32_t *>(scratch.dev<char>() + kCountsOffset);   // [0, 2): integrate; [2, 5): raycast
     std::shared_ptr<EgoMotion> modelPose;
     std::shared_ptr<cart_model_track_result> trackResult;
+    std::shared_ptr<cart_model_track_color_result> trackColorResult;
     if (options.track) {
         // the prediction: the previous tracked pose chained with this frame's relative pose (kept where the frame has none); frame 1 takes the pose itself
         if (haveTracked) chainPose(tracked, ego->result, pose);
         const cart_model_track_params tp = trackParamsOf(options);
-        if (cart_model_track_refine(tracker, map, &cam, pose, &tp, disparity->ptr<int16_t>(), disparity->step, mask ? mask->ptr<uint8_t>() : nullptr, mask ? mask->step : 0,
-                                    cols, rows, scratch.dev<cart_model_track_result>(), s) != 0)
-            failAbi("cart_model_track_refine");
-        hipCheck(hipMemcpyAsync(scratch.host(), scratch.dev(), sizeof(cart_model_track_result), hipMemcpyDeviceToHost, s), "hipMemcpyAsync of the model tracking result");
-        scratch.wait();   // the pose decides where the frame is integrated: the host must see the record first
-        trackResult = std::make_shared<cart_model_track_result>();
-        std::memcpy(trackResult.get(), scratch.host(), sizeof(*trackResult));
-        if (acceptModelTrack(*trackResult, options.minInliers))
+        bool take = false;
+        if (options.trackColor) {   // S38: against both volumes as the earlier frames left them, with this frame's reference image
+            const image_t image = getReferenceImage(data.dataElement);
+            if ((image.type() != CV_8UC3 && image.type() != CV_8UC1) || image.rows != rows || image.cols != cols)
+                throw std::runtime_error("VoxelMapModule: track_color needs a CV_8UC1 or CV_8UC3 reference image of the disparity's size");
+            const cart_model_track_color_params cp = trackColorParamsOf(options);
+            cart_model_track_color_result *record = reinterpret_cast<cart_model_track_color_result *>(scratch.dev<char>() + kTrackColorOffset);
+            if (cart_model_track_refine_color(tracker, map, color, &cam, pose, &tp, &cp, disparity->ptr<int16_t>(), disparity->step, image.ptr<uint8_t>(), image.step,
+                                              image.type() == CV_8UC3 ? 3 : 1, mask ? mask->ptr<uint8_t>() : nullptr, mask ? mask->step : 0, cols, rows, record, s) != 0)
+                failAbi("cart_model_track_refine_color");
+            hipCheck(hipMemcpyAsync(scratch.host<char>() + kTrackColorOffset, record, sizeof(*record), hipMemcpyDeviceToHost, s), "hipMemcpyAsync of the colour-aided tracking result");
+            scratch.wait();   // the pose decides where the frame is integrated: the host must see the record first
+            trackColorResult = std::make_shared<cart_model_track_color_result>();
+            std::memcpy(trackColorResult.get(), scratch.host<char>() + kTrackColorOffset, sizeof(*trackColorResult));
+            trackResult = std::make_shared<cart_model_track_result>();   // the first 136 bytes have its layout and meaning
+            std::memcpy(trackResult.get(), trackColorResult.get(), sizeof(*trackResult));
+            take = acceptModelTrackColor(*trackColorResult, options.minInliers);
+        } else {
+            if (cart_model_track_refine(tracker, map, &cam, pose, &tp, disparity->ptr<int16_t>(), disparity->step, mask ? mask->ptr<uint8_t>() : nullptr, mask ? mask->step : 0,
+                                        cols, rows, scratch.dev<cart_model_track_result>(), s) != 0)
+                failAbi("cart_model_track_refine");
+            hipCheck(hipMemcpyAsync(scratch.host(), scratch.dev(), sizeof(cart_model_track_result), hipMemcpyDeviceToHost, s), "hipMemcpyAsync of the model tracking result");
+            scratch.wait();   // the pose decides where the frame is integrated: the host must see the record first
+            trackResult = std::make_shared<cart_model_track_result>();
+            std::memcpy(trackResult.get(), scratch.host(), sizeof(*trackResult));
+            take = acceptModelTrack(*trackResult, options.minInliers);
+        }
+        if (take)
             for (int r = 0; r < 3; ++r) {
                 for (int c = 0; c < 3; ++c) pose[4 * r + c] = trackResult->R[3 * r + c];
                 pose[4 * r + 3] = trackResult->t[r];
@@ -304,6 +337,7 @@ system_data_t VoxelMapModule::runInternal(System &, SystemRunData &data) {
     if (options.track) {
         out.push_back(MODULE_PAIR(CARTSLAM_KEY_MODEL_POSE, modelPose));
         out.push_back(MODULE_PAIR(CARTSLAM_KEY_MODEL_TRACK_RESULT, trackResult));
+        if (options.trackColor) out.push_back(MODULE_PAIR(CARTSLAM_KEY_MODEL_TRACK_COLOR_RESULT, trackColorResult));
     }
     return out;
 }

@@ -1385,6 +1385,49 @@ int cart_model_track_refine(cart_model_track *obj, cart_voxel_map *map, const ca
                             const cart_model_track_params *params, const int16_t *disp, size_t disp_step, const uint8_t *mask,
                             size_t mask_step, int width, int height, cart_model_track_result *result, void *stream);
 
+/* Extension: colour-aided frame-to-model tracking (spec S38).  S34's evaluation, to the letter, plus a photometric term
+ * read from the colour companion of the volume (cart_voxel_color, S37), for every geometric inlier and only if photo_weight > 0:
+ *   7. L_obs = b + 2 g + r of the frame's pixel (x, y) in integers (0 .. 1020; 4 v for one channel).
+ *   8. The colour sample at p against the colour object's OWN grid and origin: a = p / voxel_size - 0.5, i0 = floor(a), fr = a - i0; known
+ *      iff a colour window exists, all eight corners lie in it (compared as doubles) and each has weight >= color_min_weight.  With
+ *      t[dz][dy][dx] = b + 2 g + r of the corner word, the value C and the gradient gc are step 3's expressions on these integers.
+ *   9. rc = (C - (double)L_obs) / 1020.0; the pixel is a photometric inlier iff |rc| < photo_gate.
+ *  10. Gc = gc / (1020.0 voxel_size) (the product first), Jc = (p_y Gc_z - p_z Gc_y, p_z Gc_x - p_x Gc_z, p_x Gc_y - p_y Gc_x, Gc).
+ *  11. After the pixel's geometric terms: the 21 upper sums += (photo_weight Jc_i) Jc_j, the 6 += (photo_weight Jc_i) rc, a 29th sum
+ *      += rc rc (unweighted; sum 27 stays the geometric r r), and a third count n_photo.
+ *   Order of every sum: S34's two-level lane order over 29 sums and three counts.  The step is S34's: stop at cnt < min_inliers or at a
+ *   pivot that is not > 0; H[i][i] += damping (double)cnt with the geometric count.
+ *   cost = sqrt((sum r r + photo_weight sum rc rc) / ((double)cnt + photo_weight (double)n_photo)), 0.0 at a zero denominator.
+ *   Acceptance is the consumer's: take the pose iff status == 1, every number of the record is finite, cost <= cost_initial and
+ *   n_inliers >= min_inliers, else keep pose0.  With photo_weight == 0 neither the image nor the colour volume is read, and the first
+ *   136 bytes of the record are cart_model_track_refine's on the same inputs. */
+typedef struct cart_model_track_color_params {
+    double photo_weight;                      /* finite, >= 0: the weight of the photometric term */
+    double photo_gate;                        /* finite, 0 < . <= 1: inlier gate on |rc| */
+    int32_t color_min_weight;                 /* 1..255: least weight of each colour corner */
+    int32_t reserved;                         /* must be 0 */
+} cart_model_track_color_params;
+void cart_model_track_color_default_params(cart_model_track_color_params *p); /* extension: 64, 0.25, 1, 0 (build-owned, untuned) */
+typedef struct cart_model_track_color_result { /* 176 bytes; the first 136 have cart_model_track_result's layout and meaning */
+    double R[9], t[3];
+    double rms_initial, rms;                  /* the geometric rms */
+    int32_t status, n_candidates, n_initial, n_inliers, steps, reserved;
+    double rms_photo_initial, rms_photo;      /* sqrt(sum rc rc / n_photo) at pose0 and at (R, t); 0.0 at n_photo == 0 */
+    double cost_initial, cost;                /* the weighted mean residual at pose0 and at (R, t) */
+    int32_t n_photo_initial, n_photo;         /* photometric inliers at pose0 and at (R, t) */
+} cart_model_track_color_result;
+/* Extension.  cart_model_track_refine's arguments plus `color` (made for a map of `map`'s shape, on the object's device), its parameters
+ * and the frame's image: device u8, width x height of `channels` (1 = gray, 3 = B, G, R) bytes per pixel, image_step in bytes, as
+ * cart_voxel_color_integrate takes it.  Checked in this order, all before any device call: params, color_params, channels, camera,
+ * pose0, sizes, the object, the map, the colour object (NULL, devices, shape), then pointers, alignment, steps and overlaps; a refused
+ * call touches no output.  result = DEVICE record (8-byte aligned, overlapping no input).  Reads both volumes only.  Takes the object,
+ * then the map, then the colour object.  2 (iterations + 1) plain launches on `stream`, no host synchronisation. */
+int cart_model_track_refine_color(cart_model_track *obj, cart_voxel_map *map, cart_voxel_color *color, const cart_ego_camera *camera,
+                                  const double *pose0, const cart_model_track_params *params,
+                                  const cart_model_track_color_params *color_params, const int16_t *disp, size_t disp_step,
+                                  const uint8_t *image, size_t image_step, int channels, const uint8_t *mask, size_t mask_step, int width,
+                                  int height, cart_model_track_color_result *result, void *stream);
+
 /* Stand-in for ImageOpticalFlowModule's device work (src/modules/optflow.cpp:96-140: cvtColor x2 +
  * cv::cuda::NvidiaOpticalFlow_2_0::calc(current, previous), NVIDIA fixed-function hardware): dense census block
  * matching (oracle S15).  cur / prev = the reference images of frame id and id-1 (1-channel gray or 3-channel BGR),
