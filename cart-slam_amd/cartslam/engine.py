@@ -151,6 +151,17 @@ class Engine:
         self._check(self._lib.cart_engine_set_option(self._h, _lib.OPT_BAND_ROWS, int(k)), "cart_engine_set_option")
         self._check(self._lib.cart_engine_set_option(self._h, _lib.OPT_BAND_PROBE, 1 if probe else 0), "cart_engine_set_option")
 
+    def set_band_diag(self, on=True):
+        """Plan "band_up": the WTA rebuilds the up-right diagonal path inside its tile instead of reading its slab (default on; same bits
+        either way).  Ignored with the probe and by engines that never take the plan."""
+        self._check(self._lib.cart_engine_set_option(self._h, _lib.OPT_BAND_DIAG, 1 if on else 0), "cart_engine_set_option")
+
+    def get_option(self, option):
+        """The engine's current value of one CART_OPT_* option (cart_engine_get_option)."""
+        v = C.c_int(0)
+        self._check(self._lib.cart_engine_get_option(self._h, int(option), C.byref(v)), "cart_engine_get_option")
+        return int(v.value)
+
     def set_chunk_frames(self, n):
         self._check(self._lib.cart_engine_set_option(self._h, _lib.OPT_CHUNK_FRAMES, int(n)), "cart_engine_set_option")
 

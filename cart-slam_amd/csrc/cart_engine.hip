@@ -138,9 +138,10 @@ struct Options {
     int spec;
     int band_rows;
     bool band_probe;
+    bool band_diag;
 };
 Options snapshot_options(const cart_engine *e) {   // caller holds e->mu
-    return Options{e->opt_plan, e->opt_plan_min_frames, e->chunk_frames, e->timing, e->opt_spec, e->opt_band_rows, e->opt_band_probe != 0};
+    return Options{e->opt_plan, e->opt_plan_min_frames, e->chunk_frames, e->timing, e->opt_spec, e->opt_band_rows, e->opt_band_probe != 0, e->opt_band_diag != 0};
 }
 
 // The launch plan of `n` frames handed to one launch sequence (include/cart_engine.h, CART_PLAN_*).
@@ -264,7 +265,7 @@ void launch_agg_wta(cart_engine *e, const Options &opt, const SlabTable &slabs, 
     a.ckpt_rows = band && !opt.band_probe ? opt.band_rows : 0;   // the "up" scan stores its checkpoint rows only
     launch_aggregate(a, n, st);
     between();
-    if (band) launch_wta_band(cl, cr, slabs, wl, rpk, g, e->uniq_thr, n, opt.band_rows, opt.band_probe, st);
+    if (band) launch_wta_band(cl, cr, slabs, wl, rpk, g, e->uniq_thr, n, opt.band_rows, opt.band_probe, opt.band_diag, st);
     else if (fused) launch_wta_fused(cl, cr, slabs, wl, rpk, e->rv_partial + s0 * wta_fused_partial_elems(g), g, e->uniq_thr, n, st);
     else launch_wta(slabs, wl, rpk, g, e->uniq_thr, n, st, (opt.spec & 4) != 0);
 }
@@ -411,6 +412,10 @@ int cart_engine_set_option(cart_engine *e, int option, int value) {
             if (value != 0 && value != 1) return fail("the band probe is 0 or 1");
             e->opt_band_probe = value;
             return 0;
+        case CART_OPT_BAND_DIAG:
+            if (value != 0 && value != 1) return fail("the band diagonal option is 0 or 1");
+            e->opt_band_diag = value;   // engines that never take BAND_UP keep the value and never read it
+            return 0;
         case CART_OPT_FLOW_GATHER:
             if (value != 0 && value != 1) return fail("the flow gather option is 0 or 1");
             e->opt_flow_gather = value;
@@ -436,6 +441,7 @@ int cart_engine_get_option(cart_engine *e, int option, int *value) {
         case CART_OPT_CHUNK_FRAMES: *value = e->chunk_frames; return 0;
         case CART_OPT_BAND_ROWS: *value = e->opt_band_rows; return 0;
         case CART_OPT_BAND_PROBE: *value = e->opt_band_probe; return 0;
+        case CART_OPT_BAND_DIAG: *value = e->opt_band_diag; return 0;
         case CART_OPT_FLOW_GATHER: *value = e->opt_flow_gather; return 0;
         case CART_OPT_SPEC_S8_ZERO_INVALID: *value = (e->opt_spec & 1) ? 1 : 0; return 0;
         case CART_OPT_SPEC_S7_REPLICATE_BORDER: *value = (e->opt_spec & 2) ? 1 : 0; return 0;

@@ -67,6 +67,7 @@ struct Slot {
 // Plan BAND_UP (sgm_wta.hip, wta_band_kernel): rows per band, and the launch size from which CART_PLAN_AUTO takes the plan at D = 128 with
 // 8 paths.  Both from the A/B at 1242x375 in DESIGN.md 4.1 (profiles/band_up.txt).
 constexpr int kBandRowsDefault = 8;
+constexpr int kBandDiagDefault = 1;     // the banded WTA rebuilds the up-right diagonal in LDS (CART_OPT_BAND_DIAG; profiles/band_diag.txt)
 constexpr int kBandAutoMinFrames = 4;   // 2-frame launches stay on SLABS; 4, 6, 8, 12 and 16 frames measured
 constexpr int kMaxTimings = 8;
 constexpr int kTimingRing = 256;
@@ -121,6 +122,7 @@ struct cart_engine {
     int opt_plan = CART_PLAN_AUTO;       // cart_engine_set_option
     int auto_band_min_frames = 1 << 30;  // CART_OPT_PLAN = auto: launches of at least this many frames take BAND_UP (D = 128, 8 paths)
     int opt_band_rows = cart_amd::kBandRowsDefault, opt_band_probe = 0;   // CART_OPT_BAND_ROWS / CART_OPT_BAND_PROBE
+    int opt_band_diag = cart_amd::kBandDiagDefault;                       // CART_OPT_BAND_DIAG
     int opt_plan_min_frames = 1;         // with a forced plan: launches of fewer frames still take CART_PLAN_SLABS
     int opt_flow_gather = 0;             // CART_OPT_FLOW_GATHER
     int opt_spec = 0;                    // CART_OPT_SPEC_* bits: upstream variants of S8 / S7 (default: the oracle's spec)

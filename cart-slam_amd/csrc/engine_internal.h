@@ -94,15 +94,19 @@ void launch_wta(const SlabTable &slabs, uint16_t *wta_l, uint32_t *right_pk, con
 // Slab index of the "up" direction (oracle order: down, up, right, left, diagonals).  The fused WTA computes that path itself and never reads its slab
 // (the aggregate launch may skip the direction); plan BAND_UP keeps only its checkpoint rows there.
 constexpr int kUpPath = 1;
+// Slab index of the up-right diagonal {dx = +1, dy = -1}: the banded WTA can rebuild it inside its tile (CART_OPT_BAND_DIAG) and then reads
+// only the row under each band and the column left of each tile from this slab.  The aggregation launch always writes it in full.
+constexpr int kUpRightPath = 7;
 size_t wta_fused_partial_elems(const Geometry &g);  // u32 elements of the per-frame right-view partial buffer
 void launch_wta_fused(const uint32_t *cen_l, const uint32_t *cen_r, const SlabTable &slabs, uint16_t *wta_l, uint32_t *right_pk,
                       uint32_t *partial, const Geometry &g, const uint16_t *thr, int n_frames, hipStream_t s);
 // WTA over bands of K rows that recomputes the "up" path from the checkpoint rows a launch_aggregate with ckpt_rows = K left in slab
 // kUpPath (plan BAND_UP: D = 128, 8 paths, K = 4, 8 or 16)
 // probe: the read-rate probe -- all P slabs are read (the aggregation launch stored every row), nothing is recomputed; K = 1 allowed
+// diag: the kernel also rebuilds path kUpRightPath in LDS instead of reading its slab (CART_OPT_BAND_DIAG; ignored with the probe)
 bool wta_band_supported(const Geometry &g, int K, bool probe);
 void launch_wta_band(const uint32_t *cen_l, const uint32_t *cen_r, const SlabTable &slabs, uint16_t *wta_l, uint32_t *right_pk,
-                     const Geometry &g, const uint16_t *thr, int n_frames, int K, bool probe, hipStream_t s);
+                     const Geometry &g, const uint16_t *thr, int n_frames, int K, bool probe, bool diag, hipStream_t s);
 void launch_uniq_table(float u, uint16_t *out_dev, hipStream_t s);   // test access to the integer uniqueness threshold
 void uniq_table_host(float u, uint16_t *out);
 void launch_post(const uint16_t *wta_l, const uint32_t *right_pk, const uint8_t *gray_l, const OutBatch &out, const Geometry &g, int n_frames, hipStream_t s,

@@ -165,6 +165,33 @@ __device__ __forceinline__ void agg_step(uint32_t (&a)[8], uint32_t &mm, const u
     for (int i = 0; i < 8; ++i) a[i] = n[i];
 }
 
+template <int LPP>
+__device__ __forceinline__ v4u agg_step_c(uint32_t (&a)[8], uint32_t &mm, const uint32_t (&c)[8], uint32_t sel_lo, uint32_t sel_hi,
+                                          uint32_t p1p1, uint32_t p2p2) {
+    // agg_step with the matching costs handed in: c[i] = (C[d0+8+i] << 16) + C[d0+i], the pair agg_step builds from its popcounts;
+    // returns the lane's 16 slab bytes (the caller stores them).  Used where one cost vector serves more than one consumer: the split
+    // horizontal scans of aggregate_kernel (producer / consumer waves) and the two recurrences of wta_band_kernel<.., DIAG = true>.
+    const uint32_t mp2 = mm + p2p2;
+    const uint32_t lo0 = perm(a[7], dpp_mov<DPP_ROW_SHR1>(a[7]), sel_lo);
+    const uint32_t hi7 = perm(dpp_mov<DPP_ROW_SHL1>(a[0]), a[0], sel_hi);
+    uint32_t n[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const uint32_t lo = i == 0 ? lo0 : a[i - 1];
+        const uint32_t hi = i == 7 ? hi7 : a[i + 1];
+        uint32_t t = pk_min(lo, hi) + p1p1;
+        t = pk_min3(t, a[i], mp2);
+        n[i] = (t - mm) + c[i];   // both halves of t are >= m (see agg_step)
+    }
+    const v4u q = {perm(n[1], n[0], 0x06040200u), perm(n[3], n[2], 0x06040200u), perm(n[5], n[4], 0x06040200u), perm(n[7], n[6], 0x06040200u)};
+    uint32_t x = pk_min(pk_min3(n[0], n[1], n[2]), pk_min3(n[3], n[4], pk_min3(n[5], n[6], n[7])));
+    x = pk_min(x, __builtin_amdgcn_alignbit(x, x, 16));
+    mm = group_allmin<LPP>(x);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) a[i] = n[i];
+    return q;
+}
+
 // ---- LDS staging of the right-census window (vertical + diagonal directions) ----
 // The P = 64/LPP pixels a wave works on at one step are adjacent columns of one image row, so the
 // P windows of D right features overlap in all but P-1 entries.  Per-lane window loads cost 4 B per

@@ -232,13 +232,14 @@ struct UpSweep {
         const uint8_t *ps = ps0 + (ptrdiff_t)y * row_bytes + (ptrdiff_t)path * slab_bytes;
         return __builtin_nontemporal_load((const CART_GLOBAL v4u *)((const CART_GLOBAL char *)sgpr(ps) + pin_v(lo_s)));
     }
-    // row y of the stored slabs into sv[k]: every path, or (SKIP_UP) the paths other than kUpPath
-    template <bool SKIP_UP, int NS>
+    // row y of the stored slabs into sv[k]: every path, or the paths other than kUpPath (SKIP_UP) and kUpRightPath (SKIP_UR)
+    template <bool SKIP_UP, bool SKIP_UR = false, int NS>
     __device__ __forceinline__ void load_slab_row(int y, uint32_t (&sv)[NS][4]) {
 #pragma unroll
-        for (int p = 0; p < (SKIP_UP ? NS + 1 : NS); ++p) {
+        for (int p = 0; p < NS + (SKIP_UP ? 1 : 0) + (SKIP_UR ? 1 : 0); ++p) {
             if (SKIP_UP && p == kUpPath) continue;
-            const int k = SKIP_UP && p > kUpPath ? p - 1 : p;   // compile-time after unrolling
+            if (SKIP_UR && p == kUpRightPath) continue;
+            const int k = p - (SKIP_UP && p > kUpPath ? 1 : 0) - (SKIP_UR && p > kUpRightPath ? 1 : 0);   // compile-time after unrolling
             const v4u v = load_slab(y, p);
             sv[k][0] = v.x; sv[k][1] = v.y; sv[k][2] = v.z; sv[k][3] = v.w;
         }
@@ -396,10 +397,29 @@ struct BandArgs {
 
 // RECOMP = false is the read-rate probe of the design: the same walk over all P stored slabs with no recompute, i.e. wta_kernel's work
 // in K-row tiles (CART_OPT_BAND_PROBE; K = 1 is wta_kernel's tiling).
-template <int LPP, int K, bool RECOMP = true>
+//
+// DIAG (CART_OPT_BAND_DIAG) rebuilds the up-right diagonal {dx = +1, dy = -1} (slab kUpRightPath) inside the tile as well and reads one slab less.  Like
+// "up" that path advances one row per step of the bottom-to-top walk; its predecessor of pixel (x, y) is (x - 1, y + 1), the pixel the lane group to the
+// left finished one row earlier.  The 16 slab-format bytes every lane produces for row y go to s_dg[y & 1][its lane] before the row's barrier, and the
+// lane group of column xl reads those of xl - 1 from s_dg[(y + 1) & 1] on the next row.  From HBM the path then needs only
+//   * row y1 under the band (all columns; nothing when y1 = h: the path starts fresh on the image's last row, oracle S4), which seeds s_dg[y1 & 1], and
+//   * per row the one pixel left of the tile, (x0 - 1, y + 1): a 16-byte load per lane from a wave-uniform base, every pixel of the block reading the
+//     same line, issued a row ahead with the slab prefetch and unconditional for every lane (exact counted vmcnt waits); lane group xl = 0 selects it
+//     over the LDS value.  At x0 = 0 the load is clamped to column 0 and the value replaced by the fresh state (bytes 0, minimum 0): x = 0 starts a line.
+// Both recurrences of a row sit on the same pixel, so the eight packed matching costs are computed once and both run through agg_step_c; the diagonal's
+// returned bytes are the slab's own (same kSlabChunkOrder) and enter the sum through sum_add_slab.  The diagonal keeps no registers across rows: its
+// state is unpacked from the predecessor's bytes with the checkpoint's two v_perm selectors and its minimum recomputed by path_min.
+// s_dg needs TWO buffers and no barrier of its own.  In row y a wave reads buffer (y + 1) & 1 and writes buffer y & 1, both before the barrier of row y.
+// A wave that writes buffer (y + 1) & 1 again does so in row y - 1, i.e. after it has passed the barrier of row y, which every wave reaches only after its
+// row-y read has returned (lds_barrier waits for lgkmcnt(0)); and the values a wave reads in row y were written before the barrier of row y + 1 (or the
+// set-up barrier for the seed).  With one buffer a fast wave's write of row y would race the slower neighbour's read of row y + 1's bytes.
+// Columns past the image compute on census padding and clamped slab columns as before and never write.  The path flows rightwards, so such a column can
+// never be the predecessor of a valid one -- which is why this diagonal is rebuilt and not its mirror image {-1, -1}.
+template <int LPP, int K, bool RECOMP = true, bool DIAG = false>
 __global__ __launch_bounds__(64 * LPP, 4) void wta_band_kernel(BandArgs a) {
     using WN = Win<LPP>;
-    constexpr int D = WN::D, P = WN::P, NT = 64 * LPP, NP = kMaxPaths, NS = RECOMP ? NP - 1 : NP;
+    static_assert(RECOMP || !DIAG, "the diagonal shares the matching costs of the \"up\" recompute");
+    constexpr int D = WN::D, P = WN::P, NT = 64 * LPP, NP = kMaxPaths, NS = RECOMP ? (DIAG ? NP - 2 : NP - 1) : NP;
     constexpr int DP = D + 8;                    // LDS pitch of a pixel's sum row (as wta_kernel)
     constexpr int NRV = kWtaTileX + D;
     static_assert(P * LPP == 64 && NT / LPP == kWtaTileX, "one pixel of the tile per lane group");
@@ -407,6 +427,7 @@ __global__ __launch_bounds__(64 * LPP, 4) void wta_band_kernel(BandArgs a) {
     __shared__ uint32_t s_rv[2][NRV];
     __shared__ uint32_t s_win[RECOMP ? LPP : 1][WN::BUF];     // one window buffer per wave
     __shared__ uint16_t s_thr[2048];
+    __shared__ v4u s_dg[DIAG ? 2 : 1][DIAG ? NT : 1];          // DIAG: the diagonal's slab bytes of the previous and of this row, one entry per lane
     const Geometry &g = a.g;
     keep_f16_denormals();
     const int x0 = blockIdx.x * kWtaTileX, frame = blockIdx.z;
@@ -421,6 +442,18 @@ __global__ __launch_bounds__(64 * LPP, 4) void wta_band_kernel(BandArgs a) {
     const bool valid = sw.valid;
     uint32_t *wbuf = &s_win[RECOMP ? sw.wid : 0][0];
     uint32_t cw[WN::NLD], cfl, sv[NS][4];
+    // DIAG: slab kUpRightPath at the column left of the tile (clamped to column 0 at x0 = 0, where the value is not used) -- wave-uniform row-0 base,
+    // the lane's 16 bytes at d0; dg_rd = where the lane group left of this one put its bytes (xl = 0 reads its own entry and discards it)
+    const uint8_t *pc0 = nullptr;
+    unsigned lo_c = (unsigned)d0;
+    v4u cv = {0u, 0u, 0u, 0u};
+    bool colz = true;   // block-uniform: the pixel left of the tile starts the path (x0 = 0, or the row under it is past the image)
+    const int dg_wr = (int)threadIdx.x, dg_rd = xl == 0 ? dg_wr : dg_wr - LPP;
+    if constexpr (DIAG) pc0 = a.slabs.frame[frame] + uniform((ptrdiff_t)kUpRightPath * (ptrdiff_t)g.slab_bytes + (ptrdiff_t)max(x0 - 1, 0) * D);
+    auto load_col = [&](int yy) {
+        const uint8_t *pc = pc0 + (ptrdiff_t)yy * sw.row_bytes;
+        return __builtin_nontemporal_load((const CART_GLOBAL v4u *)((const CART_GLOBAL char *)sgpr(pc) + pin_v(lo_c)));
+    };
 
     // the path's state under the band: nothing below the image's last row (the scan starts there, oracle S4), else the checkpoint row y1
     uint32_t st[8], mm = 0;
@@ -436,8 +469,19 @@ __global__ __launch_bounds__(64 * LPP, 4) void wta_band_kernel(BandArgs a) {
         }
         mm = path_min<LPP>(st);
     }
-    sw.template load_slab_row<RECOMP>(y1 - 1, sv);
-    lds_barrier();   // s_rv and s_thr are set up; the first row's loads stay in flight
+    if constexpr (DIAG) {
+        // the diagonal under the band: row y1 of its slab at the lane's own (clamped) column -- the lane group to the right reads it as its
+        // predecessor (x - 1, y1) -- and (x0 - 1, y1) for xl = 0; fresh state when y1 is past the image.  Row y1 is read only when it exists.
+        v4u seed = {0u, 0u, 0u, 0u};
+        if (y1 < g.h) seed = sw.load_slab(y1, kUpRightPath);
+        cv = load_col(min(y1, g.h - 1));
+        colz = x0 == 0 || y1 >= g.h;
+        sw.template load_slab_row<RECOMP, DIAG>(y1 - 1, sv);
+        s_dg[y1 & 1][dg_wr] = seed;   // (after the band's first slab loads have been issued: the store waits for the seed)
+    } else {
+        sw.template load_slab_row<RECOMP>(y1 - 1, sv);
+    }
+    lds_barrier();   // s_rv and s_thr (and the seed of s_dg) are set up; the first row's loads stay in flight
 
     auto row = [&](int y, auto last_c) {
         constexpr bool LAST = decltype(last_c)::value;   // the band's top row: nothing left to prefetch (every VMEM instruction of the body unconditional)
@@ -452,15 +496,40 @@ __global__ __launch_bounds__(64 * LPP, 4) void wta_band_kernel(BandArgs a) {
             uint32_t xr[16];
             agg_xor(c, xr);
             if constexpr (!LAST) sw.load_census_row(y - 1, cw, cfl);
-            agg_step<LPP, false>(st, mm, xr, sw.sel_lo, sw.sel_hi, sw.p1p1, sw.p2p2, nullptr);
-            sum_from_state(sm, st);
+            if constexpr (DIAG) {
+                uint32_t mc[8];   // the pixel's matching costs, once for both recurrences: the pairs agg_step builds from its popcounts
+#pragma unroll
+                for (int i = 0; i < 8; ++i) mc[i] = ((uint32_t)__builtin_popcount(xr[7 - i]) << 16) + (uint32_t)__builtin_popcount(xr[15 - i]);
+                (void)agg_step_c<LPP>(st, mm, mc, sw.sel_lo, sw.sel_hi, sw.p1p1, sw.p2p2);
+                sum_from_state(sm, st);
+                // the diagonal: predecessor bytes from the lane group to the left (LDS) or, for xl = 0, from the column left of the tile
+                const v4u nb = s_dg[(y + 1) & 1][dg_rd];
+                const bool edge = xl == 0;
+                uint32_t pv[4], ds[8];
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    pv[q] = edge ? (colz ? 0u : cv[q]) : nb[q];
+                    ds[2 * q] = perm(0u, pv[q], 0x0c010c00u);       // slab dword q = the low bytes of (ds[2q], ds[2q+1]), as the checkpoint above
+                    ds[2 * q + 1] = perm(0u, pv[q], 0x0c030c02u);
+                }
+                uint32_t dm = path_min<LPP>(ds);
+                const v4u dq = agg_step_c<LPP>(ds, dm, mc, sw.sel_lo, sw.sel_hi, sw.p1p1, sw.p2p2);
+                s_dg[y & 1][dg_wr] = dq;
+                sum_add_slab(sm, dq);
+            } else {
+                agg_step<LPP, false>(st, mm, xr, sw.sel_lo, sw.sel_hi, sw.p1p1, sw.p2p2, nullptr);
+                sum_from_state(sm, st);
+            }
         } else {
 #pragma unroll
             for (int k = 0; k < 8; ++k) sm[k] = 0;
         }
 #pragma unroll
         for (int k = 0; k < NS; ++k) sum_add_slab(sm, sv[k]);
-        if constexpr (!LAST) sw.template load_slab_row<RECOMP>(y - 1, sv);
+        if constexpr (!LAST) {
+            if constexpr (DIAG) cv = load_col(y);   // (x0 - 1, y): the predecessor of the tile's first column on row y - 1
+            sw.template load_slab_row<RECOMP, DIAG>(y - 1, sv);
+        }
         v4u *dst = reinterpret_cast<v4u *>(s_sum + xl * DP + d0);  // LDS tile in natural disparity order
         dst[0] = v4u{sm[0], sm[1], sm[2], sm[3]};
         dst[1] = v4u{sm[4], sm[5], sm[6], sm[7]};
@@ -481,14 +550,17 @@ __global__ __launch_bounds__(64 * LPP, 4) void wta_band_kernel(BandArgs a) {
             if (p >= 0 && p < g.w && best != 0xffffffffu) atomicMin(&a.right_pk[(size_t)frame * g.npx + (size_t)y * g.w + p], best);
         }
     };
-    for (int y = y1 - 1; y > y0; --y) row(y, std::false_type{});
+    for (int y = y1 - 1; y > y0; --y) {
+        row(y, std::false_type{});
+        if constexpr (DIAG) colz = x0 == 0;   // rows above the band's first have a row under them
+    }
     row(y0, std::true_type{});
 }
 
 bool wta_band_supported(const Geometry &g, int K, bool probe) { return g.D == 128 && g.P == kMaxPaths && (K == 4 || K == 8 || K == 16 || (probe && K == 1)); }
 
 void launch_wta_band(const uint32_t *cen_l, const uint32_t *cen_r, const SlabTable &slabs, uint16_t *wta_l, uint32_t *right_pk,
-                     const Geometry &g, const uint16_t *thr, int n_frames, int K, bool probe, hipStream_t s) {
+                     const Geometry &g, const uint16_t *thr, int n_frames, int K, bool probe, bool diag, hipStream_t s) {
     dim3 grid((g.w + kWtaTileX - 1) / kWtaTileX, (g.h + K - 1) / K, n_frames), block(64 * (g.D / 16));
     BandArgs a{cen_l, cen_r, slabs, wta_l, right_pk, g, thr};
     if (probe) {
@@ -497,6 +569,14 @@ void launch_wta_band(const uint32_t *cen_l, const uint32_t *cen_r, const SlabTab
             case 4: hipLaunchKernelGGL((wta_band_kernel<8, 4, false>), grid, block, 0, s, a); break;
             case 8: hipLaunchKernelGGL((wta_band_kernel<8, 8, false>), grid, block, 0, s, a); break;
             default: hipLaunchKernelGGL((wta_band_kernel<8, 16, false>), grid, block, 0, s, a); break;
+        }
+        return;
+    }
+    if (diag) {
+        switch (K) {
+            case 4: hipLaunchKernelGGL((wta_band_kernel<8, 4, true, true>), grid, block, 0, s, a); break;
+            case 8: hipLaunchKernelGGL((wta_band_kernel<8, 8, true, true>), grid, block, 0, s, a); break;
+            default: hipLaunchKernelGGL((wta_band_kernel<8, 16, true, true>), grid, block, 0, s, a); break;
         }
         return;
     }

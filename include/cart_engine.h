@@ -70,8 +70,11 @@ void cart_engine_destroy(cart_engine *engine);
  *   SLABS     all P path slabs are written by the aggregation launch and read by the WTA launch (2*P*D bytes / pixel);
  *   FUSED_UP  the "up" path is computed inside the WTA sweep and never stored (2*(P-1)*D bytes / pixel);
  *   BAND_UP   the "up" path is stored on every K-th row only (checkpoints, in place in its slab) and recomputed in registers by a
- *             WTA that works on tiles of 64 columns x K rows (2*(P-1 + 1/K)*D bytes / pixel).  D = 128 with 8 paths only: any
- *             other engine answers SLABS.
+ *             WTA that works on tiles of 64 columns x K rows.  The aggregation launch WRITES (P-1 + 1/K)*D bytes / pixel.  The WTA
+ *             READS less than that: it also rebuilds the up-right diagonal {+1, -1} inside its tile (CART_OPT_BAND_DIAG, default 1) and
+ *             takes from that path's slab only the row under each band and the column left of each tile:
+ *             (P-2 + 2/K + 1/64)*D bytes / pixel, 6.27 instead of 7.125 slabs at K = 8.  The slab is still written in full, and
+ *             cart_engine_describe_plan still reports P-1 slabs.  D = 128 with 8 paths only: any other engine answers SLABS.
  * AUTO picks per launch from the measured table in DESIGN.md section 4.  Options are plain integers so that the
  * boundary stays C; nothing in the engine reads the environment.
  */
@@ -91,8 +94,11 @@ enum {
     CART_OPT_BAND_ROWS = 6,                 /* K of plan BAND_UP: 4, 8 or 16 rows per band (default: the measured winner); 1 with the probe */
     CART_OPT_BAND_PROBE = 7,                /* measurement only, 1: plan BAND_UP stores and reads all P slabs and recomputes nothing -- the two-kernel WTA's
                                                work in K-row tiles (the read-rate probe of DESIGN.md 8); describe_plan then reports P slabs */
-    CART_OPT_FLOW_GATHER = 8                /* tests and measurements, 1: the refinement kernel of cart_optical_flow_pyramid never stages the previous
+    CART_OPT_FLOW_GATHER = 8,               /* tests and measurements, 1: the refinement kernel of cart_optical_flow_pyramid never stages the previous
                                                features in LDS and gathers them from global memory in every tile (same bits; default 0: per tile) */
+    CART_OPT_BAND_DIAG = 9                  /* 0 | 1 (default 1): the WTA of plan BAND_UP rebuilds the up-right diagonal path in LDS instead of reading its
+                                               slab (same bits; what the aggregation launch writes does not change).  Ignored with CART_OPT_BAND_PROBE;
+                                               engines that never take BAND_UP accept and ignore it */
 };
 int cart_engine_set_option(cart_engine *engine, int option, int value);
 int cart_engine_get_option(cart_engine *engine, int option, int *value);
@@ -101,8 +107,9 @@ int cart_engine_get_option(cart_engine *engine, int option, int *value);
 typedef struct {
     int frames_per_launch;
     int plan;             /* CART_PLAN_SLABS | FUSED_UP | BAND_UP */
-    int slabs_written;    /* u8 slabs of D bytes per pixel written (and read once) per frame.  BAND_UP reports P - 1: its checkpoint rows are
-                             1/K of one more slab, which this integer cannot say (bench.py's moved_bytes is 1.6 % low at K = 8) */
+    int slabs_written;    /* u8 slabs of D bytes per pixel written per frame (and, except under BAND_UP, read once).  BAND_UP reports P - 1: its
+                             checkpoint rows are 1/K of one more slab, which this integer cannot say, and with CART_OPT_BAND_DIAG its WTA reads
+                             only P - 2 + 2/K + 1/64 slabs (bench.py's moved_bytes, priced as written = read, is 3.4 % high at K = 8) */
 } cart_launch_plan;
 int cart_engine_describe_plan(cart_engine *engine, int n_frames, cart_launch_plan *out);
 
